@@ -10,7 +10,7 @@ count), 10M reads per GPU.  `--db-window 0 --genome-len 262144` is the heavier e
 were tuned on (2.3e8 keys from 2.7e8 bases: every k-mer of a read is in the db); both are reported in
 DESIGN.md.  N>1: one process per GPU, db RCCL-broadcast from rank 0, reads sharded, per-step gather of the taxids to
 rank 0.  Weak scaling by default (--reads per GPU); `--scaling strong --total-reads T` shards a fixed total (configs[3]:
-"1B reads sharded").  An N>1 line carries `per_rank`: every rank's kernel time and roofline fraction, and a parity sample
+"1B reads sharded").  An N>1 line carries `per_rank`: every rank's kernel time and roofline fraction, and (--full) a parity sample
 per rank -- rank 0 regenerates the first reads of rank r's last batch from the seed, classifies them itself and with the CPU
 oracle, and compares both with the slice of the GATHERED result that came from rank r: a wrong broadcast, shard or gather
 cannot print a fine-looking number.  BNS_BENCH_FORCE_DIST=1 runs the same collectives at world size 1 (how a one-GPU box
@@ -21,7 +21,8 @@ through torch.distributed.run on 127.0.0.1 and fails loudly when the node has fe
 `python -m torch.distributed.run ... bench.py --gpus N` it is one of the ranks.  `n_gpus` in the output is the world size
 RCCL actually formed.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps and prints it; --full adds the checks and legs
+that the headline figure does not need (CPU oracle parity and baseline, probe roofline, text / inflate / gzip legs).
 """
 import argparse
 import json
@@ -105,9 +106,18 @@ def parse():
                                                               "(FASTQ, 314 bytes per 150-bp record) and what the timed kernel says about them as DIR/taxa.u32")
     ap.add_argument("--dry-run-world", type=int, default=0,
                     help="walk the N-rank job on THIS node's one GPU: W ranks (gloo rendezvous, all on device 0), the db at 1/W of its size, "
-                         "--reads / W per rank, a few steps -- launch, shard bounds, broadcast sizes, gather buffers and the per-rank parity "
-                         "sample of the real run, none of its numbers (the line says so)")
+                         "--reads / W per rank, a few steps -- launch, shard bounds, broadcast sizes, gather buffers and (--full) the per-rank "
+                         "parity sample of the real run, none of its numbers (the line says so)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU oracle's parity sample and baseline (and the reference's "
+                         "compiled functions), the standalone probe-kernel roofline, the text-path, BGZF-inflate and gzip-stream legs, "
+                         "and the N>1 per-rank parity samples.  Off: set up, warm up, time --steps, print the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/{taxon,missing,ambig}.npy (float64) for a fixed, "
+                         "seeded sample of at most 2^20 reads (the sampled read numbers as DIR/read_index.npy); N>1: rank 0's shard")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.dry_run_world > 0:
         W = a.dry_run_world
         shrink = max(0, int(np.ceil(np.log2(W))))
@@ -651,6 +661,21 @@ def oracle_check(O, table, tax, k, gaps, paired, d_bases, d_offsets, S, got_t, g
     return mism, best, res["taxon"]
 
 
+def dump_outputs(d, n_units, taxon, missing, ambig, sample=1 << 20):
+    """what the last timed step handed its caller (per read or pair: taxon, missing, ambig, all u32) as float64 .npy files, for
+    output-for-output comparison of two builds: all of it up to `sample` units, else a fixed seeded sample of that many (32 MiB with the index)"""
+    os.makedirs(d, exist_ok=True)
+    if n_units > sample:
+        idx = np.sort(np.random.default_rng(101).choice(n_units, sample, replace=False))
+    else:
+        idx = np.arange(n_units)
+    torch.cuda.synchronize()
+    it = torch.from_numpy(idx).to(taxon.device)
+    np.save(os.path.join(d, "read_index.npy"), idx.astype(np.float64))
+    for name, t in (("taxon", taxon), ("missing", missing), ("ambig", ambig)):
+        np.save(os.path.join(d, name + ".npy"), t[:n_units][it].cpu().numpy().view(np.uint32).astype(np.float64))
+
+
 def main():
     a = parse()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -941,6 +966,8 @@ def main():
     dt = time.perf_counter() - t0
     ksum_ms, kcount = ctx.timing_summary()
     ctx.set_timing(False)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, n_units, taxons[(a.steps - 1) & 1], missing, ambig)
     fetch_dbg = None
     if hasattr(ctx.L, "bns_debug_fetch_count"):     # measurement build only (-DBNS_COUNT_FETCHES, tools/measure.sh)
         import ctypes
@@ -1054,7 +1081,7 @@ def main():
         out["debug_fetch_count"] = fetch_dbg
 
     oracle = None
-    if rank == 0 and not a.no_cpu:
+    if rank == 0 and a.full and not a.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
         hf, hk, hv = host_arrays if host_arrays is not None else (flags.cpu().numpy().view(np.uint32), keys.cpu().numpy().view(np.uint64),
@@ -1062,7 +1089,7 @@ def main():
         oracle = (O, O.Table.wrap(int(hdr[0]), int(hdr[2]), int(hdr[1]), int(hdr[3]), hf, hk, hv),
                   O.Taxonomy(pairs=[(int(c), int(p)) for c, p in enumerate(parent) if p != 0xFFFFFFFF and c != 0]))
 
-    # ---- N>1 (or the forced one-rank group): every rank's kernel time, and per rank a parity sample taken from the GATHERED
+    # ---- N>1 (or the forced one-rank group): every rank's kernel time, and (--full) per rank a parity sample taken from the GATHERED
     # result -- rank 0 re-derives the head of rank r's last batch from its seed, classifies it on its own GPU and (unless
     # --no-cpu) with the oracle, and compares both with what the gather delivered for rank r
     if multi:
@@ -1076,7 +1103,7 @@ def main():
             last_b = last_j % n_batches
             inc = 2 if a.paired else 1
             for r in range(world):
-                S = min(a.rank_sample, sizes[r] * inc)
+                S = min(a.rank_sample, sizes[r] * inc) if a.full else 0
                 S -= S % 2
                 if S <= 0:
                     continue
@@ -1107,11 +1134,11 @@ def main():
 
     # ---- standalone probe kernel (the metric's "% HBM roofline on probe"), rank 0 at N=1: keys WITHOUT read locality
     # (half present, half random 62-bit misses), so every lookup fetches its own 128-byte bucket
-    if rank == 0 and world == 1 and not a.no_probe and a.layout == "minbucket" and not a.spacing and not a.stream_load:
+    if rank == 0 and world == 1 and a.full and not a.no_probe and a.layout == "minbucket" and not a.spacing and not a.stream_load:
         out["probe_roofline"] = probe_leg(ctx, a, dev, stream, flags, keys, nb, float(hdr[2]) / nb)
 
     # ---- the text path at the C ABI (rank 0, N=1, the default single-end fixed-length shape)
-    if rank == 0 and world == 1 and not a.no_text and not a.paired and not a.spacing and a.len_dist == "fixed" and not a.packed and a.emulate_rank < 0:
+    if rank == 0 and world == 1 and a.full and not a.no_text and not a.paired and not a.spacing and a.len_dist == "fixed" and not a.packed and a.emulate_rank < 0:
         try:
             torch.cuda.synchronize()
             lj_t = (a.steps - 1) & 1
@@ -1124,7 +1151,7 @@ def main():
             out["text_path"] = {"error": str(e)[:200]}
 
     # ---- BGZF members inflated on the device (rank 0, N=1)
-    if rank == 0 and world == 1 and not a.no_inflate and a.emulate_rank < 0:
+    if rank == 0 and world == 1 and a.full and not a.no_inflate and a.emulate_rank < 0:
         try:
             torch.cuda.synchronize()
             il = inflate_leg(ctx.L, local)

@@ -88,7 +88,7 @@ def test_two_ranks_one_device_hip_path(paired):
 def test_bench_self_launch_two_ranks():
     """bench.py --gpus 2 without torchrun: refuses on a 1-GPU node, and with the one-device debug mapping launches 2 ranks itself."""
     small = ["--genomes", "32", "--genome-len", "65536", "--log2-buckets", "22", "--reads", "40000", "--steps", "2", "--warmup", "1",
-             "--no-cpu", "--no-probe"]
+             "--no-cpu", "--no-probe", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     if torch.cuda.device_count() < 2:
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + small, env=env, capture_output=True, timeout=600)
@@ -119,7 +119,7 @@ def test_bench_rccl_collectives_at_world_one():
     gather, all_gather_object / all_reduce of the timings -- and the per-rank parity sample (gathered slice vs re-derived reads,
     on the GPU and with the CPU oracle) must be clean."""
     small = ["--genomes", "32", "--genome-len", "65536", "--log2-buckets", "22", "--reads", "60000", "--steps", "3", "--warmup", "1",
-             "--no-probe", "--cpu-sample", "20000", "--rank-sample", "30000", "--no-ref"]
+             "--no-probe", "--cpu-sample", "20000", "--rank-sample", "30000", "--no-ref", "--full"]
     out, err = _bench(small, {"BNS_BENCH_FORCE_DIST": "1"})
     assert out["n_gpus"] == 1 and "error" not in out
     pr = out["per_rank"]
@@ -128,10 +128,30 @@ def test_bench_rccl_collectives_at_world_one():
     assert out["parity_sample"]["mismatches"] == 0 and pr[0]["parity_sample"]["classified_frac"] > 0.5
 
 
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain bench.py run times its steps and nothing else (the legs and checks are --full's); --dump-outputs writes what the last
+    timed step computed for a seeded sample of 2^20 of its 1.1 M reads, the same from run to run whatever else the run does."""
+    small = ["--genomes", "32", "--genome-len", "65536", "--log2-buckets", "22", "--reads", "1100000", "--steps", "3", "--warmup", "1"]
+    d1, d2 = str(tmp_path / "plain"), str(tmp_path / "full")
+    out, _ = _bench(small + ["--dump-outputs", d1], {})
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and "error" not in out
+    assert not {"cpu_baseline", "parity_sample", "probe_roofline", "text_path", "inflate_path", "gz_stream_path"} & set(out)
+    full, _ = _bench(small + ["--full", "--no-ref", "--no-probe", "--no-text", "--no-inflate", "--cpu-sample", "40000", "--dump-outputs", d2], {})
+    assert full["parity_sample"]["reads"] == 40000 and full["parity_sample"]["mismatches"] == 0 and "error" not in full
+    got = {}
+    for name in ("read_index", "taxon", "missing", "ambig"):
+        a1, a2 = np.load(os.path.join(d1, name + ".npy")), np.load(os.path.join(d2, name + ".npy"))
+        assert a1.dtype == np.float64 and a1.shape == (1 << 20,) and np.array_equal(a1, a2), name
+        got[name] = a1
+    idx = got["read_index"]
+    assert idx[0] >= 0 and idx[-1] < 1_100_000 and (np.diff(idx) > 0).all()
+    assert (got["taxon"] != 0).mean() > 0.9
+
+
 def test_bench_strong_scaling_two_ranks():
     """--scaling strong --total-reads T: the total is sharded (uneven shards allowed), value counts T per step"""
     small = ["--genomes", "32", "--genome-len", "65536", "--log2-buckets", "22", "--scaling", "strong", "--total-reads", "50001",
-             "--steps", "2", "--warmup", "1", "--no-cpu", "--no-probe", "--rank-sample", "5000"]
+             "--steps", "2", "--warmup", "1", "--no-cpu", "--no-probe", "--rank-sample", "5000", "--full"]
     out, err = _bench(["--gpus", "2"] + small, {"BNS_BENCH_ONE_DEVICE": "1", "BNS_BENCH_BACKEND": "gloo"})
     assert out["scaling"] == "strong" and out["n_gpus"] == 2 and out["config"]["total_reads_per_step"] == 50001
     assert sorted(r["reads"] for r in out["per_rank"]) == [25000, 25001] and "error" not in out
@@ -142,7 +162,7 @@ def test_bench_eight_ranks_one_device():
     """bench.py --dry-run-world 8: the 8-rank job walked on the one GPU there is -- eight processes (gloo rendezvous, all on device 0), the
     db at 1/8 of its size broadcast from rank 0, eight shards, the double-buffered gather, and the per-rank parity sample of the gathered
     result against reads re-derived on rank 0; every rank says where it runs (device, PCI id, NUMA node, CPUs, collective library)"""
-    out, err = _bench(["--dry-run-world", "8", "--genome-len", "65536", "--log2-buckets", "24", "--reads", "6400000"], {}, timeout=1500)
+    out, err = _bench(["--dry-run-world", "8", "--genome-len", "65536", "--log2-buckets", "24", "--reads", "6400000", "--full"], {}, timeout=1500)
     assert out["n_gpus"] == 8 and "error" not in out and "dry_run" in out
     assert [r["rank"] for r in out["per_rank"]] == list(range(8))
     assert out["collectives"]["shard_units"] == [r["shard"]["units"] for r in out["per_rank"]] and sum(out["collectives"]["shard_units"]) == out["config"]["total_reads_per_step"]

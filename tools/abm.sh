@@ -7,8 +7,8 @@ show() { python -c "
 import sys,json
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); c=d['config']; print('%-12s %-22s kernel %.3f ms  m=%s spilled %d ovf %s parity %s' % ('$1', '$2', d['roofline']['kernel_ms'], c['table_minimizer_m'], c['table_spilled_keys'], c['table_overflow_keys'], d.get('parity_sample')))"; }
 for lib in $LIBS; do
-  BONSAI_AMD_LIB=$PWD/bonsai_amd/lib/$lib python bench.py --steps 3 --warmup 1 --no-probe --cpu-sample 200000 2>/dev/null | show $lib "default(parity)"
-  BONSAI_AMD_LIB=$PWD/bonsai_amd/lib/$lib python bench.py --steps 3 --warmup 1 --no-probe --cpu-sample 200000 $AK 2>/dev/null | show $lib "allkmers(parity)"
+  BONSAI_AMD_LIB=$PWD/bonsai_amd/lib/$lib python bench.py --full --steps 3 --warmup 1 --no-probe --cpu-sample 200000 2>/dev/null | show $lib "default(parity)"
+  BONSAI_AMD_LIB=$PWD/bonsai_amd/lib/$lib python bench.py --full --steps 3 --warmup 1 --no-probe --cpu-sample 200000 $AK 2>/dev/null | show $lib "allkmers(parity)"
 done
 for rep in 1 2 3; do
   for lib in $LIBS; do

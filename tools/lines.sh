@@ -7,7 +7,7 @@ rm -rf "$O"; mkdir -p "$O"
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout 2400 python -m pytest tests -m gpu -x -q > "$O/pytest.log" 2>&1; echo "pytest rc=$?" | tee -a "$O/pytest.log"; tail -15 "$O/pytest.log"
 fi
-run() { name=$1; shift; timeout 900 python bench.py "$@" > "$O/$name.json" 2> "$O/$name.err"; echo "$name rc=$?"; python tools/_line.py "$O/$name.json"; tail -2 "$O/$name.err"; }
+run() { name=$1; shift; timeout 900 python bench.py --full "$@" > "$O/$name.json" 2> "$O/$name.err"; echo "$name rc=$?"; python tools/_line.py "$O/$name.json"; tail -2 "$O/$name.err"; }
 run default
 run wide52 --identity 52 --no-cpu --no-probe
 run load34 --table-buckets 66000000 --no-cpu --no-probe

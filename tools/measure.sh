@@ -20,7 +20,7 @@ if [ ! -f bonsai_amd/lib/libbonsai_amd_count.so ] || [ bonsai_amd/csrc/bns_kerne
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout 1500 python -m pytest tests -m gpu -x -q > "$O/pytest.log" 2>&1; echo "pytest rc=$?" | tee -a "$O/pytest.log"; tail -3 "$O/pytest.log"
 fi
-timeout 900 python bench.py > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"; cut -c1-600 "$O/bench.json"
+timeout 900 python bench.py --full > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"; cut -c1-600 "$O/bench.json"
 PASSES=(
  "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum"
  "FETCH_SIZE TCC_BUBBLE_sum"
@@ -40,19 +40,19 @@ for pass in "${PASSES[@]}"; do
 done
 tools/micro/bin/gather_calib 29 200 > "$O/calib_plain.log" 2>&1
 # the standalone probe kernel under the read-request counters (bench with its probe leg, 2 steps)
-timeout 600 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_32B_sum --kernel-trace --output-format csv -d "$O/probe_pmc" -o bench -- python bench.py --no-cpu --no-text --no-inflate --steps 2 --warmup 1 > "$O/probe_pmc.log" 2>&1
+timeout 600 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_32B_sum --kernel-trace --output-format csv -d "$O/probe_pmc" -o bench -- python bench.py --full --no-cpu --no-text --no-inflate --steps 2 --warmup 1 > "$O/probe_pmc.log" 2>&1
 # configs[2] (spaced, paired) bench line + its kernel-trace stats
-timeout 600 python bench.py --spacing 1x15,0x15 --paired --log2-buckets 31 --no-probe --steps 10 > "$O/bench_c2.json" 2> "$O/bench_c2.err"
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_c2" -o bench -- python bench.py --spacing 1x15,0x15 --paired --log2-buckets 31 --no-cpu --no-probe --steps 10 > "$O/bench_kt_c2.log" 2>&1
-timeout 600 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum --kernel-trace --output-format csv -d "$O/c2_pmc" -o bench -- python bench.py --spacing 1x15,0x15 --paired --log2-buckets 31 --no-cpu --no-probe --steps 2 --warmup 1 > "$O/c2_pmc.log" 2>&1
+timeout 600 python bench.py --full --spacing 1x15,0x15 --paired --log2-buckets 31 --no-probe --steps 10 > "$O/bench_c2.json" 2> "$O/bench_c2.err"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_c2" -o bench -- python bench.py --full --spacing 1x15,0x15 --paired --log2-buckets 31 --no-cpu --no-probe --steps 10 > "$O/bench_kt_c2.log" 2>&1
+timeout 600 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum --kernel-trace --output-format csv -d "$O/c2_pmc" -o bench -- python bench.py --full --spacing 1x15,0x15 --paired --log2-buckets 31 --no-cpu --no-probe --steps 2 --warmup 1 > "$O/c2_pmc.log" 2>&1
 j=0
 for pass in "${SQPASSES[@]}"; do
   timeout 600 rocprofv3 --pmc $pass --kernel-trace --output-format csv -d "$O/bench_sq$j" -o bench -- python bench.py --no-cpu --no-probe --no-text --no-inflate --steps 2 --warmup 1 > "$O/bench_sq$j.log" 2>&1
   j=$((j+1))
 done
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -o bench -- python bench.py --no-cpu --no-text > "$O/bench_kt.log" 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -o bench -- python bench.py --full --no-cpu --no-text > "$O/bench_kt.log" 2>&1
 if [ -f bonsai_amd/lib/libbonsai_amd_count.so ]; then
-  BONSAI_AMD_LIB=$PWD/bonsai_amd/lib/libbonsai_amd_count.so timeout 600 python bench.py --no-cpu --no-probe --no-text --steps 4 --warmup 1 > "$O/bench_count.json" 2> "$O/bench_count.err"
+  BONSAI_AMD_LIB=$PWD/bonsai_amd/lib/libbonsai_amd_count.so timeout 600 python bench.py --full --no-cpu --no-probe --no-text --steps 4 --warmup 1 > "$O/bench_count.json" 2> "$O/bench_count.err"
   cut -c1-200 "$O/bench_count.json"; grep -o '"debug_fetch_count.*' "$O/bench_count.json"
 fi
 # keep what goes back small: drop the per-dispatch traces of torch's own kernels

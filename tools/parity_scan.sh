@@ -1,7 +1,7 @@
 #!/bin/bash
 # in-bench parity sample (GPU vs oracle at full table size) over read lengths and modes.  usage: tools/parity_scan.sh
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-run() { python bench.py --steps 3 --warmup 1 --no-probe --reads 1000000 --cpu-sample 100000 "$@" 2>/dev/null | grep "^{" | tail -1 | python -c "
+run() { python bench.py --full --steps 3 --warmup 1 --no-probe --reads 1000000 --cpu-sample 100000 "$@" 2>/dev/null | grep "^{" | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); print('$*', d['parity_sample'], 'err' if 'error' in d else 'ok')"; }
 for L in 31 32 62 94 95 101 151 158 159 250 1000 2100 4200; do run --read-len $L; done

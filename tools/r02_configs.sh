@@ -14,7 +14,7 @@ mkdir -p "$O"; : > "$O/configs.jsonl"
 run() {
   name=$1; shift
   echo "== $name: $*"
-  line=$(timeout 900 python bench.py --steps 10 --warmup 2 --no-probe "$@" 2> "$O/$name.err" | grep '^{' | tail -1)
+  line=$(timeout 900 python bench.py --full --steps 10 --warmup 2 --no-probe "$@" 2> "$O/$name.err" | grep '^{' | tail -1)
   if [ -z "$line" ]; then line='null'; tail -3 "$O/$name.err"; fi
   printf '{"name": "%s", "args": "%s", "bench": %s}\n' "$name" "$*" "$line" >> "$O/configs.jsonl"
   echo "$line" | python -c "

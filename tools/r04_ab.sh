@@ -11,7 +11,7 @@ if [ "$MODE" != "notest" ]; then
 fi
 shape() { name=$1; shift
   for lib in $LIBS; do
-    BONSAI_AMD_LIB=$PWD/bonsai_amd/lib/$lib python bench.py --steps 3 --warmup 1 --no-probe --cpu-sample 200000 "$@" 2>&1 | tail -1 | python -c "
+    BONSAI_AMD_LIB=$PWD/bonsai_amd/lib/$lib python bench.py --full --steps 3 --warmup 1 --no-probe --cpu-sample 200000 "$@" 2>&1 | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print('$name $lib parity', d.get('parity_sample'), d.get('error'))"
   done

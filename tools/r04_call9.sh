@@ -6,13 +6,13 @@ timeout 2400 python -m pytest tests -m gpu -q -x --deselect tests/test_gpu_scale
 LIBS="libbonsai_amd_v2.so libbonsai_amd.so"
 shape() { name=$1; shift
   for rep in 1 2; do for lib in $LIBS; do
-    BONSAI_AMD_LIB=$PWD/bonsai_amd/lib/$lib timeout 900 python bench.py --no-probe --steps 5 --warmup 1 --cpu-sample 200000 "$@" 2>/dev/null | tail -1 > "$O/$name.$lib.$rep.json"; echo -n "$name:$lib "; python tools/_line.py "$O/$name.$lib.$rep.json"
+    BONSAI_AMD_LIB=$PWD/bonsai_amd/lib/$lib timeout 900 python bench.py --full --no-probe --steps 5 --warmup 1 --cpu-sample 200000 "$@" 2>/dev/null | tail -1 > "$O/$name.$lib.$rep.json"; echo -n "$name:$lib "; python tools/_line.py "$O/$name.$lib.$rep.json"
   done; done; }
 shape allk34 --genome-len 262144 --db-window 0 --table-buckets 67000000
 shape allk34p --genome-len 262144 --db-window 0 --table-buckets 67000000 --paired
 shape big8e9 --genomes 36000 --genome-len 262144 --db-window 0 --log2-buckets 34 --stream-load
 BIG="--genomes 36000 --genome-len 262144 --db-window 0 --log2-buckets 34 --stream-load --no-probe --no-cpu --steps 3 --warmup 1"
-BONSAI_AMD_LIB=$PWD/bonsai_amd/lib/libbonsai_amd_count.so timeout 900 python bench.py $BIG > "$O/count_8e9.json" 2> "$O/count_8e9.err"; grep -o '"debug_fetch_count.*' "$O/count_8e9.json" | cut -c1-400
+BONSAI_AMD_LIB=$PWD/bonsai_amd/lib/libbonsai_amd_count.so timeout 900 python bench.py --full $BIG > "$O/count_8e9.json" 2> "$O/count_8e9.err"; grep -o '"debug_fetch_count.*' "$O/count_8e9.json" | cut -c1-400
 # container path: one vs two contexts on the device (is the caller thread or the link the limit?)
 python - <<'PY' 2>&1 | cut -c1-250
 import os, subprocess, sys, time

@@ -5,7 +5,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/${1:-fillab}
 rm -rf "$O"; mkdir -p "$O"
-run() { name=$1; shift; echo "$*" > "$O/$name.args"; timeout 900 python bench.py "$@" > "$O/$name.json" 2> "$O/$name.err"; echo "$name rc=$?"; python tools/_line.py "$O/$name.json"; }
+run() { name=$1; shift; echo "$*" > "$O/$name.args"; timeout 900 python bench.py --full "$@" > "$O/$name.json" 2> "$O/$name.err"; echo "$name rc=$?"; python tools/_line.py "$O/$name.json"; }
 S="--no-probe --no-cpu --steps 20 --warmup 2"
 AK="--genome-len 262144 --db-window 0"
 for d in 0x10 0 0x8010 0x8000; do

@@ -15,7 +15,7 @@ STEP=${STEPS:-1234}
 if [[ $STEP == *1* ]]; then
   timeout 900 python -m pytest tests/test_gpu_scale.py -m gpu -q -x -k "config1 or config2" > "$O/pytest_shapes.log" 2>&1; echo "shape tests rc=$?"; tail -3 "$O/pytest_shapes.log"
 fi
-run() { name=$1; shift; timeout 1500 python bench.py --no-probe "$@" > "$O/$name.json" 2> "$O/$name.err"; echo "$name rc=$?"; python tools/_line.py "$O/$name.json"; grep "bench.py:" "$O/$name.err" | head -3; }
+run() { name=$1; shift; timeout 1500 python bench.py --full --no-probe "$@" > "$O/$name.json" 2> "$O/$name.err"; echo "$name rc=$?"; python tools/_line.py "$O/$name.json"; grep "bench.py:" "$O/$name.err" | head -3; }
 if [[ $STEP == *2* ]]; then
   S3="--scaling strong --total-reads 1000000000 --world 8 --steps 3 --warmup 1 --cpu-sample 200000"
   run c3_w50_2e9_r0 --genomes 10240 --log2-buckets 32 $S3 --emulate-rank 0
@@ -26,7 +26,7 @@ fi
 if [[ $STEP == *3* ]]; then
   run c4_len10k --read-len 10000 --reads 100000 --steps 10 --cpu-sample 20000
   run c4_len10k_allk --read-len 10000 --reads 100000 --steps 10 --cpu-sample 20000 --genome-len 262144 --db-window 0
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_len10k" -o b -- python bench.py --no-probe --no-cpu --read-len 10000 --reads 100000 --steps 10 > "$O/kt_len10k.log" 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_len10k" -o b -- python bench.py --full --no-probe --no-cpu --read-len 10000 --reads 100000 --steps 10 > "$O/kt_len10k.log" 2>&1
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_rolling" -o b -- python tools/rolling_bench.py 20000 > "$O/rolling.log" 2>&1; grep -v amdgpu "$O/rolling.log" | tail -4
   find "$O" -name "*_kernel_trace.csv" -size +5M -delete
 fi

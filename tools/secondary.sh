@@ -5,7 +5,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/${1:-r04c}
 rm -rf "$O"; mkdir -p "$O"
-run() { name=$1; shift; echo "$*" > "$O/$name.args"; timeout 1500 python bench.py "$@" > "$O/$name.json" 2> "$O/$name.err"; echo "$name rc=$?"; python tools/_line.py "$O/$name.json"; }
+run() { name=$1; shift; echo "$*" > "$O/$name.args"; timeout 1500 python bench.py --full "$@" > "$O/$name.json" 2> "$O/$name.err"; echo "$name rc=$?"; python tools/_line.py "$O/$name.json"; }
 S="--no-probe --no-cpu"
 run load34 --table-buckets 66000000 $S
 run load17 --table-buckets 132000000 $S
