@@ -151,6 +151,19 @@ class Context:
     def load_taxonomy(self, parent):
         parent = np.ascontiguousarray(parent, dtype=np.uint32)
         self._chk(self.L.bns_load_taxonomy(self.h, _p(parent, u32p), parent.size), "bns_load_taxonomy")
+        self._n_tax = int(parent.size)
+
+    def tally_enable(self, on=True):
+        """bns_tally_enable: count every unit the classify calls report per taxon bin (0 unclassified, n not in the taxonomy)"""
+        self._chk(self.L.bns_tally_enable(self.h, int(bool(on))), "bns_tally_enable")
+
+    def tally(self, reset=False):
+        """bns_tally_read -> (direct, clade): uint64 arrays of n + 1 entries (n = the size of the parent array loaded)"""
+        n = getattr(self, "_n_tax", 0)
+        direct = np.zeros(n + 1, dtype=np.uint64)
+        clade = np.zeros(n + 1, dtype=np.uint64)
+        self._chk(self.L.bns_tally_read(self.h, _p(direct, u64p), _p(clade, u64p), n + 1, int(bool(reset))), "bns_tally_read")
+        return direct, clade
 
     # ---- hot path (host buffers)
     def classify(self, bases, offsets, paired=False, want_hits=False):

@@ -2,6 +2,7 @@
 // Single translation unit for the device library: the kernels are included so their templates are visible.
 #include "../../include/bonsai_amd.h"
 #include "bns_kernels.hip"
+#include "bns_tally.hpp"
 
 #include <dlfcn.h>
 #if defined(__x86_64__)
@@ -115,6 +116,10 @@ struct bns_ctx {
     // taxonomy
     TaxNode *nodes = nullptr;
     u32 n_nodes = 0;
+    u32 tax_clock = 0;              // Euler positions of the forest: tin / tout run over [1, tax_clock]
+    // bns_tally_enable: direct[n_nodes + 1] counts of classified units per bin; clade / scan: bns_tally_read's workspace
+    bool tally_on = false;
+    DevBuf tally_direct, tally_clade, tally_scan;
     // workspace (grow-only)
     DevBuf words, nmask, ovf_list, scratch, small, records;      // small: ovf_count + misc counters
     DevBuf st_bases, st_offsets, st_out[4], st_hits, st_kmers, st_aux, st_runs[4], st_words, st_nmask, st_bad;   // st_words..: packed host batches   // st_runs: run_start, n_runs, run_tax, run_len
@@ -312,7 +317,7 @@ bool launch_fixed_k(const ClassifyParams &p, unsigned grid, hipStream_t st, bool
 
 extern "C" {
 
-int bns_version(void) { return 104; }
+int bns_version(void) { return 105; }
 
 int bns_device_pci_bus_id(int device, char *out, int cap)
 {
@@ -433,7 +438,8 @@ void bns_destroy(bns_ctx *ctx)
     if (ctx->nodes) (void)hipFree(ctx->nodes);
     DevBuf *bufs[] = {&ctx->words, &ctx->nmask, &ctx->ovf_list, &ctx->scratch, &ctx->small, &ctx->records, &ctx->st_bases, &ctx->st_offsets,
                       &ctx->st_out[0], &ctx->st_out[1], &ctx->st_out[2], &ctx->st_out[3], &ctx->st_hits, &ctx->st_kmers, &ctx->st_aux,
-                      &ctx->st_runs[0], &ctx->st_runs[1], &ctx->st_runs[2], &ctx->st_runs[3], &ctx->st_words, &ctx->st_nmask, &ctx->st_bad};
+                      &ctx->st_runs[0], &ctx->st_runs[1], &ctx->st_runs[2], &ctx->st_runs[3], &ctx->st_words, &ctx->st_nmask, &ctx->st_bad,
+                      &ctx->tally_direct, &ctx->tally_clade, &ctx->tally_scan};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->peer_stage) (void)hipHostFree(ctx->peer_stage);
     if (ctx->h_run_tax) (void)hipHostFree(ctx->h_run_tax);
@@ -1188,6 +1194,81 @@ int bns_table_geometry(const bns_ctx *ctx, uint64_t *geo8)
 
 const char *bns_table_warning(const bns_ctx *ctx) { return ctx ? ctx->warn.c_str() : ""; }
 
+}  // extern "C"
+namespace {
+// direct[n_nodes + 1] allocated (kept when it is large enough) and zeroed
+int tally_zero(bns_ctx *ctx)
+{
+    const size_t bytes = ((size_t)ctx->n_nodes + 1) * 8;
+    const int rc = ensure(ctx, ctx->tally_direct, bytes);
+    if (rc != BNS_OK) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->tally_direct.p, 0, bytes, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return BNS_OK;
+}
+
+// the units of one classify launch into the tally, on the launch's stream behind it (neg: out again -- a batch the caller did not take)
+int tally_units(bns_ctx *ctx, const u32 *d_taxon, u64 n_units, hipStream_t st, bool neg = false)
+{
+    if (!ctx->tally_on || n_units == 0) return BNS_OK;
+    const unsigned grid = grid_for(ctx, n_units, TALLY_BLOCK * 16, 2);
+    hipLaunchKernelGGL(tally_kernel, dim3(grid), dim3(TALLY_BLOCK), 0, st, d_taxon, (u64)n_units, (const TaxNode *)ctx->nodes, ctx->n_nodes,
+                       (unsigned long long *)ctx->tally_direct.p, neg ? 1 : 0);
+    HIPCHK(ctx, hipGetLastError());
+    return BNS_OK;
+}
+}  // namespace
+extern "C" {
+
+int bns_tally_enable(bns_ctx *ctx, int on)
+{
+    if (!ctx) return BNS_ERR_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!on) {
+        if (ctx->tally_on) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        release(ctx->tally_direct); release(ctx->tally_clade); release(ctx->tally_scan);
+        ctx->tally_on = false;
+        return BNS_OK;
+    }
+    if (!ctx->nodes) return fail(ctx, BNS_ERR_STATE, "no taxonomy loaded (bns_load_taxonomy)");
+    const int rc = tally_zero(ctx);
+    if (rc != BNS_OK) return rc;
+    ctx->tally_on = true;
+    return BNS_OK;
+}
+
+int bns_tally_read(bns_ctx *ctx, uint64_t *direct, uint64_t *clade, uint32_t len, int reset)
+{
+    if (!ctx) return BNS_ERR_ARG;
+    if (!ctx->tally_on) return fail(ctx, BNS_ERR_STATE, "tally not enabled (bns_tally_enable)");
+    if (len != ctx->n_nodes + 1u) return fail(ctx, BNS_ERR_ARG, "len must be n + 1 (n as given to bns_load_taxonomy)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const u32 n = ctx->n_nodes;
+    const size_t bytes = ((size_t)n + 1) * 8;
+    if (clade) {
+        const u32 n_pos = ctx->tax_clock + 1u;                               // positions 0 (nothing in front of the first tin) .. tax_clock
+        int rc;
+        if ((rc = ensure(ctx, ctx->tally_clade, bytes)) != BNS_OK) return rc;
+        if ((rc = ensure(ctx, ctx->tally_scan, (size_t)n_pos * 8)) != BNS_OK) return rc;
+        unsigned long long *S = (unsigned long long *)ctx->tally_scan.p;
+        const unsigned long long *d = (const unsigned long long *)ctx->tally_direct.p;
+        HIPCHK(ctx, hipMemsetAsync(S, 0, (size_t)n_pos * 8, st));
+        hipLaunchKernelGGL(clade_scatter_kernel, dim3(grid_for(ctx, n, 256)), dim3(256), 0, st, (const TaxNode *)ctx->nodes, n, d, S, n_pos);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(clade_scan_kernel, dim3(1), dim3(CLADE_SCAN_BLOCK), 0, st, S, (u64)n_pos);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(clade_kernel, dim3(grid_for(ctx, (u64)n + 1, 256)), dim3(256), 0, st, (const TaxNode *)ctx->nodes, n, d,
+                           (const unsigned long long *)S, n_pos, (unsigned long long *)ctx->tally_clade.p);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(clade, ctx->tally_clade.p, bytes, hipMemcpyDeviceToHost, st));
+    }
+    if (direct) HIPCHK(ctx, hipMemcpyAsync(direct, ctx->tally_direct.p, bytes, hipMemcpyDeviceToHost, st));
+    if (reset) HIPCHK(ctx, hipMemsetAsync(ctx->tally_direct.p, 0, bytes, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return BNS_OK;
+}
+
 // Host-side flattening of the parent map into {parent, Euler interval, flags} records.
 int bns_load_taxonomy(bns_ctx *ctx, const uint32_t *parent, uint32_t n)
 {
@@ -1249,8 +1330,8 @@ int bns_load_taxonomy(bns_ctx *ctx, const uint32_t *parent, uint32_t n)
     HIPCHK(ctx, hipMalloc((void **)&d, (size_t)n * sizeof(TaxNode)));
     HIPCHK(ctx, hipMemcpy(d, nodes.data(), (size_t)n * sizeof(TaxNode), hipMemcpyHostToDevice));
     if (ctx->nodes) (void)hipFree(ctx->nodes);
-    ctx->nodes = d; ctx->n_nodes = n;
-    return BNS_OK;
+    ctx->nodes = d; ctx->n_nodes = n; ctx->tax_clock = clock;
+    return ctx->tally_on ? tally_zero(ctx) : BNS_OK;      // a new taxonomy, new bins: the tally starts again
 }
 
 int bns_set_timing(bns_ctx *ctx, int enabled)
@@ -1392,7 +1473,7 @@ static int classify_device_impl(bns_ctx *ctx, const char *d_bases, const uint64_
     hipLaunchKernelGGL(unpack_kernel, dim3(grid_for(ctx, n_units, 256)), dim3(256), 0, st, (const uint4 *)ctx->records.p, (u64)n_units,
                        d_taxon, d_missing, d_ambig, d_n_hits);
     HIPCHK(ctx, hipGetLastError());
-    return BNS_OK;
+    return tally_units(ctx, d_taxon, n_units, st);       // (every classifying entry point comes through here, once per unit)
 }
 
 int bns_classify_batch_device(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_reads,

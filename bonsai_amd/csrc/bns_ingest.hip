@@ -655,6 +655,7 @@ struct TextCall {
     u32 ns = 1;
     u32 batch_no = 0;                                   // batches classified so far
     u64 runs_done = 0;                                  // runs whose copy to the host has been queued
+    u64 prev_units = 0;                                 // units of the last classified batch (bns_tally_enable: what a roll-back takes out again)
     bool runs_overflow = false;                         // the caller's run arrays are full: the batch whose runs did not fit (and what follows) is not his
     bool rolled_back = false;
     // accepted so far (slices parsed and counted, classified or waiting in the open batch) / the open batch / where the open batch began /
@@ -719,14 +720,20 @@ int text_flush_runs_of_prev(bns_ctx *ctx, TextWork &tw, TextCall &tc)
     return BNS_OK;
 }
 
-// the last classified batch is not the caller's after all (its runs did not fit his arrays): nor is what came behind it
-void text_roll_back(TextCall &tc)
+// the last classified batch is not the caller's after all (its runs did not fit his arrays): nor is what came behind it.  (Nothing was
+// classified behind it; its units leave the tally again -- the caller classifies them once more.)
+int text_roll_back(bns_ctx *ctx, TextWork &tw, TextCall &tc)
 {
-    if (tc.rolled_back) return;
+    if (tc.rolled_back) return BNS_OK;
     tc.rolled_back = true;
+    if (!tc.parse_only && tc.batch_no) {
+        const int rc = tally_units(ctx, (const u32 *)tw.out[(tc.batch_no - 1u) & 1u][0].p, tc.prev_units, ctx->stream, true);
+        if (rc != BNS_OK) return rc;
+    }
     tc.done_reads = tc.reads_before_prev; tc.names_done = tc.names_before_prev; tc.bases_done = tc.bases_before_prev;
     for (u32 s = 0; s < tc.ns; ++s) tc.cons[s] = tc.cons_before_prev[s];
     tc.acc_reads = tc.acc_bases = tc.acc_names = 0; tc.acc_max_len = 0;
+    return BNS_OK;
 }
 
 // ---- the open batch -> one classify launch; its results behind those of the batches in front.  Results leave on the back stream:
@@ -746,7 +753,7 @@ int text_flush_batch(bns_ctx *ctx, TextWork &tw, TextCall &tc)
     if (tc.batch_no && ctx->timing && !parse_only) { float ms = 0; if (hipEventElapsedTime(&ms, tw.tc0[q ^ 1u], tw.tc1[q ^ 1u]) == hipSuccess) tc.ms_classify += ms; }
     int frc = text_flush_runs_of_prev(ctx, tw, tc);
     if (frc != BNS_OK) return frc;
-    if (tc.runs_overflow) { text_roll_back(tc); tc.status = BNS_TEXT_CAP; return BNS_OK; }
+    if (tc.runs_overflow) { tc.status = BNS_TEXT_CAP; return text_roll_back(ctx, tw, tc); }
     u32 *o0 = (u32 *)tw.out[q][0].p, *o1 = (u32 *)tw.out[q][1].p, *o2 = (u32 *)tw.out[q][2].p, *o3 = (u32 *)tw.out[q][3].p;
     unsigned long long *d_cur = &((SmallLayout *)ctx->small.p)->runs_cursor;     // (zeroed at the start of the call: it runs on over the batches)
     if (!parse_only) {
@@ -756,6 +763,7 @@ int text_flush_batch(bns_ctx *ctx, TextWork &tw, TextCall &tc)
                                    out->ambig || want_runs ? o2 : nullptr, (out->n_hits || want_runs) ? o3 : nullptr, want_runs ? (u32 *)tw.hits.p : nullptr, st);
         if (frc != BNS_OK) return frc;
         ++tc.n_launches;
+        tc.prev_units = n_units;
         if (ctx->timing) HIPCHK(ctx, hipEventRecord(tw.tc1[q], st));
         if (want_runs) {
             hipLaunchKernelGGL(hit_runs_kernel, dim3(grid_for(ctx, (n_units + HIT_RUNS_GROUP - 1) / HIT_RUNS_GROUP, 4)), dim3(256), 0, st, (const u32 *)tw.hits.p,
@@ -829,7 +837,7 @@ int text_wrap_up(bns_ctx *ctx, TextWork &tw, TextCall &tc, bns_text_info *info)
     if (tc.batch_no && ctx->timing && !tc.parse_only) { float ms = 0; if (hipEventElapsedTime(&ms, tw.tc0[(tc.batch_no - 1u) & 1u], tw.tc1[(tc.batch_no - 1u) & 1u]) == hipSuccess) tc.ms_classify += ms; }
     if (!tc.rolled_back) {
         if ((rc = text_flush_runs_of_prev(ctx, tw, tc)) != BNS_OK) return text_bail(ctx, tc, rc);
-        if (tc.runs_overflow) { text_roll_back(tc); tc.status = BNS_TEXT_CAP; }
+        if (tc.runs_overflow) { tc.status = BNS_TEXT_CAP; if ((rc = text_roll_back(ctx, tw, tc)) != BNS_OK) return text_bail(ctx, tc, rc); }
     }
     WUCHK(hipStreamSynchronize(bs));
 #undef WUCHK

@@ -18,6 +18,7 @@
 #include <stdexcept>
 #include <string>
 #include <string_view>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -78,6 +79,22 @@ struct Database {
 
 // util.h:766-785.  parent[id], BNS_TAX_ABSENT where id is not a key; parent[1] == 0.
 std::vector<u32> build_parent_map(const char *nodes_dmp);
+
+// ---- taxon report (`bonsai classify -R`; no reference counterpart) -------------------------------------------------------------
+// nodes.dmp's third field ("rank") per taxid, indexed like build_parent_map's array; "no rank" where a line has no such field, "" for
+// an id without a line
+std::vector<std::string> read_node_ranks(const char *nodes_dmp);
+// names.dmp's "scientific name" rows: taxid -> name (the first row of a taxid)
+std::unordered_map<u32, std::string> read_scientific_names(const char *names_dmp);
+// Kraken 2's standard report layout from the device tally (bns_tally_read): direct / clade have n + 1 entries -- bin 0 unclassified, bin n
+// "not in the taxonomy" --, parent[] n (build_parent_map).  One line per node with units in its clade:
+// "%6.2f\t%llu\t%llu\t%s\t%u\t%s%s\n" = percent of all units, clade, direct, rank code, taxid, two spaces per depth, name (the decimal id
+// when names has none).  "unclassified" first (when bin 0 counts), then every root whose parent is 0 in ascending taxid order, depth first,
+// children by clade descending, ties by taxid ascending; "(not in taxonomy)" last (when bin n counts).  Rank codes: taxid 1 R,
+// superkingdom / domain D, kingdom K, phylum P, class C, order O, family F, genus G, species S; any other rank the code of its nearest
+// coded ancestor followed by the steps from it (a strain under a species: S1), "-" when no ancestor has one.
+std::string format_report(const u64 *direct, const u64 *clade, u32 n, const u32 *parent, const std::vector<std::string> &ranks,
+                          const std::unordered_map<u32, std::string> &names);
 
 // ---- reads --------------------------------------------------------------------------------------------
 struct bseq1_t {                // kseq_declare.h:40-44; the fields are VIEWS into memory owned by a ReadChunk (below)
@@ -291,11 +308,17 @@ struct ClassifierGeneric {
     int get_emit_kraken() const { return output_flag_ & KRAKEN; }
     int get_emit_fastq() const { return output_flag_ & FASTQ; }
     std::FILE *taxon_out_ = nullptr;         // `bonsai classify -b`: the taxon of every unit, in input order, as raw little-endian u32
+    std::FILE *report_out_ = nullptr;        // `bonsai classify -R`: the taxon report, written by write_report after the last unit
     bool nseq_printed_ = false;              // process_dataset's "nseq:" line on stderr has been printed (by the device text path or the host one)
     u64 n_classified() const { return classified_[0]; }
     u64 n_unclassified() const { return classified_[1]; }
 };
 using Classifier = ClassifierGeneric;
+
+// `bonsai classify -R`: a tally on every context of the classifier (bns_tally_enable), before the first unit ...
+void enable_tally(ClassifierGeneric &c);
+// ... and, after the last, the tallies summed over the contexts and the report written to c.report_out_ (names_dmp may be nullptr)
+void write_report(ClassifierGeneric &c, const std::vector<u32> &parent, const char *nodes_dmp, const char *names_dmp);
 
 // classifier.h:112-129 / 72-108 / 45-61: byte-for-byte formatters.  The hit stream comes either as the reference's `taxa`
 // vector or already run-length encoded (bns_classify_batch_runs): same text.

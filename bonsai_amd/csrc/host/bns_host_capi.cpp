@@ -1,5 +1,6 @@
 // bns_host_capi.cpp -- plain-C exports of the host-side readers/formatters (libbns_host.so) so that Python
 // hosts and the CPU test tier can reach them without a GPU.  No compute here: file formats and text only.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -206,6 +207,70 @@ size_t bnsh_fastq_record(const char *name1, const char *seq1, const char *qual1,
     append_fastq_classification(std::vector<tax_t>(hits, hits + n_hits), taxon, ambig, missing, bs, s, verbose, paired);
     if (s.size() <= cap) std::memcpy(buf, s.data(), s.size());
     return s.size();
+}
+
+// ---- taxon report (bonsai classify -R).  Strings cross as one malloc'd block of NUL-terminated strings (free with bnsh_free).
+namespace {
+char *join_nul(const std::vector<std::string> &v, uint64_t *bytes)
+{
+    size_t tot = 0;
+    for (const auto &x : v) tot += x.size() + 1;
+    char *b = static_cast<char *>(std::malloc(tot ? tot : 1)), *w = b;
+    for (const auto &x : v) { std::memcpy(w, x.c_str(), x.size() + 1); w += x.size() + 1; }
+    *bytes = tot;
+    return b;
+}
+std::vector<std::string> split_nul(const char *blob, uint64_t count)
+{
+    std::vector<std::string> v;
+    v.reserve(count);
+    for (uint64_t i = 0; i < count; ++i) { v.emplace_back(blob); blob += v.back().size() + 1; }
+    return v;
+}
+}  // namespace
+
+// read_node_ranks: n strings (rank of taxid i), n = the largest taxid + 1
+int bnsh_node_ranks(const char *nodes_dmp, char **blob, uint64_t *bytes, uint32_t *n)
+{
+    return guard([&] {
+        const std::vector<std::string> r = read_node_ranks(nodes_dmp);
+        *n = (uint32_t)r.size();
+        *blob = join_nul(r, bytes);
+    });
+}
+
+// read_scientific_names: count (taxid, name) pairs, ids[] malloc'd as well
+int bnsh_scientific_names(const char *names_dmp, uint32_t **ids, char **blob, uint64_t *bytes, uint64_t *count)
+{
+    return guard([&] {
+        const auto m = read_scientific_names(names_dmp);
+        std::vector<std::pair<uint32_t, std::string>> v(m.begin(), m.end());
+        std::sort(v.begin(), v.end());
+        std::vector<std::string> names;
+        *count = v.size();
+        *ids = static_cast<uint32_t *>(std::malloc(v.size() * 4 + 4));
+        for (size_t i = 0; i < v.size(); ++i) { (*ids)[i] = v[i].first; names.push_back(v[i].second); }
+        *blob = join_nul(names, bytes);
+    });
+}
+
+// format_report: direct / clade n + 1 entries, parent n; ranks = n_ranks strings (taxid order), names = n_names (id, string) pairs.
+// The text comes back malloc'd in *out (*out_bytes bytes, NUL-terminated).
+int bnsh_format_report(const uint64_t *direct, const uint64_t *clade, uint32_t n, const uint32_t *parent, const char *ranks_blob, uint32_t n_ranks,
+                       const uint32_t *name_ids, const char *names_blob, uint64_t n_names, char **out, uint64_t *out_bytes)
+{
+    return guard([&] {
+        const std::vector<std::string> ranks = ranks_blob ? split_nul(ranks_blob, n_ranks) : std::vector<std::string>{};
+        std::unordered_map<u32, std::string> names;
+        if (names_blob) {
+            const std::vector<std::string> nm = split_nul(names_blob, n_names);
+            for (uint64_t i = 0; i < n_names; ++i) names.emplace(name_ids[i], nm[i]);
+        }
+        const std::string s = format_report(direct, clade, n, parent, ranks, names);
+        *out = static_cast<char *>(std::malloc(s.size() + 1));
+        std::memcpy(*out, s.c_str(), s.size() + 1);
+        *out_bytes = s.size();
+    });
 }
 
 }  // extern "C"

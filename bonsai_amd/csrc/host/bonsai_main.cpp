@@ -40,6 +40,9 @@ void usage(const char *exe)
                  "\tn:bytes sets the stretch length.  Output does not depend on it.\n"
                  "-N:\tDo not bind the host threads to the CPUs next to the GPU(s) (the default narrows the affinity mask to them).\n"
                  "-b:\tAlso write every read's (pair's) taxon, in input order, as raw little-endian u32 to this path.\n"
+                 "-R:\tAlso write a taxon report to this path after the last read (Kraken 2's standard report layout: percent of all\n"
+                 "\treads, clade count, direct count, rank code, taxid, indented name), tallied on the GPU(s).\n"
+                 "-n:\tnames.dmp for the report's names (scientific names; without it a taxon is named by its id).\n"
                  "<inr1.fq> may be a read container written by `bonsai pack` (2-bit reads + names): no parsing, no packing.\n",
                  exe, 1 << 24);
     std::exit(EXIT_FAILURE);
@@ -54,9 +57,10 @@ int classify_main(int argc, char *argv[])
     std::string devices = "0";
     int layout = BNS_LAYOUT_MINBUCKET;
     bool canonicalize = true;
-    std::FILE *ofp = stdout, *taxon_fp = nullptr;
+    std::FILE *ofp = stdout, *taxon_fp = nullptr, *report_fp = nullptr;
+    const char *names_path = nullptr;
     if (argc < 4) usage(argv[0]);
-    while ((co = getopt(argc, argv, "Cc:p:o:S:afFkKg:L:NP:b:h?")) >= 0) {
+    while ((co = getopt(argc, argv, "Cc:p:o:S:afFkKg:L:NP:b:R:n:h?")) >= 0) {
         switch (co) {
             case 'h': case '?': usage(argv[0]); break;
             case 'C': canonicalize = false; break;
@@ -69,6 +73,8 @@ int classify_main(int argc, char *argv[])
             case 'p': num_threads = std::atoi(optarg); if (num_threads < 0) num_threads = bns::usable_cpus(); break;
             case 'o': ofp = std::fopen(optarg, "w"); break;
             case 'b': taxon_fp = std::fopen(optarg, "wb"); if (!taxon_fp) { std::fprintf(stderr, "Could not open taxon file\n"); return EXIT_FAILURE; } break;
+            case 'R': report_fp = std::fopen(optarg, "w"); if (!report_fp) { std::fprintf(stderr, "Could not open report file\n"); return EXIT_FAILURE; } break;
+            case 'n': names_path = optarg; break;
             case 'S': break;
             case 'g': devices = optarg; break;
             case 'N': bind_cpus = false; break;
@@ -138,6 +144,8 @@ int classify_main(int argc, char *argv[])
         bns::ClassifierGeneric &c = *new bns::ClassifierGeneric(db, taxmap, devs, num_threads, emit_all, emit_fastq, emit_kraken,
                                                                 canonicalize, layout);
         c.taxon_out_ = taxon_fp;
+        c.report_out_ = report_fp;
+        if (report_fp) bns::enable_tally(c);
         if (devs.size() > 1) {                                   // which collective library replicated the db over how many devices
             // (one line per device: a multi-GPU record says what it ran on)
             for (size_t i = 0; i < devs.size(); ++i) {
@@ -172,6 +180,12 @@ int classify_main(int argc, char *argv[])
         bns::process_dataset(c, argv[optind + 2], npos == 4 ? argv[optind + 3] : nullptr, ofp, (unsigned)chunk_size, parser_threads, segment_bytes);
         if (std::getenv("BNS_CLI_TIMING"))
             std::fprintf(stderr, "[timing] process_dataset %.3f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_pd).count());
+        if (report_fp) {
+            const auto t_rep = std::chrono::steady_clock::now();
+            bns::write_report(c, taxmap, argv[optind + 1], names_path);
+            if (std::getenv("BNS_CLI_TIMING"))
+                std::fprintf(stderr, "[timing] report %.3f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_rep).count());
+        }
         std::fprintf(stderr, "Classified %llu, unclassified %llu\n", (unsigned long long)c.n_classified(),
                      (unsigned long long)c.n_unclassified());
     } catch (const std::exception &e) {
@@ -180,6 +194,7 @@ int classify_main(int argc, char *argv[])
     }
     if (ofp != stdout) std::fclose(ofp);
     if (taxon_fp) std::fclose(taxon_fp);
+    if (report_fp && std::fclose(report_fp) != 0) { std::fprintf(stderr, "[E] Could not write the report\n"); return EXIT_FAILURE; }
     if (std::getenv("BNS_CLI_TIMING"))
         std::fprintf(stderr, "[timing] since start %.3f s\n",
                      std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count());

@@ -48,8 +48,63 @@ def lib():
         L.bnsh_encoder_from_str.argtypes = [C.c_uint, C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64]
         L.bnsh_encoder_hash_from_str.restype = C.c_long
         L.bnsh_encoder_hash_from_str.argtypes = [C.c_uint, C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64]
+        L.bnsh_node_ranks.restype = C.c_int
+        L.bnsh_node_ranks.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        L.bnsh_scientific_names.restype = C.c_int
+        L.bnsh_scientific_names.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.bnsh_format_report.restype = C.c_int
+        L.bnsh_format_report.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_char_p,
+                                         C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
+
+
+def _take_blob(ptr, nbytes):
+    """bytes of a malloc'd block from libbns_host, which is freed"""
+    b = C.string_at(ptr.value, nbytes) if nbytes else b""
+    lib().bnsh_free(ptr)
+    return b
+
+
+def read_node_ranks(path):
+    """nodes.dmp's rank column: list indexed by taxid ("no rank" where a line has no rank field, "" for an id without a line)"""
+    blob, nb, n = C.c_void_p(), C.c_uint64(), C.c_uint32()
+    if lib().bnsh_node_ranks(path.encode(), C.byref(blob), C.byref(nb), C.byref(n)) != 0:
+        raise HostIOError(lib().bnsh_last_error().decode())
+    parts = _take_blob(blob, nb.value).split(b"\0")
+    return [x.decode() for x in parts[:n.value]]
+
+
+def read_scientific_names(path):
+    """names.dmp's "scientific name" rows -> {taxid: name}"""
+    ids, blob, nb, cnt = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+    if lib().bnsh_scientific_names(path.encode(), C.byref(ids), C.byref(blob), C.byref(nb), C.byref(cnt)) != 0:
+        raise HostIOError(lib().bnsh_last_error().decode())
+    n = cnt.value
+    idv = np.frombuffer(C.string_at(ids.value, n * 4), dtype=np.uint32).tolist() if n else []
+    lib().bnsh_free(ids)
+    names = _take_blob(blob, nb.value).split(b"\0")[:n]
+    return {int(i): x.decode() for i, x in zip(idv, names)}
+
+
+def format_report(direct, clade, parent, ranks=None, names=None):
+    """the `bonsai classify -R` report text (bns::format_report) from the tallies (n + 1 entries each), parent[] (n), ranks (list by
+    taxid) and names ({taxid: name})"""
+    direct = np.ascontiguousarray(direct, dtype=np.uint64); clade = np.ascontiguousarray(clade, dtype=np.uint64)
+    parent = np.ascontiguousarray(parent, dtype=np.uint32)
+    n = parent.size
+    if direct.size != n + 1 or clade.size != n + 1:
+        raise ValueError("direct and clade need n + 1 entries")
+    ranks = list(ranks or [])
+    rb = b"".join(r.encode() + b"\0" for r in ranks)
+    items = sorted((names or {}).items())
+    ids = np.array([i for i, _ in items], dtype=np.uint32)
+    nb = b"".join(x.encode() + b"\0" for _, x in items)
+    out, ob = C.c_void_p(), C.c_uint64()
+    if lib().bnsh_format_report(direct.ctypes.data, clade.ctypes.data, n, parent.ctypes.data, rb if ranks else None, len(ranks),
+                                ids.ctypes.data if items else None, nb if items else None, len(items), C.byref(out), C.byref(ob)) != 0:
+        raise HostIOError(lib().bnsh_last_error().decode())
+    return _take_blob(out, ob.value).decode()
 
 
 def encoder_hash_from_str(seq, k, gaps=None, canon=True, w=0, hash_k=0):

@@ -165,6 +165,20 @@ const char *bns_table_warning(const bns_ctx *ctx);
  * BNS_TAX_ABSENT where id is not a key.  parent[1] must already be 0 (util.h:780-781). */
 int bns_load_taxonomy(bns_ctx *ctx, const uint32_t *parent, uint32_t n);
 
+/* ---- per-taxon tally (what `bonsai classify -R` reports) ------------------------------------------------------------------------
+ * No reference counterpart: the reference counts classified / unclassified reads (classifier.h:138,238) and prints neither.
+ * bns_tally_enable(ctx, 1): needs a loaded taxonomy; allocates and zeroes u64 direct[n + 1] (n as given to bns_load_taxonomy).  From then
+ * on every classifying entry point (bns_classify_batch, _runs, _device, the _packed three, bns_classify_text and bns_text_finish) adds
+ * the units it reports, once each, on the stream of the classify launch: bin 0 = taxon 0 (unclassified); bin t = a taxon t < n whose
+ * chain reaches a root with parent 0; bin n = anything else (t >= n, 0xFFFFFFFF, a taxid that is not a key, a broken chain).  Records a
+ * call does not take are not counted.  bns_resolve_batch, bns_probe* and the build are not counted.  Reloading the taxonomy zeroes the tally;
+ * bns_tally_enable(ctx, 0) frees it.  Off (the default): nothing is launched or allocated.
+ * bns_tally_read: len must be n + 1.  direct (may be NULL) receives the counts; clade (may be NULL) the sums over each node's subtree
+ * (clade_kernel over the Euler intervals), bins 0 and n as they are.  reset: zero the counts after reading.  Runs on the context's stream;
+ * _device calls made on another stream must be complete.  Counts of several contexts add up (clade sums too). */
+int bns_tally_enable(bns_ctx *ctx, int on);
+int bns_tally_read(bns_ctx *ctx, uint64_t *direct, uint64_t *clade, uint32_t len, int reset);
+
 /* ---- hot path --------------------------------------------------------------------------------- */
 /* Replaces: the kt_forpool fan-out in classify_seqs (classifier.h:275) over classify_seq
  * (classifier.h:212-251), i.e. per read (or mate pair): Encoder::for_each -> kh_get(c) ->
