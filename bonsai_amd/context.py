@@ -4,6 +4,7 @@ Context bundles what bin/bonsai.cpp:149-157 builds before process_dataset: the D
 (database.h:33-56), the Spacer/Encoder (classifier.h:155-166) and the parent map (util.h:766-785).
 """
 import ctypes as C
+from fractions import Fraction
 
 import numpy as np
 
@@ -43,6 +44,22 @@ def pack_reads(bases, offsets, threads=1):
         if nb.value <= cap:
             raise BonsaiAmdError("bns_pack_reads: %s" % L.bns_strerror(rc).decode())
         cap = int(nb.value)
+
+
+def confidence_fraction(threshold):
+    """a confidence threshold (int, str, Fraction or float; a float goes through its shortest repr: 0.1 is 1/10) -> (num, den) in
+    lowest terms, what bns_set_confidence takes; ValueError outside [0, 1]"""
+    if isinstance(threshold, bool):
+        raise ValueError("confidence threshold must be a number in [0, 1], not %r" % (threshold,))
+    if isinstance(threshold, float):
+        threshold = str(threshold)
+    try:
+        f = Fraction(threshold)
+    except (TypeError, ValueError, ZeroDivisionError):
+        raise ValueError("confidence threshold must be a number in [0, 1], not %r" % (threshold,)) from None
+    if not 0 <= f <= 1:
+        raise ValueError("confidence threshold must lie in [0, 1], not %s" % f)
+    return f.numerator, f.denominator
 
 
 class Context:
@@ -164,6 +181,12 @@ class Context:
         clade = np.zeros(n + 1, dtype=np.uint64)
         self._chk(self.L.bns_tally_read(self.h, _p(direct, u64p), _p(clade, u64p), n + 1, int(bool(reset))), "bns_tally_read")
         return direct, clade
+
+    def set_confidence(self, threshold):
+        """bns_set_confidence: every classify call walks its taxa up to the first ancestor whose clade holds ceil(threshold * Q) of a
+        unit's Q probed k-mers (0 when none does); threshold 0 turns it off.  Needs a loaded taxonomy (unless 0)."""
+        num, den = confidence_fraction(threshold)
+        self._chk(self.L.bns_set_confidence(self.h, num, den), "bns_set_confidence")
 
     # ---- hot path (host buffers)
     def classify(self, bases, offsets, paired=False, want_hits=False):

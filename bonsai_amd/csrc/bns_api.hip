@@ -3,6 +3,7 @@
 #include "../../include/bonsai_amd.h"
 #include "bns_kernels.hip"
 #include "bns_tally.hpp"
+#include "bns_confidence.hpp"
 
 #include <dlfcn.h>
 #if defined(__x86_64__)
@@ -10,6 +11,7 @@
 #endif
 #include <rccl/rccl.h>          // types and declarations only: the library itself is dlopen()ed (see Rccl below)
 #include <mutex>
+#include <numeric>
 #include <algorithm>
 #include <array>
 #include <cstdio>
@@ -120,6 +122,9 @@ struct bns_ctx {
     // bns_tally_enable: direct[n_nodes + 1] counts of classified units per bin; clade / scan: bns_tally_read's workspace
     bool tally_on = false;
     DevBuf tally_direct, tally_clade, tally_scan;
+    // bns_set_confidence: theta = conf_num / conf_den (0: off); conf_hits: the hit stream of a launch whose caller wants none
+    u64 conf_num = 0, conf_den = 1;
+    DevBuf conf_hits;
     // workspace (grow-only)
     DevBuf words, nmask, ovf_list, scratch, small, records;      // small: ovf_count + misc counters
     DevBuf st_bases, st_offsets, st_out[4], st_hits, st_kmers, st_aux, st_runs[4], st_words, st_nmask, st_bad;   // st_words..: packed host batches   // st_runs: run_start, n_runs, run_tax, run_len
@@ -317,7 +322,7 @@ bool launch_fixed_k(const ClassifyParams &p, unsigned grid, hipStream_t st, bool
 
 extern "C" {
 
-int bns_version(void) { return 105; }
+int bns_version(void) { return 106; }
 
 int bns_device_pci_bus_id(int device, char *out, int cap)
 {
@@ -439,7 +444,7 @@ void bns_destroy(bns_ctx *ctx)
     DevBuf *bufs[] = {&ctx->words, &ctx->nmask, &ctx->ovf_list, &ctx->scratch, &ctx->small, &ctx->records, &ctx->st_bases, &ctx->st_offsets,
                       &ctx->st_out[0], &ctx->st_out[1], &ctx->st_out[2], &ctx->st_out[3], &ctx->st_hits, &ctx->st_kmers, &ctx->st_aux,
                       &ctx->st_runs[0], &ctx->st_runs[1], &ctx->st_runs[2], &ctx->st_runs[3], &ctx->st_words, &ctx->st_nmask, &ctx->st_bad,
-                      &ctx->tally_direct, &ctx->tally_clade, &ctx->tally_scan};
+                      &ctx->tally_direct, &ctx->tally_clade, &ctx->tally_scan, &ctx->conf_hits};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->peer_stage) (void)hipHostFree(ctx->peer_stage);
     if (ctx->h_run_tax) (void)hipHostFree(ctx->h_run_tax);
@@ -1269,6 +1274,23 @@ int bns_tally_read(bns_ctx *ctx, uint64_t *direct, uint64_t *clade, uint32_t len
     return BNS_OK;
 }
 
+int bns_set_confidence(bns_ctx *ctx, uint64_t num, uint64_t den)
+{
+    if (!ctx) return BNS_ERR_ARG;
+    if (den == 0 || num > den) return fail(ctx, BNS_ERR_ARG, "confidence num / den: den > 0 and num <= den");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (num == 0) {
+        if (ctx->conf_num) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        release(ctx->conf_hits);
+        ctx->conf_num = 0; ctx->conf_den = 1;
+        return BNS_OK;
+    }
+    if (!ctx->nodes) return fail(ctx, BNS_ERR_STATE, "no taxonomy loaded (bns_load_taxonomy)");
+    const u64 g = std::gcd(num, den);                // (the same theta; small terms keep the device's exact ceil on its short path)
+    ctx->conf_num = num / g; ctx->conf_den = den / g;
+    return BNS_OK;
+}
+
 // Host-side flattening of the parent map into {parent, Euler interval, flags} records.
 int bns_load_taxonomy(bns_ctx *ctx, const uint32_t *parent, uint32_t n)
 {
@@ -1405,7 +1427,11 @@ static int classify_device_impl(bns_ctx *ctx, const char *d_bases, const uint64_
     p.offsets = d_offsets; p.n_units = n_units; p.nmates = nm; p.bases = (const u8 *)d_bases;
     if (packed) { p.words = (const u64 *)d_words; p.nmask = (const u32 *)d_nmask; }
     p.taxon = d_taxon; p.missing = d_missing; p.ambig = d_ambig; p.n_hits = d_n_hits; p.hits = d_hits;
-    p.want_hits = d_hits ? 1 : 0;
+    if (ctx->conf_num && !d_hits) {                  // the confidence pass reads the hit stream: into a buffer of ours when the caller takes none
+        if ((rc = ensure(ctx, ctx->conf_hits, (size_t)total_bases * 4 + 4)) != BNS_OK) return rc;
+        p.hits = (u32 *)ctx->conf_hits.p;
+    }
+    p.want_hits = p.hits ? 1 : 0;
     if ((rc = ensure(ctx, ctx->records, (size_t)n_units * 16)) != BNS_OK) return rc;
     p.records = (uint4 *)ctx->records.p;
     p.ovf_count = d_ovf; p.ovf_list = can_overflow ? (u64 *)ctx->ovf_list.p : nullptr;
@@ -1469,6 +1495,12 @@ static int classify_device_impl(bns_ctx *ctx, const char *d_bases, const uint64_
             });
             HIPCHK(ctx, hipGetLastError());
         }
+    }
+    if (ctx->conf_num) {                             // bns_set_confidence: the taxa of the records walked up to theta's clade
+        hipLaunchKernelGGL(confidence_kernel, dim3(grid_for(ctx, (n_units + CONF_GROUP - 1) / CONF_GROUP, 4)), dim3(256), 0, st, (uint4 *)ctx->records.p,
+                           (const u64 *)d_offsets, (u32)nm, (const u32 *)p.hits, (u64)n_units, (const TaxNode *)ctx->nodes, ctx->n_nodes, ctx->conf_num,
+                           ctx->conf_den);
+        HIPCHK(ctx, hipGetLastError());
     }
     hipLaunchKernelGGL(unpack_kernel, dim3(grid_for(ctx, n_units, 256)), dim3(256), 0, st, (const uint4 *)ctx->records.p, (u64)n_units,
                        d_taxon, d_missing, d_ambig, d_n_hits);

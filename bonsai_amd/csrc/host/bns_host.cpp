@@ -420,6 +420,11 @@ ClassifierGeneric::ClassifierGeneric(const Database &db, const std::vector<u32> 
     }
 }
 
+void set_confidence(ClassifierGeneric &c, u64 num, u64 den)
+{
+    for (bns_ctx *cx : c.ctxs_) chk(cx, bns_set_confidence(cx, num, den), "bns_set_confidence");
+}
+
 ClassifierGeneric::~ClassifierGeneric()
 {
     work_.res.release(); work_.first.release();              // (page-locked memory goes back while the contexts still exist)

@@ -315,6 +315,8 @@ struct ClassifierGeneric {
 };
 using Classifier = ClassifierGeneric;
 
+// `bonsai classify -t`: the confidence threshold num / den on every context of the classifier (bns_set_confidence), before the first unit
+void set_confidence(ClassifierGeneric &c, u64 num, u64 den);
 // `bonsai classify -R`: a tally on every context of the classifier (bns_tally_enable), before the first unit ...
 void enable_tally(ClassifierGeneric &c);
 // ... and, after the last, the tallies summed over the contexts and the report written to c.report_out_ (names_dmp may be nullptr)

@@ -43,9 +43,25 @@ void usage(const char *exe)
                  "-R:\tAlso write a taxon report to this path after the last read (Kraken 2's standard report layout: percent of all\n"
                  "\treads, clade count, direct count, rank code, taxid, indented name), tallied on the GPU(s).\n"
                  "-n:\tnames.dmp for the report's names (scientific names; without it a taxon is named by its id).\n"
+                 "-t:\tConfidence threshold in [0, 1] (digits, at most 9 after the point) [0]: a read (pair) is called at the first of its\n"
+                 "\ttaxon and the taxon's ancestors whose clade holds at least that fraction of its k-mers, else unclassified.\n"
                  "<inr1.fq> may be a read container written by `bonsai pack` (2-bit reads + names): no parsing, no packing.\n",
                  exe, 1 << 24);
     std::exit(EXIT_FAILURE);
+}
+
+// `-t`: a decimal in [0, 1] -- digits, an optional point, at most 9 digits behind it -- parsed exactly into num / 10^d
+bool parse_confidence(const char *s, unsigned long long &num, unsigned long long &den)
+{
+    unsigned long long ip = 0, fp = 0, scale = 1;
+    int n_int = 0, n_frac = 0;
+    const char *c = s;
+    for (; *c >= '0' && *c <= '9'; ++c, ++n_int) { ip = ip * 10 + (unsigned)(*c - '0'); if (ip > 1) return false; }
+    if (*c == '.')
+        for (++c; *c >= '0' && *c <= '9'; ++c) { if (++n_frac > 9) return false; fp = fp * 10 + (unsigned)(*c - '0'); scale *= 10; }
+    if (*c || n_int + n_frac == 0) return false;
+    num = ip * scale + fp; den = scale;
+    return num <= den;
 }
 
 int classify_main(int argc, char *argv[])
@@ -59,8 +75,9 @@ int classify_main(int argc, char *argv[])
     bool canonicalize = true;
     std::FILE *ofp = stdout, *taxon_fp = nullptr, *report_fp = nullptr;
     const char *names_path = nullptr;
+    unsigned long long conf_num = 0, conf_den = 1;
     if (argc < 4) usage(argv[0]);
-    while ((co = getopt(argc, argv, "Cc:p:o:S:afFkKg:L:NP:b:R:n:h?")) >= 0) {
+    while ((co = getopt(argc, argv, "Cc:p:o:S:afFkKg:L:NP:b:R:n:t:h?")) >= 0) {
         switch (co) {
             case 'h': case '?': usage(argv[0]); break;
             case 'C': canonicalize = false; break;
@@ -75,6 +92,12 @@ int classify_main(int argc, char *argv[])
             case 'b': taxon_fp = std::fopen(optarg, "wb"); if (!taxon_fp) { std::fprintf(stderr, "Could not open taxon file\n"); return EXIT_FAILURE; } break;
             case 'R': report_fp = std::fopen(optarg, "w"); if (!report_fp) { std::fprintf(stderr, "Could not open report file\n"); return EXIT_FAILURE; } break;
             case 'n': names_path = optarg; break;
+            case 't':
+                if (!parse_confidence(optarg, conf_num, conf_den)) {
+                    std::fprintf(stderr, "[E] -t: the confidence threshold must be a decimal in [0, 1] with at most 9 digits after the point, not '%s'\n", optarg);
+                    return EXIT_FAILURE;
+                }
+                break;
             case 'S': break;
             case 'g': devices = optarg; break;
             case 'N': bind_cpus = false; break;
@@ -145,6 +168,7 @@ int classify_main(int argc, char *argv[])
                                                                 canonicalize, layout);
         c.taxon_out_ = taxon_fp;
         c.report_out_ = report_fp;
+        if (conf_num) bns::set_confidence(c, conf_num, conf_den);
         if (report_fp) bns::enable_tally(c);
         if (devs.size() > 1) {                                   // which collective library replicated the db over how many devices
             // (one line per device: a multi-GPU record says what it ran on)

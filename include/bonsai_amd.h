@@ -179,6 +179,18 @@ int bns_load_taxonomy(bns_ctx *ctx, const uint32_t *parent, uint32_t n);
 int bns_tally_enable(bns_ctx *ctx, int on);
 int bns_tally_read(bns_ctx *ctx, uint64_t *direct, uint64_t *clade, uint32_t len, int reset);
 
+/* ---- confidence threshold (what `bonsai classify -t` sets) -------------------------------------------------------------------------
+ * No reference counterpart: Kraken 2's --confidence, as defined in DESIGN.md.  theta = num / den, exact.  For each unit, Q = its hits +
+ * its missing k-mers (every k-mer made only of A/C/G/T; ambig does not enter), R = ceil(theta * Q) in integers; the resolved taxon T
+ * becomes the first of T, parent(T), ... whose clade (hits equal to it or inside its subtree, u32 counts) holds >= R hits, and 0 when
+ * the walk passes a root first.  T stays when R = 0, T = 0, or T is not a node whose chain reaches a root (bns_tally_enable's bin n).
+ * Only the taxon changes: missing, ambig, n_hits and the hits stay.  Every classifying entry point (those bns_tally_enable lists)
+ * applies it on the stream of the classify launch (confidence_kernel, before the results are unpacked), so the tally counts the new
+ * taxa; a call that takes no hits has them written to a buffer of the context's (4 bytes per base).
+ * den > 0 and num <= den, else BNS_ERR_ARG.  num > 0 needs a loaded taxonomy, else BNS_ERR_STATE.  num = 0 turns it off (the default):
+ * nothing is launched or allocated.  Reloading the taxonomy keeps the setting.  bns_resolve_batch and bns_probe* are not affected. */
+int bns_set_confidence(bns_ctx *ctx, uint64_t num, uint64_t den);
+
 /* ---- hot path --------------------------------------------------------------------------------- */
 /* Replaces: the kt_forpool fan-out in classify_seqs (classifier.h:275) over classify_seq
  * (classifier.h:212-251), i.e. per read (or mate pair): Encoder::for_each -> kh_get(c) ->
