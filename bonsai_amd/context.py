@@ -48,7 +48,7 @@ def pack_reads(bases, offsets, threads=1):
 
 def confidence_fraction(threshold):
     """a confidence threshold (int, str, Fraction or float; a float goes through its shortest repr: 0.1 is 1/10) -> (num, den) in
-    lowest terms, what bns_set_confidence takes; ValueError outside [0, 1]"""
+    lowest terms, what bns_set_confidence takes; ValueError outside [0, 1], and when a term does not fit the C ABI's uint64_t"""
     if isinstance(threshold, bool):
         raise ValueError("confidence threshold must be a number in [0, 1], not %r" % (threshold,))
     if isinstance(threshold, float):
@@ -59,6 +59,8 @@ def confidence_fraction(threshold):
         raise ValueError("confidence threshold must be a number in [0, 1], not %r" % (threshold,)) from None
     if not 0 <= f <= 1:
         raise ValueError("confidence threshold must lie in [0, 1], not %s" % f)
+    if f.denominator >= 1 << 64:                         # (num <= den) ctypes would pass the terms mod 2^64: another threshold
+        raise ValueError("confidence threshold %s: num and den in lowest terms must be below 2^64" % f)
     return f.numerator, f.denominator
 
 
