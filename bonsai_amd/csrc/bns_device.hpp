@@ -413,6 +413,32 @@ constexpr u32 MINB_NONE = 0xFFFFFFFFu;          // "no bucket wanted" (bucket in
 // of); the standalone probe kernel is short of registers instead and runs every pass through the general form.
 // TAGS: the caller hands in tbit = minb_tagbit(minimizer value) and a lane leaves its home bucket only when that bit is set in the
 // bucket's header (the crowded-table instantiations; without it every miss in a full home that spilled anything walks on).
+// Rare: lanes whose chain was exhausted (found == 2) look their key up in the overflow table, one lane at a time with wave-uniform
+// (scalar) control flow -- a divergent per-lane walk here costs the hot loop ~20 SGPRs of lane masks.
+__device__ __forceinline__ void minb_ovf_walk(u64 key, u32 &found, u32 &val, const Slot *__restrict__ ovf_slots, u64 ovf_mask)
+{
+    const int lane = lane_id();
+    u64 todo = ballot64(found == 2u);
+    while (todo) {
+        const int l = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const u64 skey = readlane64(key, l);
+        const uint4 *ob = reinterpret_cast<const uint4 *>(ovf_slots);
+        u64 b2 = ovf_bucket(skey, ovf_mask), step = 0;
+        bool hit = false, open = false;
+        u32 hv = 0;
+        while (!hit && !open) {
+            for (int s = 0; s < 4 && !hit && !open; ++s) {
+                const uint4 sl = ob[b2 * 4 + (u64)s];
+                if (!sl.w) open = true;
+                else if ((((u64)sl.y << 32) | sl.x) == skey) { hit = true; hv = sl.z; }
+            }
+            b2 = (b2 + (++step)) & ovf_mask;
+        }
+        if (hit && lane == l) { found = 1u; val = hv; }
+    }
+}
+
 template <bool KEY_MAY_BE_ONES = true, int NB = 16, bool OVF_COOP = false, bool PEEL = true, bool TAGS = false>
 __device__ __forceinline__ ProbeResult probe_minbucket(const MinBucket *__restrict__ buckets, u64 key, u32 b, bool active, u32 *aux,
                                                        const Slot *__restrict__ ovf_slots, u64 ovf_mask, u32 tbit = 0u)
@@ -576,29 +602,114 @@ __device__ __forceinline__ ProbeResult probe_minbucket(const MinBucket *__restri
         }
         return ProbeResult{val, (found & 1u) != 0u};
     }
-    // Rare: lanes whose chain was exhausted look their key up in the overflow table, one lane at a time with wave-uniform
-    // (scalar) control flow -- a divergent per-lane walk here costs the hot loop ~20 SGPRs of lane masks.
-    u64 todo = ballot64(found == 2u);
-    while (todo) {
-        const int l = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const u64 skey = readlane64(key, l);
-        const uint4 *ob = reinterpret_cast<const uint4 *>(ovf_slots);
-        u64 b2 = ovf_bucket(skey, ovf_mask), step = 0;
-        bool hit = false, open = false;
-        u32 hv = 0;
-        while (!hit && !open) {
-            for (int s = 0; s < 4 && !hit && !open; ++s) {
-                const uint4 sl = ob[b2 * 4 + (u64)s];
-                if (!sl.w) open = true;
-                else if ((((u64)sl.y << 32) | sl.x) == skey) { hit = true; hv = sl.z; }
-            }
-            b2 = (b2 + (++step)) & ovf_mask;
-        }
-        if (hit && lane == l) { found = 1u; val = hv; }
-    }
+    minb_ovf_walk(key, found, val, ovf_slots, ovf_mask);
     ProbeResult r{val, (found & 1u) != 0u};
     return r;
+}
+
+// Two-key probe: the lookups of two consecutive rounds of a read (contiguous seeds: half A = round 2p, half B = round 2p + 1) in
+// ONE set of passes.  A 150-bp read touches ~15 distinct minimizer groups over its 120 k-mers, so the 16-bucket stage usually
+// holds all of them: one pass, one HBM round trip and one run-leader ranking per read instead of one per round.  The positions
+// are ranked as if the wavefront were 128 lanes wide -- half A's lanes 0..63, then half B's -- so half B's lane 0 compares
+// against half A's lane 63 and the group that straddles the two rounds is one run, fetched once; half B's ranks start at half
+// A's leader count.  Everything else -- stage, chain walk, home / tag bits, MINB_N_IN_OVF, the overflow table, runs ranked NB
+// and beyond left for a later pass -- is probe_minbucket's (TAGS = false, OVF_COOP = false, NB = 16), once per half.
+template <bool KEY_MAY_BE_ONES = true, int NB = 16>
+__device__ __forceinline__ void probe_minbucket2(const MinBucket *__restrict__ buckets, u64 keyA, u32 bA, bool activeA, u64 keyB, u32 bB,
+                                                 bool activeB, u32 *aux, const Slot *__restrict__ ovf_slots, u64 ovf_mask,
+                                                 ProbeResult &ra, ProbeResult &rb)
+{
+    static_assert(NB == 16, "the two-key probe stages 16 buckets (two 1 KiB loads)");
+    const int lane = lane_id();
+    u32 *list = aux;
+    uint4 *stage = reinterpret_cast<uint4 *>(aux + MINB_LIST_U32);
+    const uint4 *base = reinterpret_cast<const uint4 *>(buckets);
+    u32 bktA = activeA ? bA : MINB_NONE, bktB = activeB ? bB : MINB_NONE;
+    u32 foundA = 0u, valA = 0u, homeA = 0u, foundB = 0u, valB = 0u, homeB = 0u;
+    const u32 xfA = mph_fold(keyA), xfB = mph_fold(keyB);
+    constexpr u32 GO = 1u << MINB_HOME_SHIFT;
+    // one half's lookup in the stage and its verdict (probe_minbucket's, TAGS = false); returns "walks on"
+    auto look = [&](auto first_tag, u32 &bkt, u32 rank, u32 xf, u64 key, u32 &found, u32 &val, u32 home, u32 &hx) -> bool {
+        constexpr bool FIRST = decltype(first_tag)::value;
+        const bool mine = bkt != MINB_NONE && rank < (u32)NB;
+        const char *B = reinterpret_cast<const char *>(stage) + (mine ? rank : 0u) * (16u * MINB_STRIDE);
+        const uint2 hdr = *reinterpret_cast<const uint2 *>(B + 120);
+        const u32 slot = mph_slot(xf, hdr.y);
+        const bool eq = *reinterpret_cast<const u64 *>(B + 8u * slot) == key;
+        const bool hit = mine & eq & (!KEY_MAY_BE_ONES || ((hdr.x >> (8u + slot)) & 1u));
+        const u32 v = *reinterpret_cast<const u32 *>(B + 80 + 4u * slot);
+        found = hit ? 1u : found;
+        val = hit ? v : val;
+        bool cont;
+        if (FIRST) cont = mine & !hit & ((hdr.x & (GO | 0xFFu)) >= (GO | MINB_CAP));
+        else       cont = mine & !hit & ((hdr.x & 0xFFu) >= MINB_CAP) & ((((home ? home : hdr.x) & GO)) != 0u);
+        bkt = (mine && !cont) ? MINB_NONE : bkt;
+        hx = hdr.x;
+        return cont;
+    };
+    // a lane that walks on (probe_minbucket's chain step)
+    auto walk = [&](auto first_tag, bool cont, u32 hx, u32 &bkt, u32 &found, u32 &home) {
+        constexpr bool FIRST = decltype(first_tag)::value;
+        const u32 cur = (FIRST || home == 0u) ? ((hx & MINB_HOME_MASK) | (GO << 4)) : home;
+        const bool exhausted = cont && (cur >> (MINB_HOME_SHIFT + 2u)) == 0u;
+        found |= (exhausted || (cont && (hx & 0xFFu) == MINB_N_IN_OVF)) ? 2u : 0u;
+        const u32 next = exhausted ? MINB_NONE : bkt + 1u;
+        bkt = cont ? next : bkt;
+        home = cont ? cur >> 1 : home;
+    };
+    bool more = true;
+    auto pass = [&](auto first_tag) -> bool {
+        // run leaders over the 128 positions: half B's lane 0 continues half A's lane 63
+        const u32 a63 = readlane(bktA, 63);
+        const u32 prevA = (u32)__builtin_amdgcn_update_dpp((int)~bktA, (int)bktA, DPP_WAVE_SHR1, 0xf, 0xf, false);
+        const u32 prevB = (u32)__builtin_amdgcn_update_dpp((int)a63, (int)bktB, DPP_WAVE_SHR1, 0xf, 0xf, false);
+        const bool pendA = bktA != MINB_NONE, chgA = bktA != prevA, pendB = bktB != MINB_NONE, chgB = bktB != prevB;
+        const u64 leadA = ballot64(pendA) & ballot64(chgA), leadB = ballot64(pendB) & ballot64(chgB);
+        if (!(leadA | leadB)) return false;
+        const u32 nA = (u32)__popcll(leadA);
+        const int n_lead = (int)nA + __popcll(leadB);
+#ifdef BNS_COUNT_FETCHES
+        if (lane == 0) { atomicAdd(&g_fetch_count[0], (unsigned long long)(n_lead < NB ? n_lead : NB)); atomicAdd(&g_fetch_count[1], 1ULL); }
+#endif
+        const u32 rankA = __builtin_amdgcn_mbcnt_hi((u32)(leadA >> 33), __builtin_amdgcn_mbcnt_lo((u32)(leadA >> 1), (u32)(leadA & 1ULL) - 1u));
+        const u32 rankB = __builtin_amdgcn_mbcnt_hi((u32)(leadB >> 33), __builtin_amdgcn_mbcnt_lo((u32)(leadB >> 1), nA + (u32)(leadB & 1ULL) - 1u));
+        // (the list has 64 entries: half A's ranks are below 64, half B's reach 127 -- and only the first NB are fetched)
+        if (pendA & chgA) list[rankA] = bktA;
+        if ((pendB & chgB) && rankB < (u32)NB) list[rankB] = bktB;
+        __builtin_amdgcn_wave_barrier();
+        {
+            const u32 last = (u32)n_lead - 1u, slot = (u32)lane >> 3;
+            typedef const void __attribute__((address_space(1))) *gptr_t;
+            typedef void __attribute__((address_space(3))) *lptr_t;
+            const u32 b0 = list[slot < last ? slot : last];
+            __builtin_amdgcn_global_load_lds((gptr_t)(base + ((u64)b0 * 8 + (u64)(lane & 7))), (lptr_t)stage, 16, 0, 2);
+            if (last >= 8u) {
+                const u32 b1 = list[slot + 8u < last ? slot + 8u : last];
+                __builtin_amdgcn_global_load_lds((gptr_t)(base + ((u64)b1 * 8 + (u64)(lane & 7))), (lptr_t)(stage + 64), 16, 0, 2);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __builtin_amdgcn_wave_barrier();
+        u32 hxA, hxB;
+        const bool contA = look(first_tag, bktA, rankA, xfA, keyA, foundA, valA, homeA, hxA);
+        const bool contB = look(first_tag, bktB, rankB, xfB, keyB, foundB, valB, homeB, hxB);
+        const u64 cA = ballot64(contA), cB = ballot64(contB);
+        more = n_lead > NB || (cA | cB) != 0ULL;
+        if (cA) walk(first_tag, contA, hxA, bktA, foundA, homeA);                  // uncommon: walk on down the chain
+        if (cB) walk(first_tag, contB, hxB, bktB, foundB, homeB);
+        __builtin_amdgcn_wave_barrier();
+        return true;
+    };
+    if (pass(std::true_type{}))
+        while (more && pass(std::false_type{})) {}
+#ifdef BNS_COUNT_FETCHES
+    { const u64 gA = ballot64(foundA == 2u), gB = ballot64(foundB == 2u);
+      if ((gA | gB) && lane == 0) { atomicAdd(&g_fetch_count[2], (unsigned long long)(__popcll(gA) + __popcll(gB))); atomicAdd(&g_fetch_count[3], 1ULL); } }
+#endif
+    minb_ovf_walk(keyA, foundA, valA, ovf_slots, ovf_mask);
+    minb_ovf_walk(keyB, foundB, valB, ovf_slots, ovf_mask);
+    ra = ProbeResult{valA, (foundA & 1u) != 0u};
+    rb = ProbeResult{valB, (foundB & 1u) != 0u};
 }
 
 // ---- taxonomy ----------------------------------------------------------------------------------------

@@ -907,6 +907,33 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
 #ifdef BNS_PAD_UNIT                                             // marginal-cost experiments: N extra instructions per unit
     { u32 pv = (u32)lane; for (int q = 0; q < BNS_PAD_UNIT; ++q) asm volatile("v_mul_lo_u32 %0, %0, %0" : "+v"(pv)); asm volatile("" :: "v"(pv)); }
 #endif
+    // Contiguous seeds on the minbucket layout with a compile-time k (the usual form: no tags, no wide identity) go through the probe
+    // two rounds at a time (probe_minbucket2): one probe pass and one vote for the 120 k-mers of a 150-bp read instead of two.
+    constexpr bool PAIRS = !SPACED && LAYOUT == 2 && KT != 0 && !OVC && !WIDE;
+    // a round's found / valid lanes into missing, n_hits and the hit stream (k-mer order); returns the found mask
+    auto tally = [&](const ProbeResult &pr, bool valid) -> u64 {
+        const u64 fm = ballot64(pr.found), vm = ballot64(valid);
+        missing += (u32)__popcll(vm & ~fm);
+        if (want_hits && pr.found) { u32 *hp = cold_params()->hits; hp[readlane64(offv, (int)ob) + n_hits + (u32)__popcll(fm & lanemask_lt())] = pr.val; }
+        n_hits += (u32)__popcll(fm);
+        return fm;
+    };
+    // the vote of two consecutive rounds: each taxon counted once over both, half A's taxa first, each half in lane order -- the
+    // insertion order of voting round by round, which is what decides resolve ties
+    auto vote2 = [&](u64 fa, u32 va, u64 fb, u32 vb) {
+        u64 ra = fa, rb = fb;
+        while (ra | rb) {
+            const bool inA = ra != 0ULL;
+            const int l = __builtin_ctzll(inA ? ra : rb);
+            const u32 t = readlane(inA ? va : vb, l);
+            const u64 ma = ballot64(va == t) & ra, mb = ballot64(vb == t) & rb;
+            ra &= ~ma; rb &= ~mb;
+            const u32 c = (u32)(__popcll(ma) + __popcll(mb));
+            const bool eq = ckey == t;
+            if (ballot64(eq) & dmask) { ccnt = eq ? ccnt + c : ccnt; continue; }
+            if (!counter_insert(ckey, ccnt, dmask, keys, cnt, cap, D, t, c)) { overflow = true; break; }
+        }
+    };
     for (int m = 0; m < nm; ++m) {
         const u32 L = readlane((u32)offv, (int)ob + m + 1) - readlane((u32)offv, (int)ob + m);     // (reads are < 4 GiB: the low words suffice)
         const u32 nk = (L >= c && !(SPACED && p.emit_none)) ? L - c + 1u : 0u;     // (emit_none: spaced seeds only)
@@ -922,6 +949,36 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
                 if (!p.n_runs) M = (PACKED && clean) ? 0u : mask2_to_mask1((u32)lane < n_written ? pk[64 + lane] : ~0ULL);   // (the comb <= 64 path reads the image itself)
             }
             const u32 chunk_nk = (nk - j0) < rounds_per_chunk * 64u ? (nk - j0) : rounds_per_chunk * 64u;
+            if constexpr (PAIRS) {
+                // one round up to its bucket: extraction, canonical form, minimizer (the van Herk ring sees the rounds in order)
+                auto key_round = [&](u32 rd, u64 &key, u32 &bkt) -> bool {
+                    u64 win = 0;
+                    bool valid;
+                    extract_lds32(pk, rd, k, clean, win, valid);
+                    const u64 kf = win >> (64u - 2u * k), krc = revcomp_top(win, k);
+                    key = kf < krc ? kf : krc;
+                    bkt = bucket_of(round_minhash<MW, SPAN == 15>(kf, krc, rd, k, mlen, ring), n_mb);
+                    return valid && rd * 64u + (u32)lane < chunk_nk;
+                };
+                for (u32 rd = 0; rd * 64u < chunk_nk; rd += 2u) {
+                    u64 keyA;
+                    u32 bA;
+                    const bool vA = key_round(rd, keyA, bA);
+                    if ((rd + 1u) * 64u < chunk_nk) {                 // (wave-uniform) rounds rd and rd + 1: one probe, one vote
+                        u64 keyB;
+                        u32 bB;
+                        const bool vB = key_round(rd + 1u, keyB, bB);
+                        ProbeResult pa, pb;
+                        probe_minbucket2<(KT == 32), NB>(p.minb, keyA, bA, vA, keyB, bB, vB, aux, p.slots, p.ovf_mask, pa, pb);
+                        const u64 fa = tally(pa, vA), fb = tally(pb, vB);
+                        vote2(fa, pa.val, fb, pb.val);
+                    } else {                                          // an odd last round: the one-round probe
+                        const ProbeResult pa = probe_minbucket<(KT == 32), NB>(p.minb, keyA, bA, vA, aux, p.slots, p.ovf_mask);
+                        vote2(tally(pa, vA), pa.val, 0ULL, 0u);
+                    }
+                }
+                continue;
+            }
             for (u32 rd = 0; rd * 64u < chunk_nk; ++rd) {
                 const u32 jl = rd * 64u + (u32)lane;
                 u64 kmer, win = 0;
@@ -962,10 +1019,7 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
                                                                                      OVC ? minb_tagbit(minh) : 0u);
                 } else if (LAYOUT == 1) pr = probe_bucket(p.slots, p.bucket_mask, kmer, valid);
                 else                  pr = probe_khash(p.kflags, p.kkeys, p.kvals, p.kh_nb, kmer, valid);
-                const u64 fm = ballot64(pr.found), vm = ballot64(valid);
-                missing += (u32)__popcll(vm & ~fm);
-                if (want_hits && pr.found) { u32 *hp = cold_params()->hits; hp[readlane64(offv, (int)ob) + n_hits + (u32)__popcll(fm & lanemask_lt())] = pr.val; }
-                n_hits += (u32)__popcll(fm);
+                const u64 fm = tally(pr, valid);
 #ifdef BNS_ABLATION
                 u64 rem = (p.dbg & 2) ? 0ULL : fm;
 #else

@@ -1,0 +1,214 @@
+"""classify_kernel runs the k-mer rounds of a read through the clustered-table probe two at a time (probe_minbucket2): one
+set of probe passes and one vote for rounds 2p and 2p + 1.  These cases pin the device result -- taxon, missing, ambig and
+the ordered hit stream -- to the oracle where that pairing has edges: k-mer counts around the round and pair boundaries, an
+odd last round, chunks of 2048 bases (31 rounds: every chunk ends on a one-round probe), minimizer groups that straddle
+k-mer 64, pairs with more distinct groups than the 16-bucket stage holds, chain walks and overflow-table keys in the second
+round only, N bases at the round boundary, and units with more than 64 taxa.  Each case checks that its data reaches its
+branch, from a host restatement of the minimizer bucket (bucket_of / round_minhash, bns_device.hpp)."""
+import numpy as np
+import pytest
+
+import synth
+
+pytestmark = pytest.mark.gpu
+
+M32 = 0xFFFFFFFF
+CODE = np.full(256, 255, dtype=np.uint8)
+for _i, _c in enumerate(b"ACGT"):
+    CODE[_c] = _i
+    CODE[_c | 0x20] = _i
+
+
+def kmer_buckets(seq, k, m, n_mb):
+    """Home bucket of every k-mer of seq (None for one with a non-ACGT base): canonical m-mers, 32-bit identity."""
+    codes = CODE[np.frombuffer(seq.tobytes(), dtype=np.uint8)]
+    n = codes.size - k + 1
+    if n <= 0:
+        return []
+    nm = codes.size - m + 1
+    mh = []
+    for i in range(nm):
+        c = codes[i:i + m]
+        if (c == 255).any():
+            mh.append(None)
+            continue
+        fw = 0
+        rc = 0
+        for j, x in enumerate(c):
+            fw = (fw << 2) | int(x)
+            rc |= (3 - int(x)) << (2 * j)
+        x = min(fw, rc)
+        x = (x & M32) ^ (((x >> 32) << 13 | (x >> 32) >> 19) & M32) if m > 16 else x
+        mh.append((x * 0x7FEB352D) & M32)
+    out = []
+    for j in range(n):
+        win = mh[j:j + k - m + 1]
+        if any(h is None for h in win):
+            out.append(None)
+            continue
+        x = (min(win) * 0x9E3779B1) & M32
+        x ^= x >> 15
+        r = int("{:032b}".format(x)[::-1], 2)
+        out.append((r * n_mb) >> 32)
+    return out
+
+
+def pair_runs(b):
+    """Runs of equal buckets per pair of rounds (positions 128 p .. 128 p + 127 of a chunk-free read), and whether k-mers 63
+    and 64 share a bucket."""
+    runs = []
+    for p0 in range(0, len(b), 128):
+        seg = b[p0:p0 + 128]
+        runs.append(sum(1 for i, x in enumerate(seg) if x is not None and (i == 0 or seg[i - 1] != x)))
+    straddle = len(b) > 64 and b[63] is not None and b[63] == b[64]
+    return runs, straddle
+
+
+def check(ctx, oracle, w, reads, paired=False):
+    bases, offsets = synth.concat(reads)
+    exp = oracle.classify_batch(w.table, w.tax, w.k, bases, offsets, paired=paired, canon=True)
+    got = ctx.classify(bases, offsets, paired=paired, want_hits=True)
+    for key in ("taxon", "missing", "ambig", "n_hits"):
+        assert np.array_equal(got[key], exp[key]), key
+    inc = 2 if paired else 1
+    for u in range(len(reads) // inc):
+        s2 = reads[u * inc + 1].tobytes() if paired else None
+        _, _, _, hits = oracle.classify_seq(w.table, w.tax, w.k, reads[u * inc].tobytes(), s2, canon=True)
+        assert np.array_equal(got["hits"][u], hits), u
+    import bonsai_amd
+    words, bw, bm = bonsai_amd.pack_reads(bases, offsets, threads=2)
+    gp = ctx.classify_packed(words, bw, bm, offsets, paired=paired, want_hits=True)
+    for key in ("taxon", "missing", "ambig", "n_hits"):
+        assert np.array_equal(gp[key], got[key]), "packed " + key
+    assert all(np.array_equal(a, b) for a, b in zip(gp["hits"], got["hits"])), "packed hits"
+    return got
+
+
+def load(ctx, w, n_mb=0):
+    ctx.set_encoder(w.k, None, canonicalize=True)
+    ctx.set_table_buckets(n_mb)
+    ctx.set_minimizer_identity(32)
+    try:
+        ctx.load_table(w.n_buckets, w.flags, w.keys, w.vals, layout=2)
+    finally:
+        ctx.set_table_buckets(0)
+        ctx.set_minimizer_identity(0)
+    ctx.load_taxonomy(w.parent)
+    g = ctx.table_geometry()
+    assert g["identity_bits"] == 32                                     # (the wide identity keeps the one-round kernel)
+    return g
+
+
+_WORLDS = {}
+
+
+def world(oracle, k):
+    if k not in _WORLDS:
+        _WORLDS[k] = synth.make_world(oracle, seed=40 + k, k=k, genome_len=6000)
+    return _WORLDS[k]
+
+
+NK = [1, 63, 64, 65, 120, 127, 128, 129, 191, 192, 193]
+
+
+def shaped_reads(w, rng, n_per):
+    """Reads from the genomes with the k-mer counts above, reads past one and two 2048-base chunks, and N bases on either
+    side of the round boundary (k-mers 63 / 64)."""
+    g = np.concatenate(list(w.genomes.values()))
+    reads = []
+    for nk in NK * n_per + [2100 - w.k + 1, 4200 - w.k + 1, 2048 - w.k + 1 + 64]:
+        L = nk + w.k - 1
+        st = int(rng.integers(0, g.size - L))
+        r = synth.mutate(rng, g[st:st + L], 0.005, 0.0)
+        reads.append(r if rng.random() < 0.5 else synth.revcomp(r))
+    for pos in (62, 63, 64, 65, 63 + w.k - 1, 64 + w.k - 1):
+        st = int(rng.integers(0, g.size - 200))
+        r = g[st:st + 120 + w.k - 1].copy()
+        r[pos] = ord("N")
+        reads.append(r)
+    return reads
+
+
+@pytest.mark.parametrize("k", [31, 21, 27, 32])
+@pytest.mark.parametrize("paired", [False, True])
+def test_round_pairs_shapes(gpu_ctx, oracle, k, paired):
+    w = world(oracle, k)
+    geo = load(gpu_ctx, w)
+    rng = np.random.default_rng(7 * k + paired)
+    reads = shaped_reads(w, rng, 4)
+    if paired and len(reads) % 2:
+        reads.append(reads[0])
+    got = check(gpu_ctx, oracle, w, reads, paired)
+    assert (got["taxon"] != 0).mean() > 0.5
+    # branches: an odd last round (a one-round probe), a chunk of 31 rounds, the straddling group ranked once, a pair with
+    # more runs than the stage holds (a second pass)
+    nks = [r.size - k + 1 for r in reads]
+    assert any(nk > 0 and ((nk + 63) // 64) % 2 == 1 for nk in nks)
+    assert any(nk > 2048 - k + 1 for nk in nks)
+    runs, straddles = [], []
+    for r in reads:
+        if r.size - k + 1 > 2048 - k + 1:
+            continue
+        rr, s = pair_runs(kmer_buckets(r, k, geo["m"], geo["buckets"]))
+        runs += rr
+        straddles.append(s)
+    assert any(straddles)
+    assert max(runs) > 16
+
+
+def test_round_pairs_dense_table_second_round(gpu_ctx, oracle):
+    """A crowded table (keys down their chains, buckets whose keys went to the overflow table), probed by reads whose first
+    round is random sequence and whose second round comes from the genomes: the chain walks and overflow-table lookups are
+    half B's.  Arrival-order fill and the per-lane overflow walk: the kernel form that runs rounds in pairs."""
+    w = world(oracle, 31)
+    n_keys = int(w.table.header()[1])
+    gpu_ctx.debug_set(0x10 | 0x2000 | 0x100)                 # plain fill, never the cooperative lookup, forced overflow buckets
+    try:
+        geo = load(gpu_ctx, w, n_mb=max(16, n_keys * 10 // 85))
+        assert geo["spilled_keys"] > 0 and gpu_ctx.table_stats()["n_overflow_keys"] > 0
+        rng = np.random.default_rng(99)
+        g = np.concatenate(list(w.genomes.values()))
+        reads = []
+        for i in range(600):
+            nk = int(rng.integers(65, 129))
+            tail = nk - 64 + w.k - 1
+            st0 = int(rng.integers(0, g.size - tail))
+            reads.append(np.concatenate([synth.rand_seq(rng, 64), g[st0:st0 + tail]]))
+        got = check(gpu_ctx, oracle, w, reads)
+        assert (got["n_hits"] > 0).mean() > 0.9
+        # every found k-mer sits in round B: the first 64 k-mers are random (k-mers 34..63 straddle into the genome part)
+        check(gpu_ctx, oracle, w, reads, paired=True)
+    finally:
+        gpu_ctx.debug_set(0)
+
+
+def test_round_pairs_many_taxa(gpu_ctx, oracle):
+    """Units with more than 64 distinct taxa (the counter past its registers) and with exactly tied scores, where the
+    insertion order of the vote -- round A's taxa before round B's -- feeds the tie fold."""
+    k = 31
+    n_leaf = 90
+    pairs = [(1, 1), (2, 1), (3, 1)] + [(100 + i, 2 + (i % 2)) for i in range(n_leaf)]
+    tax = oracle.Taxonomy(pairs=pairs)
+    rng = np.random.default_rng(5)
+    table = oracle.Table()
+    segs = []
+    for i in range(n_leaf):
+        s = synth.rand_seq(rng, 40)
+        segs.append(s)
+        oracle.lca_map_add(table, tax, k, s.tobytes(), 100 + i)
+    w = synth.World()
+    w.k, w.gaps, w.canon, w.tax, w.table, w.parent = k, None, True, tax, table, tax.parent
+    w.flags, w.keys, w.vals = table.arrays()
+    w.n_buckets = table.n_buckets
+    load(gpu_ctx, w)
+    reads = []
+    for rep in range(40):
+        order = rng.permutation(n_leaf)[: int(rng.integers(3, n_leaf + 1))]
+        reads.append(np.concatenate([segs[i] for i in order]))
+    for rep in range(40):                                   # two taxa, each once per round: a tie whose fold order is A, B
+        a, b = rng.choice(n_leaf, 2, replace=False)
+        reads.append(np.concatenate([segs[a], synth.rand_seq(rng, 40), segs[b]]))
+    got = check(gpu_ctx, oracle, w, reads)
+    assert (got["n_hits"] > 0).all()
+    d = [len(set(h.tolist())) for h in got["hits"]]
+    assert max(d) > 64
