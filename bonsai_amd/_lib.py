@@ -25,6 +25,7 @@ class BonsaiAmdError(RuntimeError):
 # bns_classify_text (include/bonsai_amd.h): flags, status codes and the two structs
 TEXT_FINAL, TEXT_TRIM_READNO, TEXT_DEVICE, TEXT_PARSE_ONLY, TEXT_DEFER = 1, 2, 4, 8, 16
 TEXT_OK, TEXT_IRREGULAR, TEXT_NO_RECORD, TEXT_CAP = 0, 1, 2, 3
+LINES_ALL = 1
 TEXT_WHY = {1: "CR", 2: "LEADING", 4: "AFTER_QUAL", 8: "QUAL_LEN", 16: "PLUS_RUN", 32: "LONG_RECORD", 64: "LINES"}
 
 
@@ -33,7 +34,8 @@ class TextOut(C.Structure):
                 ("run_start", C.c_void_p), ("n_runs", C.c_void_p), ("seq_len", C.c_void_p), ("rec_pos", C.c_void_p),
                 ("name_off", C.c_void_p), ("names", C.c_void_p), ("names_cap", C.c_uint64),
                 ("run_tax", C.c_void_p), ("run_len", C.c_void_p), ("runs_cap", C.c_uint64),
-                ("words", C.c_void_p), ("nmask", C.c_void_p)]
+                ("words", C.c_void_p), ("nmask", C.c_void_p),
+                ("lines", C.c_void_p), ("lines_cap", C.c_uint64), ("line_off", C.c_void_p), ("lines_flags", C.c_uint32)]
 
 
 class GzResult(C.Structure):
@@ -46,7 +48,7 @@ class TextInfo(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("consumed", C.c_uint64 * 2), ("total_bases", C.c_uint64), ("names_bytes", C.c_uint64),
                 ("n_runs_total", C.c_uint64), ("run_tax", C.POINTER(C.c_uint32)), ("run_len", C.POINTER(C.c_uint32)),
                 ("status", C.c_int32), ("why", C.c_uint32), ("n_slices", C.c_uint32), ("n_launches", C.c_uint32),
-                ("ms_parse", C.c_double), ("ms_classify", C.c_double)]
+                ("ms_parse", C.c_double), ("ms_classify", C.c_double), ("lines_bytes", C.c_uint64), ("ms_lines", C.c_double)]
 
 
 _lib = None

@@ -262,12 +262,16 @@ class Context:
         return {"taxon": taxon, "missing": missing, "ambig": ambig, "n_hits": n_hits, "runs": runs, "n_runs_total": n}
 
     def classify_text(self, texts, final=True, limit=None, trim_readno=False, parse_only=False, want_runs=False, want_words=False,
-                      cap_records=None, names_cap=None, device_ptrs=None, runs_cap=None, defer=False, between=None):
+                      cap_records=None, names_cap=None, device_ptrs=None, runs_cap=None, defer=False, between=None,
+                      want_lines=False, emit_all=True, lines_cap=None):
         """bns_classify_text: FASTA / FASTQ TEXT (bytes, or a pair of bytes: mates) parsed, packed and classified on the device.
         device_ptrs = [(ptr, n_bytes), ...]: the text is already in HBM.  -> dict with n_records, consumed, status, why, per-unit
         results, per-record seq_len / rec_pos / names, runs as classify_runs() gives them, the packed words when asked for.
         defer: the call in two halves (BNS_TEXT_DEFER, then bns_text_finish; `between()` runs in between) -- "first_half" in the result is
-        what the first half reported."""
+        what the first half reported.
+        want_lines: the units' Kraken lines, assembled on the device: "lines" (bytes), "line_off" (uint64, n_units + 1: unit u's line is
+        lines[line_off[u]:line_off[u + 1]], empty when it is not printed), "lines_bytes".  emit_all: unclassified units are printed too
+        (`classify -a`); lines_cap: room in bytes (default: ample)."""
         if isinstance(texts, (bytes, bytearray, memoryview, np.ndarray)):
             texts = [texts]
         bufs = [np.frombuffer(bytes(t), dtype=np.uint8) if not isinstance(t, np.ndarray) else np.ascontiguousarray(t, dtype=np.uint8) for t in texts]
@@ -298,6 +302,11 @@ class Context:
             nw = int(sizes.sum()) // 32 + cap + 2
             a["words"] = np.zeros(nw, np.uint64); a["nmask"] = np.zeros(nw, np.uint32)
             o.words = a["words"].ctypes.data; o.nmask = a["nmask"].ctypes.data
+        if want_lines:
+            lcap = int(lines_cap) if lines_cap is not None else 24 * int(sizes.sum()) + 128 * cap + 64
+            a["lines"] = np.zeros(max(1, lcap), np.uint8); a["line_off"] = np.zeros(nu_cap + 1, np.uint64)
+            o.lines = a["lines"].ctypes.data; o.lines_cap = lcap; o.line_off = a["line_off"].ctypes.data
+            o.lines_flags = _lib.LINES_ALL if emit_all else 0
         info = _lib.TextInfo()
         flags = (_lib.TEXT_FINAL if final else 0) | (_lib.TEXT_TRIM_READNO if trim_readno else 0) | (_lib.TEXT_PARSE_ONLY if parse_only else 0) | \
                 (_lib.TEXT_DEVICE if device_ptrs is not None else 0) | (_lib.TEXT_DEFER if defer else 0)
@@ -329,6 +338,10 @@ class Context:
                     tax = np.ctypeslib.as_array(info.run_tax, shape=(nt,)).copy() if nt else np.zeros(0, np.uint32)
                     ln = np.ctypeslib.as_array(info.run_len, shape=(nt,)).copy() if nt else np.zeros(0, np.uint32)
                 res["runs"] = [(tax[int(s):int(s) + int(c)], ln[int(s):int(s) + int(c)]) for s, c in zip(a["run_start"][:nu], a["n_runs"][:nu])]
+            if want_lines:
+                nb = int(info.lines_bytes)
+                res["lines"] = a["lines"][:nb].tobytes(); res["line_off"] = a["line_off"][:nu + 1].copy(); res["lines_bytes"] = nb
+                res["ms_lines"] = float(info.ms_lines)
         if want_words:
             nw = int(self.L.bns_packed_words(int(info.total_bases), n))
             res["words"] = a["words"][:nw].copy(); res["nmask"] = a["nmask"][:nw].copy()

@@ -40,6 +40,7 @@ struct SmallLayout {
     u32 ovf_count, max_len; u32 pad1[30];      // [128,256) classify: units handed to the overflow kernel; longest read of the batch
     unsigned long long load_cnt[8];            // [256,320) table load / device build counters
     unsigned long long runs_cursor;            // [320,328) hit_runs_kernel's output cursor
+    unsigned long long lines_cursor;           // [328,336) lines_len_kernel: line bytes of the call so far
 };
 constexpr size_t SMALL_BYTES = 512;
 constexpr size_t SMALL_CLASSIFY_ZERO = offsetof(SmallLayout, max_len) + sizeof(u32);   // what a classify call zeroes, in one memset
@@ -322,7 +323,7 @@ bool launch_fixed_k(const ClassifyParams &p, unsigned grid, hipStream_t st, bool
 
 extern "C" {
 
-int bns_version(void) { return 106; }
+int bns_version(void) { return 107; }
 
 int bns_device_pci_bus_id(int device, char *out, int cap)
 {

@@ -38,7 +38,8 @@
 //   offsets_kernel     how many records this call takes (complete ones in front of `limit`; the minimum over a pair of files), then
 //                      sequence lengths -> base offsets, name lengths -> name offsets (look-back)
 //   pack_text_kernel   one wavefront per record: bases gathered from the record's lines -> 2-bit words + invalid-base flags; its name
-// then classify_device_impl on the packed words, and hit_runs_kernel when the caller prints runs.
+// then classify_device_impl on the packed words, hit_runs_kernel when the caller prints runs, and the kernels of bns_lines.hpp when he
+// takes the finished Kraken lines.
 #include <new>
 
 namespace bns {
@@ -617,6 +618,8 @@ __global__ __launch_bounds__(256) void pack_text_kernel(ParseArgs pa, PackOut o)
 }  // namespace ingest
 }  // namespace bns
 
+#include "bns_lines.hpp"
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // host side of the entry point
 namespace {
@@ -640,10 +643,11 @@ struct TextWork {                                       // the context's workspa
     DevBuf ls[2], line_off[2], cand[2][10], info, offsets, words, nmask, hits;   // cand[s]: cand, c_next, c_seq, c_name, c_line1, c_single, c_flags, c_inside, c_pos, rec_cand (StreamArgs)
     // what goes back to the host, TWICE: batch b's results are copied (on the back stream) while batch b + 1 is parsed and classified into the other set
     DevBuf seq_len[2], name_off[2], names[2], pos64[2], out[2][4], runs[2][4];
+    DevBuf lines[2], lines_off[2], lines_state;         // the batch's Kraken lines, where each unit's starts; look-back words of lines_len_kernel
     hipEvent_t ev_done[2] = {}, tc0[2] = {}, tc1[2] = {};
-    hipEvent_t t0 = nullptr, t1 = nullptr;
+    hipEvent_t t0 = nullptr, t1 = nullptr, tl0 = nullptr, tl1 = nullptr;
     CallInfo *h_info = nullptr;                         // page-locked
-    unsigned long long *h_cursor = nullptr;
+    unsigned long long *h_cursor = nullptr;             // [0..1]: runs so far behind batch set q; [2]: line bytes so far
     struct TextCall *call = nullptr;                    // the state of the call in progress -- or, behind BNS_TEXT_DEFER, of the one that waits for bns_text_finish
 };
 
@@ -652,6 +656,9 @@ struct TextCall {
     bool pending = false;                               // BNS_TEXT_DEFER: parsed and packed, the open batch waits for bns_text_finish
     bns_text_out out{};
     bool parse_only = false, want_runs = false, on_device = false;
+    bool want_lines = false;                            // out.lines: hit runs are made whether or not the caller takes them
+    u64 lines_done = 0, lines_before_prev = 0;          // line bytes of the batches classified so far / in front of the last one
+    float ms_lines = 0;
     u32 ns = 1;
     u32 batch_no = 0;                                   // batches classified so far
     u64 runs_done = 0;                                  // runs whose copy to the host has been queued
@@ -731,10 +738,14 @@ int text_roll_back(bns_ctx *ctx, TextWork &tw, TextCall &tc)
         if (rc != BNS_OK) return rc;
     }
     tc.done_reads = tc.reads_before_prev; tc.names_done = tc.names_before_prev; tc.bases_done = tc.bases_before_prev;
+    tc.lines_done = tc.lines_before_prev;
     for (u32 s = 0; s < tc.ns; ++s) tc.cons[s] = tc.cons_before_prev[s];
     tc.acc_reads = tc.acc_bases = tc.acc_names = 0; tc.acc_max_len = 0;
     return BNS_OK;
 }
+
+// (the last classified batch recorded the events around its hit-run and line kernels)
+static inline bool want_lines_prev(const TextCall &tc) { return tc.want_lines && !tc.parse_only; }
 
 // ---- the open batch -> one classify launch; its results behind those of the batches in front.  Results leave on the back stream:
 // batch b's arrays (set b & 1) are copied out while batch b + 1 is parsed and classified into the other set.  Before a batch is
@@ -745,12 +756,15 @@ int text_flush_batch(bns_ctx *ctx, TextWork &tw, TextCall &tc)
     if (tc.rolled_back || tc.acc_reads == 0) return BNS_OK;
     hipStream_t st = ctx->stream, bs = ctx->back_stream;
     const bns_text_out *out = &tc.out;
-    const bool parse_only = tc.parse_only, want_runs = tc.want_runs;
+    const bool parse_only = tc.parse_only, want_runs = tc.want_runs, want_lines = tc.want_lines, need_runs = want_runs || want_lines;
+    bool lines_overflow = false;
+    u64 lines_bytes = 0;
     const u32 ns = tc.ns, q = tc.batch_no & 1u;
     const u64 n_reads = tc.acc_reads, n_units = tc.acc_reads / ns, u_done = tc.open_reads0 / ns;
     // (the back stream drained: the out / runs arrays of set q are free, and the run count of the batch in front is on the host)
     HIPCHK(ctx, hipStreamSynchronize(bs));
     if (tc.batch_no && ctx->timing && !parse_only) { float ms = 0; if (hipEventElapsedTime(&ms, tw.tc0[q ^ 1u], tw.tc1[q ^ 1u]) == hipSuccess) tc.ms_classify += ms; }
+    if (tc.batch_no && ctx->timing && want_lines_prev(tc)) { float ms = 0; if (hipEventElapsedTime(&ms, tw.tl0, tw.tl1) == hipSuccess) tc.ms_lines += ms; }
     int frc = text_flush_runs_of_prev(ctx, tw, tc);
     if (frc != BNS_OK) return frc;
     if (tc.runs_overflow) { tc.status = BNS_TEXT_CAP; return text_roll_back(ctx, tw, tc); }
@@ -759,17 +773,50 @@ int text_flush_batch(bns_ctx *ctx, TextWork &tw, TextCall &tc)
     if (!parse_only) {
         if (ctx->timing) HIPCHK(ctx, hipEventRecord(tw.tc0[q], st));
         frc = classify_device_impl(ctx, nullptr, (const u64 *)tw.words.p, (const u32 *)tw.nmask.p, (const u64 *)tw.offsets.p, n_reads, tc.acc_bases,
-                                   std::max<u32>(tc.acc_max_len, 1u), ns == 2 ? 1 : 0, o0, out->missing || want_runs ? o1 : nullptr,
-                                   out->ambig || want_runs ? o2 : nullptr, (out->n_hits || want_runs) ? o3 : nullptr, want_runs ? (u32 *)tw.hits.p : nullptr, st);
+                                   std::max<u32>(tc.acc_max_len, 1u), ns == 2 ? 1 : 0, o0, out->missing || need_runs ? o1 : nullptr,
+                                   out->ambig || need_runs ? o2 : nullptr, (out->n_hits || need_runs) ? o3 : nullptr, need_runs ? (u32 *)tw.hits.p : nullptr, st);
         if (frc != BNS_OK) return frc;
         ++tc.n_launches;
         tc.prev_units = n_units;
         if (ctx->timing) HIPCHK(ctx, hipEventRecord(tw.tc1[q], st));
-        if (want_runs) {
+        // (runs that only the lines are made of: counted from 0 in every batch, they never leave the device)
+        const u64 runs_base = want_runs ? tc.runs_done : 0;
+        if (want_lines && ctx->timing) HIPCHK(ctx, hipEventRecord(tw.tl0, st));
+        if (need_runs) {
+            if (!want_runs) HIPCHK(ctx, hipMemsetAsync(d_cur, 0, 8, st));
             hipLaunchKernelGGL(hit_runs_kernel, dim3(grid_for(ctx, (n_units + HIT_RUNS_GROUP - 1) / HIT_RUNS_GROUP, 4)), dim3(256), 0, st, (const u32 *)tw.hits.p,
                                (const u64 *)tw.offsets.p, ns, (const u32 *)o3, (u64)n_units, (u64 *)tw.runs[q][0].p, (u32 *)tw.runs[q][1].p,
-                               (u32 *)tw.runs[q][2].p - tc.runs_done, (u32 *)tw.runs[q][3].p - tc.runs_done, d_cur);
+                               (u32 *)tw.runs[q][2].p - runs_base, (u32 *)tw.runs[q][3].p - runs_base, d_cur);
             HIPCHK(ctx, hipGetLastError());
+        }
+        if (want_lines) {
+            // Lengths and places first; the batch's byte count comes back before a byte is written: the device buffer is sized by it (a
+            // bound from the batch's bases would be 22 bytes a base), and a batch that does not fit the caller's buffer is known at once.
+            unsigned long long *d_lcur = &((SmallLayout *)ctx->small.p)->lines_cursor;   // (zeroed at the start of the call, like runs_cursor)
+            LinesArgs la{};
+            la.taxon = o0; la.missing = o1; la.ambig = o2;
+            la.seq_len = (const u32 *)tw.seq_len[q].p; la.name_off = (const u32 *)tw.name_off[q].p;
+            la.names = (const char *)tw.names[q].p; la.name_base = (u32)tc.open_names0;
+            la.run_start = (const u64 *)tw.runs[q][0].p; la.n_runs = (const u32 *)tw.runs[q][1].p;
+            la.run_tax = (const u32 *)tw.runs[q][2].p - runs_base; la.run_len = (const u32 *)tw.runs[q][3].p - runs_base;
+            la.n_units = n_units; la.nmates = ns; la.emit_all = (out->lines_flags & BNS_LINES_ALL) ? 1u : 0u;
+            la.line_off = (u64 *)tw.lines_off[q].p; la.base = tc.lines_done;
+            la.ticket = (u32 *)tw.lines_state.p; la.state = (u64 *)tw.lines_state.p + 1; la.cursor = d_lcur;
+            const size_t n_blocks = (size_t)((n_units + 255) / 256);
+            HIPCHK(ctx, hipMemsetAsync(tw.lines_state.p, 0, (n_blocks + 2) * 8, st));
+            hipLaunchKernelGGL(lines_len_kernel, dim3(grid_for(ctx, n_units, 256)), dim3(256), 0, st, la);
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipMemcpyAsync(&tw.h_cursor[2], d_lcur, 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, hipStreamSynchronize(st));
+            lines_bytes = tw.h_cursor[2] - tc.lines_done;
+            if (tw.h_cursor[2] > out->lines_cap) lines_overflow = true;
+            else if (lines_bytes) {
+                if ((frc = ensure(ctx, tw.lines[q], (size_t)lines_bytes + 64)) != BNS_OK) return frc;
+                la.lines = (char *)tw.lines[q].p; la.cap = lines_bytes;
+                hipLaunchKernelGGL(lines_write_kernel, dim3(grid_for(ctx, (n_units + LINES_GROUP - 1) / LINES_GROUP, 4)), dim3(256), 0, st, la);
+                HIPCHK(ctx, hipGetLastError());
+            }
+            if (ctx->timing) HIPCHK(ctx, hipEventRecord(tw.tl1, st));
         }
     }
     // the copies, on the back stream behind this batch's kernels; the next batch is parsed and classified meanwhile
@@ -785,6 +832,10 @@ int text_flush_batch(bns_ctx *ctx, TextWork &tw, TextCall &tc)
             HIPCHK(ctx, hipMemcpyAsync(out->n_runs + u_done, tw.runs[q][1].p, (size_t)n_units * 4, hipMemcpyDeviceToHost, bs));
             HIPCHK(ctx, hipMemcpyAsync(&tw.h_cursor[q], d_cur, 8, hipMemcpyDeviceToHost, bs));
         }
+        if (want_lines && !lines_overflow) {
+            if (lines_bytes) HIPCHK(ctx, hipMemcpyAsync(out->lines + tc.lines_done, tw.lines[q].p, (size_t)lines_bytes, hipMemcpyDeviceToHost, bs));
+            if (out->line_off) HIPCHK(ctx, hipMemcpyAsync(out->line_off + u_done, tw.lines_off[q].p, (size_t)(n_units + 1) * 8, hipMemcpyDeviceToHost, bs));
+        }
     }
     if (out->seq_len) HIPCHK(ctx, hipMemcpyAsync(out->seq_len + tc.open_reads0, tw.seq_len[q].p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, bs));
     if (out->rec_pos) HIPCHK(ctx, hipMemcpyAsync(out->rec_pos + tc.open_reads0, tw.pos64[q].p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, bs));
@@ -798,6 +849,14 @@ int text_flush_batch(bns_ctx *ctx, TextWork &tw, TextCall &tc)
     tc.reads_before_prev = tc.open_reads0; tc.names_before_prev = tc.open_names0; tc.bases_before_prev = tc.open_bases0;
     for (u32 s = 0; s < ns; ++s) tc.cons_before_prev[s] = tc.open_cons0[s];
     tc.acc_reads = tc.acc_bases = tc.acc_names = 0; tc.acc_max_len = 0;
+    tc.lines_before_prev = tc.lines_done;
+    if (lines_overflow) {
+        // this batch's lines do not fit the caller's buffer: it is handed back like one whose runs did not fit (its bytes were never
+        // written, the cursor counts on: nothing of this call reads it again)
+        tc.status = BNS_TEXT_CAP;
+        return text_roll_back(ctx, tw, tc);
+    }
+    tc.lines_done += lines_bytes;
     return BNS_OK;
 }
 
@@ -822,6 +881,7 @@ void text_fill_info(bns_ctx *ctx, const TextCall &tc, bns_text_info *info)
     info->run_tax = tc.out.run_tax ? tc.out.run_tax : ctx->h_run_tax; info->run_len = tc.out.run_len ? tc.out.run_len : ctx->h_run_len;
     info->status = tc.status; info->why = tc.why; info->n_slices = tc.rounds + 1; info->n_launches = tc.n_launches;
     info->ms_parse = tc.ms_parse; info->ms_classify = tc.ms_classify;
+    info->lines_bytes = tc.lines_done; info->ms_lines = tc.ms_lines;
 }
 
 // The end of a call (or of bns_text_finish): the open batch (whatever ended the rounds, the records in front of that are the caller's);
@@ -835,6 +895,7 @@ int text_wrap_up(bns_ctx *ctx, TextWork &tw, TextCall &tc, bns_text_info *info)
     WUCHK(hipStreamSynchronize(st));
     WUCHK(hipStreamSynchronize(bs));
     if (tc.batch_no && ctx->timing && !tc.parse_only) { float ms = 0; if (hipEventElapsedTime(&ms, tw.tc0[(tc.batch_no - 1u) & 1u], tw.tc1[(tc.batch_no - 1u) & 1u]) == hipSuccess) tc.ms_classify += ms; }
+    if (tc.batch_no && ctx->timing && want_lines_prev(tc)) { float ms = 0; if (hipEventElapsedTime(&ms, tw.tl0, tw.tl1) == hipSuccess) tc.ms_lines += ms; }
     if (!tc.rolled_back) {
         if ((rc = text_flush_runs_of_prev(ctx, tw, tc)) != BNS_OK) return text_bail(ctx, tc, rc);
         if (tc.runs_overflow) { tc.status = BNS_TEXT_CAP; if ((rc = text_roll_back(ctx, tw, tc)) != BNS_OK) return text_bail(ctx, tc, rc); }
@@ -862,11 +923,13 @@ void text_work_free(bns_ctx *ctx)
         bufs.push_back(&tw->seq_len[q]);
         for (DevBuf &b : tw->out[q]) bufs.push_back(&b);
         for (DevBuf &b : tw->runs[q]) bufs.push_back(&b);
+        bufs.push_back(&tw->lines[q]); bufs.push_back(&tw->lines_off[q]);
         bufs.push_back(&tw->name_off[q]); bufs.push_back(&tw->names[q]); bufs.push_back(&tw->pos64[q]);
     }
+    bufs.push_back(&tw->lines_state);
     for (DevBuf *b : bufs) release(*b);
     for (auto &row : tw->up) for (Upload &u : row) for (hipEvent_t e : u.ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {tw->t0, tw->t1, tw->ev_done[0], tw->ev_done[1], tw->tc0[0], tw->tc0[1], tw->tc1[0], tw->tc1[1]}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {tw->t0, tw->t1, tw->tl0, tw->tl1, tw->ev_done[0], tw->ev_done[1], tw->tc0[0], tw->tc0[1], tw->tc1[0], tw->tc1[1]}) if (e) (void)hipEventDestroy(e);
     if (tw->h_info) (void)hipHostFree(tw->h_info);
     if (tw->h_cursor) (void)hipHostFree(tw->h_cursor);
     delete tw->call;
@@ -989,6 +1052,8 @@ int bns_classify_text(bns_ctx *ctx, const char *const *text, const uint64_t *tex
     if (!parse_only && !out->taxon) return BNS_ERR_ARG;
     if ((out->run_start != nullptr) != (out->n_runs != nullptr)) return BNS_ERR_ARG;
     if (out->name_off && !out->names) return BNS_ERR_ARG;
+    if (out->lines && parse_only) return BNS_ERR_ARG;
+    if (out->line_off && !out->lines) return BNS_ERR_ARG;
     if ((out->run_tax != nullptr) != (out->run_len != nullptr) || (out->run_tax && !out->run_start)) return BNS_ERR_ARG;
     const u32 ns = (u32)n_streams;
     for (u32 s = 0; s < ns; ++s) {
@@ -1007,8 +1072,9 @@ int bns_classify_text(bns_ctx *ctx, const char *const *text, const uint64_t *tex
     hipStream_t st = ctx->stream;
     if (!tw.h_info) {
         HIPCHK(ctx, hipHostMalloc((void **)&tw.h_info, sizeof(CallInfo), hipHostMallocDefault));
-        HIPCHK(ctx, hipHostMalloc((void **)&tw.h_cursor, 16, hipHostMallocDefault));
+        HIPCHK(ctx, hipHostMalloc((void **)&tw.h_cursor, 32, hipHostMallocDefault));
         HIPCHK(ctx, hipEventCreate(&tw.t0)); HIPCHK(ctx, hipEventCreate(&tw.t1));
+        HIPCHK(ctx, hipEventCreate(&tw.tl0)); HIPCHK(ctx, hipEventCreate(&tw.tl1));
         for (int q = 0; q < 2; ++q) {
             HIPCHK(ctx, hipEventCreateWithFlags(&tw.ev_done[q], hipEventDisableTiming));
             HIPCHK(ctx, hipEventCreate(&tw.tc0[q])); HIPCHK(ctx, hipEventCreate(&tw.tc1[q]));
@@ -1108,10 +1174,14 @@ int bns_classify_text(bns_ctx *ctx, const char *const *text, const uint64_t *tex
     if ((rc = ensure(ctx, tw.words, ((size_t)cap_bases / 32 + cap_reads + 2) * 8)) != BNS_OK) return bail(rc);
     if ((rc = ensure(ctx, tw.nmask, ((size_t)cap_bases / 32 + cap_reads + 2) * 4)) != BNS_OK) return bail(rc);
     if ((rc = ensure(ctx, tw.info, info_bytes)) != BNS_OK) return bail(rc);
-    const bool want_runs = out->run_start != nullptr && !parse_only;
+    const bool want_runs = out->run_start != nullptr && !parse_only, want_lines = out->lines != nullptr;
     if (!parse_only) {
         for (int q = 0; q < 2; ++q) for (int i = 0; i < 4; ++i) if ((rc = ensure(ctx, tw.out[q][i], (size_t)cap_reads * 4 + 64)) != BNS_OK) return bail(rc);
-        if (want_runs) {
+        if (want_lines) {                                       // (the line bytes themselves: sized batch by batch, text_flush_batch)
+            for (int q = 0; q < 2; ++q) if ((rc = ensure(ctx, tw.lines_off[q], (size_t)(cap_reads + 1) * 8 + 64)) != BNS_OK) return bail(rc);
+            if ((rc = ensure(ctx, tw.lines_state, ((size_t)cap_reads / 256 + 4) * 8)) != BNS_OK) return bail(rc);
+        }
+        if (want_runs || want_lines) {
             if ((rc = ensure(ctx, tw.hits, (size_t)cap_bases * 4 + 64)) != BNS_OK) return bail(rc);
             for (int q = 0; q < 2; ++q) {
                 if ((rc = ensure(ctx, tw.runs[q][0], (size_t)cap_reads * 8 + 64)) != BNS_OK) return bail(rc);
@@ -1128,11 +1198,12 @@ int bns_classify_text(bns_ctx *ctx, const char *const *text, const uint64_t *tex
     const u8 *d_text[2] = {src[0].base, src[1].base};
 
     if (want_runs) TXCHK(hipMemsetAsync(&((SmallLayout *)ctx->small.p)->runs_cursor, 0, 8, st));
+    if (want_lines) { TXCHK(hipMemsetAsync(&((SmallLayout *)ctx->small.p)->lines_cursor, 0, 8, st)); if (out->line_off) out->line_off[0] = 0; }
     CallInfo *d_ci = (CallInfo *)tw.info.p;
     if (!ctx->back_stream) TXCHK(hipStreamCreateWithFlags(&ctx->back_stream, hipStreamNonBlocking));
     // ---- the call's state (struct TextCall: it outlives the call behind BNS_TEXT_DEFER), under the names the rounds below use
     tc = TextCall{};
-    tc.out = *out; tc.parse_only = parse_only; tc.want_runs = want_runs; tc.on_device = on_device; tc.ns = ns;
+    tc.out = *out; tc.parse_only = parse_only; tc.want_runs = want_runs; tc.want_lines = want_lines; tc.on_device = on_device; tc.ns = ns;
     for (u32 s = 0; s < ns; ++s) { tc.cons[s] = tc.open_cons0[s] = tc.cons_before_prev[s] = tc.rel[s] = src[s].rel; tc.up[s] = src[s].up; }
     u32 &batch_no = tc.batch_no, (&cons)[2] = tc.cons, &acc_max_len = tc.acc_max_len, (&open_cons0)[2] = tc.open_cons0, &why = tc.why, &rounds = tc.rounds;
     u64 &done_reads = tc.done_reads, &names_done = tc.names_done, &bases_done = tc.bases_done, &acc_reads = tc.acc_reads, &acc_bases = tc.acc_bases, &acc_names = tc.acc_names;

@@ -5,7 +5,8 @@ namespace bns {
 // ---------------------------------------------------------------------------------------------- text on the device
 // One plain FASTA / FASTQ file classified WITHOUT a host parser or packer (bns_classify_text: record boundaries, names and the
 // 2-bit words are made by kernels from the file's bytes).  What the host still does: read(2) into page-locked blocks, one
-// library call per block, Kraken lines from the names and results that come back.
+// library call per block, and the write(2) of the Kraken lines that come back finished (lines_on_device; with BNS_LINES_GPU=0 the
+// formatter threads make them from the names, results and hit runs that come back instead).
 //
 // The file is cut into blocks of B bytes at NOMINAL offsets b * B.  Block b is the records that START in [start_b, (b + 1) * B):
 // start_b = where the first record at or behind b * B starts = where block b - 1 stopped (bns_classify_text's `limit`: the record
@@ -23,7 +24,7 @@ unsigned format_text_job(ClassifierGeneric &c, const TextJob &j, std::vector<Cla
     const unsigned nt = (unsigned)std::max(1, std::min<int>(c.nt_, (int)(n / 4096 + 1)));
     if (parts.size() < nt) parts.resize(nt);
     std::vector<u64> ncls(nt * 2, 0);
-    const bool lines = c.get_emit_kraken() != 0;
+    const bool lines = c.get_emit_kraken() != 0 && !j.dev_lines;  // (lines from the device: only the tally is left to do)
     static const char filler = 'N';
     parallel_units(nt, n, [&](unsigned lo, unsigned hi, unsigned t) {
         ClassifierGeneric::Work::Part &part = parts[t];
@@ -96,7 +97,8 @@ u64 process_text_gpu(ClassifierGeneric &c, const char *fq1, std::FILE *out)
     std::condition_variable cv;
     std::vector<std::unique_ptr<TextJob>> spare;               // recycled jobs (their page-locked buffers with them)
     unsigned jobs_made = 0;
-    unsigned max_jobs = 2 * G + 4;                             // blocks in flight: in a call, uploaded ahead of it (prefetch), read ahead of that, being formatted
+    const bool dev_lines = lines_on_device(c);
+    unsigned max_jobs = 2 * G + 4 + (dev_lines ? 2 : 0);        // blocks in flight: in a call, uploaded ahead of it (prefetch), read ahead of that, being formatted (device lines: until written)
     if (const char *e = std::getenv("BNS_TEXT_JOBS")) max_jobs = (unsigned)std::max(2, std::min(64, std::atoi(e)));
     struct Piece { TextJob *job; size_t off, len; };
     std::deque<Piece> pieces;                                  // reads to do
@@ -173,12 +175,17 @@ u64 process_text_gpu(ClassifierGeneric &c, const char *fq1, std::FILE *out)
     // ---- one library call on a block from a known (or guessed) start
     auto call_block = [&](bns_ctx *ctx, TextJob &j) {
         const u64 rel = j.start - j.file_off;
+        u64 lines_cap = dev_lines ? ((j.bytes - rel) / 160 + 4096) * LINES_ROOM_PER_RECORD : 0;
         u64 cap = (j.bytes - rel) / 160 + 4096, names_cap = cap * 24, runs_cap = cap * 4;   // (316 bytes, ~10 of name and 1-3 hit runs per 150-bp FASTQ record; BNS_TEXT_CAP doubles them)
         for (;;) {
             j.taxon.resize(ctx, cap);
             bns_text_out o{};
             o.taxon = j.taxon.data();
-            if (!taxon_only) {
+            j.dev_lines = dev_lines; j.lines_bytes = 0;
+            if (dev_lines) {
+                j.lines.resize(ctx, lines_cap);
+                o.lines = j.lines.data(); o.lines_cap = lines_cap; o.lines_flags = c.get_emit_all() ? BNS_LINES_ALL : 0u;
+            } else if (!taxon_only) {
                 j.missing.resize(ctx, cap); j.ambig.resize(ctx, cap); j.n_hits.resize(ctx, cap); j.seq_len.resize(ctx, cap); j.name_off.resize(ctx, cap + 1);
                 j.run_start.resize(ctx, cap); j.n_runs.resize(ctx, cap); j.names.resize(ctx, names_cap);
                 o.missing = j.missing.data(); o.ambig = j.ambig.data(); o.n_hits = j.n_hits.data(); o.seq_len = j.seq_len.data();
@@ -192,8 +199,8 @@ u64 process_text_gpu(ClassifierGeneric &c, const char *fq1, std::FILE *out)
             const u64 tb = j.bytes - rel;
             const u64 limit = j.last ? ~0ULL : (j.file_off + B) - j.start;
             chk(ctx, bns_classify_text(ctx, &tp, &tb, 1, limit, (j.last ? BNS_TEXT_FINAL : 0) | BNS_TEXT_TRIM_READNO, cap, &o, &info), "bns_classify_text");
-            if (info.status == BNS_TEXT_CAP) { cap *= 2; names_cap *= 2; runs_cap *= 2; continue; }      // (short records, long names or many runs: once more with room)
-            j.n_records = info.n_records; j.status = info.status; j.why = info.why;
+            if (info.status == BNS_TEXT_CAP) { cap *= 2; names_cap *= 2; runs_cap *= 2; lines_cap *= 2; continue; }      // (short records, long names or many runs: once more with room)
+            j.n_records = info.n_records; j.lines_bytes = info.lines_bytes; j.status = info.status; j.why = info.why;
             j.end = j.start + info.consumed[0];
             j.ok = info.status == BNS_TEXT_OK && (j.last ? j.end == j.file_off + j.bytes : j.end >= j.file_off + B);
             return;
@@ -295,19 +302,25 @@ u64 process_text_gpu(ClassifierGeneric &c, const char *fq1, std::FILE *out)
     if (!error.empty()) die(error);
     if (timing)
         std::fprintf(stderr, "[timing] text on the device: %llu blocks of %llu MiB on %u device(s), %u readers: page-lock %.3f s, pread %.3f (summed), calls %.3f (summed), format %.3f, write %.3f; "
-                             "callers waited %.3f s for blocks, %llu uploads started ahead of their call; %llu guessed starts, %llu classified again%s\n",
+                             "callers waited %.3f s for blocks, %llu uploads started ahead of their call; %llu guessed starts, %llu classified again%s%s\n",
                      (unsigned long long)next_verify, (unsigned long long)(B >> 20), G, R, t_alloc, t_read, t_call, sink.t_format, sink.t_write, t_idle, (unsigned long long)n_ahead,
-                     (unsigned long long)n_guess, (unsigned long long)n_redo, resume_at != fsize ? "; the host parser takes the rest" : "");
+                     (unsigned long long)n_guess, (unsigned long long)n_redo, resume_at != fsize ? "; the host parser takes the rest" : "", sink.note().c_str());
     return resume_at;
 }
 
 // the result arrays of one bns_classify_text call, sized for `cap` records (names_cap / runs_cap bytes / runs)
-void size_text_job(bns_ctx *ctx, TextJob &j, bns_text_out &o, bool taxon_only, u64 cap, u64 names_cap, u64 runs_cap)
+void size_text_job(bns_ctx *ctx, TextJob &j, bns_text_out &o, bool taxon_only, u64 cap, u64 names_cap, u64 runs_cap, u64 lines_cap, bool emit_all)
 {
     j.taxon.resize(ctx, cap);
     o = bns_text_out{};
     o.taxon = j.taxon.data();
+    j.dev_lines = !taxon_only && lines_cap != 0; j.lines_bytes = 0;
     if (taxon_only) return;
+    if (lines_cap) {
+        j.lines.resize(ctx, lines_cap);
+        o.lines = j.lines.data(); o.lines_cap = lines_cap; o.lines_flags = emit_all ? BNS_LINES_ALL : 0u;
+        return;
+    }
     j.missing.resize(ctx, cap); j.ambig.resize(ctx, cap); j.n_hits.resize(ctx, cap); j.seq_len.resize(ctx, cap); j.name_off.resize(ctx, cap + 1);
     j.run_start.resize(ctx, cap); j.n_runs.resize(ctx, cap); j.names.resize(ctx, names_cap);
     o.missing = j.missing.data(); o.ambig = j.ambig.data(); o.n_hits = j.n_hits.data(); o.seq_len = j.seq_len.data();
@@ -391,9 +404,9 @@ bool process_device_text(ClassifierGeneric &c, DeviceTextSource &src, std::FILE 
     units_done = units;
     if (src.gave_up()) handed_back = true;
     if (timing)
-        std::fprintf(stderr, "[timing] %s on the device: %llu jobs on %u device(s); %s; classify calls %.3f (their kernels: text %.3f, classify %.3f), format %.3f, write %.3f%s\n",
+        std::fprintf(stderr, "[timing] %s on the device: %llu jobs on %u device(s); %s; classify calls %.3f (their kernels: text %.3f, classify %.3f), format %.3f, write %.3f%s%s\n",
                      what, (unsigned long long)n_jobs, G, src.timing_line().c_str(), t_call, t_gpu_parse, t_gpu_cls, sink.t_format, sink.t_write,
-                     handed_back ? "; the host parser takes the rest" : "");
+                     handed_back ? "; the host parser takes the rest" : "", sink.note().c_str());
     return !handed_back;
 }
 
@@ -449,16 +462,16 @@ bool process_device_text_pair(ClassifierGeneric &c, DeviceTextSource &src0, Devi
             const double t0 = tnow();
             const char *tp[2] = {side[0].t >= 0 ? side[0].src->buf(0, side[0].t) + side[0].off : nullptr, side[1].t >= 0 ? side[1].src->buf(0, side[1].t) + side[1].off : nullptr};
             const u64 tb[2] = {side[0].len, side[1].len};
-            u64 cap = (tb[0] + tb[1]) / 160 + 4096, names_cap = cap * 24, runs_cap = cap * 4;
+            u64 cap = (tb[0] + tb[1]) / 160 + 4096, names_cap = cap * 24, runs_cap = cap * 4, lines_cap = lines_on_device(c) ? cap * LINES_ROOM_PER_RECORD : 0;
             bns_text_info info{};
             for (;;) {
                 bns_text_out o{};
-                size_text_job(ctx, *j, o, taxon_only, cap, names_cap, runs_cap);
+                size_text_job(ctx, *j, o, taxon_only, cap, names_cap, runs_cap, lines_cap, c.get_emit_all() != 0);
                 chk(ctx, bns_classify_text(ctx, tp, tb, 2, ~0ULL, BNS_TEXT_DEVICE | BNS_TEXT_TRIM_READNO | (final_call ? BNS_TEXT_FINAL : 0), cap, &o, &info), "bns_classify_text");
-                if (info.status == BNS_TEXT_CAP && info.n_records == 0) { cap *= 2; names_cap *= 2; runs_cap *= 2; continue; }
+                if (info.status == BNS_TEXT_CAP && info.n_records == 0) { cap *= 2; names_cap *= 2; runs_cap *= 2; lines_cap *= 2; continue; }
                 break;
             }
-            j->seq = n_calls; j->mates = 2; j->n_records = info.n_records;
+            j->seq = n_calls; j->mates = 2; j->n_records = info.n_records; j->lines_bytes = info.lines_bytes;
             for (int s = 0; s < 2; ++s) { side[s].off += info.consumed[s]; side[s].len -= info.consumed[s]; }
             t_call += tnow() - t0;
             t_gpu_parse += info.ms_parse * 1e-3; t_gpu_cls += info.ms_classify * 1e-3;
@@ -483,9 +496,9 @@ bool process_device_text_pair(ClassifierGeneric &c, DeviceTextSource &src0, Devi
     if (!failure.empty()) { sink.finish(0, true); die(failure); }
     sink.finish(n_calls);
     if (timing)
-        std::fprintf(stderr, "[timing] %s, text on the device: %llu calls; first file: %s; second file: %s; classify calls %.3f (their kernels: text %.3f, classify %.3f), format %.3f, write %.3f%s\n",
+        std::fprintf(stderr, "[timing] %s, text on the device: %llu calls; first file: %s; second file: %s; classify calls %.3f (their kernels: text %.3f, classify %.3f), format %.3f, write %.3f%s%s\n",
                      what, (unsigned long long)n_calls, src0.timing_line().c_str(), src1.timing_line().c_str(), t_call, t_gpu_parse, t_gpu_cls, sink.t_format, sink.t_write,
-                     handed_back ? "; the host parser takes the rest" : "");
+                     handed_back ? "; the host parser takes the rest" : "", sink.note().c_str());
     return !handed_back;
 }
 
@@ -699,9 +712,9 @@ bool process_text_gpu_pair(ClassifierGeneric &c, const char *fq1, const char *fq
     units_done = units;
     if (timing)
         std::fprintf(stderr, "[timing] pair of files, text on the device: %llu jobs, blocks of %llu + %llu MiB on %u device(s), %u readers: pread %.3f s (summed), calls %.3f (summed), format %.3f, write %.3f; "
-                             "waited %.3f s for blocks, %llu uploads started ahead of their call%s\n",
+                             "waited %.3f s for blocks, %llu uploads started ahead of their call%s%s\n",
                      (unsigned long long)n_jobs, (unsigned long long)(B >> 20), (unsigned long long)(B2 >> 20), G, R, t_read, t_call, sink.t_format, sink.t_write, t_idle,
-                     (unsigned long long)n_ahead, handed_back ? "; the host parser takes the rest" : "");
+                     (unsigned long long)n_ahead, handed_back ? "; the host parser takes the rest" : "", sink.note().c_str());
     return !handed_back;
 }
 

@@ -19,7 +19,22 @@ struct TextJob {
     PinArr<u64> run_start;
     PinArr<char> names;
     PinArr<u32> run_tax, run_len;                              // (page-locked: the library copies the hit runs straight into them)
+    // Kraken lines assembled on the device (bns_text_out::lines): of the arrays above only taxon comes back with them
+    PinArr<char> lines;
+    u64 lines_bytes = 0;
+    bool dev_lines = false;
 };
+
+// Who makes the Kraken lines of text that the device parses: its kernels (bns_lines.hpp), or the formatter threads from names, results
+// and hit runs.  BNS_LINES_GPU=1 / 0 decides; unset: LINES_GPU_DEFAULT.  (FASTQ-comment output never comes here.)
+constexpr bool LINES_GPU_DEFAULT = false;
+inline bool lines_on_device(const ClassifierGeneric &c)
+{
+    if (!c.get_emit_kraken()) return false;
+    if (const char *e = std::getenv("BNS_LINES_GPU")) { if (e[0] == '0') return false; if (e[0] == '1') return true; }
+    return LINES_GPU_DEFAULT;
+}
+constexpr u64 LINES_ROOM_PER_RECORD = 96;                    // bytes of line room per record of room (a 150-bp read's line: 45-70); BNS_TEXT_CAP doubles it
 
 unsigned format_text_job(ClassifierGeneric &c, const TextJob &j, std::vector<ClassifierGeneric::Work::Part> &parts);
 
@@ -52,6 +67,17 @@ public:
     }
     bool failed() { std::lock_guard<std::mutex> lk(mu_); return !error_.empty(); }
     double t_format = 0, t_write = 0;
+    u64 dev_line_bytes = 0, dev_jobs = 0, host_jobs = 0;
+    // for the pipelines' BNS_CLI_TIMING lines: who made the Kraken lines
+    std::string note()
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (!c_.get_emit_kraken()) return "; no Kraken lines";
+        char b[160];
+        std::snprintf(b, sizeof b, "; lines: %s formatter (%llu bytes from the device in %llu jobs, %llu jobs formatted on the host)",
+                      dev_jobs ? (host_jobs ? "device+host" : "device") : "host", (unsigned long long)dev_line_bytes, (unsigned long long)dev_jobs, (unsigned long long)host_jobs);
+        return b;
+    }
 private:
     static constexpr unsigned NF = 2, NSETS = 2 * NF;
     void fail(const std::string &w) { std::lock_guard<std::mutex> lk(mu_); if (error_.empty()) error_ = w; cancel_ = true; cv_.notify_all(); }
@@ -73,9 +99,13 @@ private:
                 w_taxa_[set].clear();
                 if (c_.taxon_out_ && j->n_records) w_taxa_[set].assign(j->taxon.data(), j->taxon.data() + j->n_records / j->mates);
                 const double t1 = tnow();
-                recycle_(std::move(j));
+                const bool dev = j->dev_lines;
+                const u64 nb = j->lines_bytes;
+                // (lines from the device are written out of the job's own buffer: it is recycled behind the write)
+                if (dev) held_[set] = std::move(j); else recycle_(std::move(j));
                 std::lock_guard<std::mutex> lk(mu_);
                 t_format += t1 - t0;
+                if (c_.get_emit_kraken()) { if (dev) { ++dev_jobs; dev_line_bytes += nb; } else ++host_jobs; }
                 w_pending_[set] = true; w_parts_[set] = np;
                 cv_.notify_all();
             }
@@ -97,6 +127,11 @@ private:
                     const char *p = out_sets_[set][t].p;
                     for (size_t off = 0, n = out_sets_[set][t].n; off < n;) { const ssize_t w = ::write(ofd_, p + off, n - off); if (w <= 0) die("write failed"); off += (size_t)w; }
                 }
+                if (held_[set]) {
+                    const char *p = held_[set]->lines.data();
+                    for (size_t off = 0, n = (size_t)held_[set]->lines_bytes; off < n;) { const ssize_t w = ::write(ofd_, p + off, n - off); if (w <= 0) die("write failed"); off += (size_t)w; }
+                    recycle_(std::move(held_[set]));
+                }
                 if (c_.taxon_out_ && !w_taxa_[set].empty())
                     if (std::fwrite(w_taxa_[set].data(), 4, w_taxa_[set].size(), c_.taxon_out_) != w_taxa_[set].size()) die("write failed (taxon file)");
                 const double t1 = tnow();
@@ -115,6 +150,7 @@ private:
     std::map<u64, std::unique_ptr<TextJob>> ready_;
     std::vector<ClassifierGeneric::Work::Part> out_sets_[NSETS];
     std::vector<u32> w_taxa_[NSETS];
+    std::unique_ptr<TextJob> held_[NSETS];
     bool w_pending_[NSETS] = {};
     unsigned w_parts_[NSETS] = {};
     u64 w_next_ = 0, n_final_ = ~0ULL;
@@ -160,7 +196,8 @@ private:
 };
 
 // the result arrays of one bns_classify_text call, sized for `cap` records (names_cap / runs_cap bytes / runs)
-void size_text_job(bns_ctx *ctx, TextJob &j, bns_text_out &o, bool taxon_only, u64 cap, u64 names_cap, u64 runs_cap);
+// lines_cap != 0: the lines come from the device (taxon and the line bytes only)
+void size_text_job(bns_ctx *ctx, TextJob &j, bns_text_out &o, bool taxon_only, u64 cap, u64 names_cap, u64 runs_cap, u64 lines_cap = 0, bool emit_all = false);
 
 // The library calls on ONE block's text.  As a rule one call in two halves: parse() under the turn, finish() behind it.  A call that
 // stops at BNS_TEXT_CAP (records of a few bytes, long names: the arrays are sized for ~160 bytes of text per record) is finished at once,
@@ -189,11 +226,12 @@ struct BlockCalls {
     {
         taxon_only_ = !c.get_emit_kraken();
         cap_ = (tb[0] + tb[1]) / 160 + 4096; names_cap_ = cap_ * 24; runs_cap_ = cap_ * 4;
+        lines_cap_ = lines_on_device(c) ? cap_ * LINES_ROOM_PER_RECORD : 0;
         for (;;) {
             if (limit != ~0ULL && used[0] >= limit) { status = BNS_TEXT_OK; pending_ = false; return; }     // (everything in front of the limit went with the calls so far)
             j_ = pool.get();
             bns_text_out o{};
-            size_text_job(ctx, *j_, o, taxon_only_, cap_, names_cap_, runs_cap_);
+            size_text_job(ctx, *j_, o, taxon_only_, cap_, names_cap_, runs_cap_, lines_cap_, c.get_emit_all() != 0);
             for (int s = 0; s < n_streams; ++s) { cp_[s] = tp[s] + used[s]; cb_[s] = tb[s] - used[s]; }
             lim_ = limit == ~0ULL ? ~0ULL : limit - used[0];
             const double tc0 = tnow();
@@ -208,8 +246,8 @@ struct BlockCalls {
             chk(ctx, bns_text_finish(ctx, &fin), "bns_text_finish");
             ms_classify += fin.ms_classify;
             for (int s = 0; s < n_streams; ++s) used[s] += fin.consumed[s];
-            if (fin.n_records) submit(fin.n_records); else pool.put(std::move(j_));
-            cap_ *= 2; names_cap_ *= 2; runs_cap_ *= 2;
+            if (fin.n_records) submit(fin.n_records, fin.lines_bytes); else pool.put(std::move(j_));
+            cap_ *= 2; names_cap_ *= 2; runs_cap_ *= 2; lines_cap_ *= 2;
         }
         // the block's last call: its second half waits.  (its job's number is taken now: the jobs are printed in this order)
         for (int s = 0; s < n_streams; ++s) used[s] += first_.consumed[s];
@@ -229,26 +267,27 @@ struct BlockCalls {
             std::fprintf(stderr, "[timing] a bns_text_finish call took %.3f s: %llu records, its classify kernels %.1f ms\n", tnow() - tf0, (unsigned long long)fin.n_records, fin.ms_classify);
         ms_classify += fin.ms_classify;
         while (fin.n_records != first_.n_records) {
-            // the hit runs did not fit the job's arrays (the first half cannot know how many there will be): the same call once more, in
+            // the hit runs (or the lines) did not fit the job's arrays (the first half cannot know how many there will be): the same call once more, in
             // one piece, with room -- the text is still where it was, the records and where the call stops are the same
             if (fin.status != BNS_TEXT_CAP) die("bns_text_finish: fewer records than the first half of the call reported");
-            runs_cap_ *= 2;
+            runs_cap_ *= 2; lines_cap_ *= 2;
             bns_text_out o{};
-            size_text_job(ctx, *j_, o, taxon_only_, cap_, names_cap_, runs_cap_);
+            size_text_job(ctx, *j_, o, taxon_only_, cap_, names_cap_, runs_cap_, lines_cap_, c.get_emit_all() != 0);
             chk(ctx, bns_classify_text(ctx, cp_, cb_, n_streams, lim_, flags, cap_, &o, &fin), "bns_classify_text");
             ms_classify += fin.ms_classify;
             if (fin.n_records == first_.n_records && (fin.consumed[0] != first_.consumed[0] || fin.consumed[1] != first_.consumed[1]))
                 die("bns_classify_text: the same text parsed differently the second time");
         }
         const u64 seq = j_->seq;
-        submit(fin.n_records, &seq);
+        submit(fin.n_records, fin.lines_bytes, &seq);
     }
     bool has_pending() const { return pending_; }
 
 private:
-    void submit(u64 n_records, const u64 *seq = nullptr)
+    void submit(u64 n_records, u64 lines_bytes, const u64 *seq = nullptr)
     {
         j_->seq = seq ? *seq : n_jobs++;
+        j_->lines_bytes = lines_bytes;
         j_->n_records = n_records; j_->mates = (unsigned)n_streams;
         units += n_records / (u64)n_streams;
         sink.submit(std::move(j_));
@@ -257,7 +296,7 @@ private:
     bns_text_info first_{};
     const char *cp_[2] = {nullptr, nullptr};
     u64 cb_[2] = {0, 0}, lim_ = ~0ULL;
-    u64 cap_ = 0, names_cap_ = 0, runs_cap_ = 0;
+    u64 cap_ = 0, names_cap_ = 0, runs_cap_ = 0, lines_cap_ = 0;
     bool taxon_only_ = false, pending_ = false;
 };
 

@@ -433,7 +433,21 @@ typedef struct bns_text_out {
     uint64_t *words; uint32_t *nmask;                /* the records' 2-bit image, bns_pack_reads' layout with DENSE flag words
                                                         (bns_packed_words(total_bases, n_records) entries each): calls of one
                                                         piece only (<= 64 MiB of text per stream), BNS_ERR_ARG otherwise */
+    /* (version 107; all zero: as before) The finished Kraken lines of the call's units, assembled by kernels from what is in HBM anyway --
+     * name, length, result, hit runs -- instead of those ingredients coming back for a host formatter.  Replaces
+     * append_kraken_classification (classifier.h:112-129, with append_taxa_runs / append_counts, classifier.h:45-70) and the kt_for loop that
+     * formats a chunk (classifier.h:269-287).  lines[0, info->lines_bytes): the lines in unit order, contiguous across the call's batches;
+     * a pair prints the first mate's name and length; a unit is printed when BNS_LINES_ALL is set or its taxon is not 0
+     * (classifier.h:239).  line_off (optional; n_units + 1 entries, cap_records + 1 of room): unit u's line is lines[line_off[u],
+     * line_off[u + 1]) -- empty for a unit that is not printed.  With lines the hit runs are computed whether or not run_start / n_runs are
+     * given, and every other array but taxon stays optional.  lines_cap too small: BNS_TEXT_CAP, with n_records / consumed[] / lines_bytes
+     * those of the batches whose lines fit whole (behind BNS_TEXT_DEFER: bns_text_finish then reports fewer records than the first half
+     * did); call again from consumed[].  Not with BNS_TEXT_PARSE_ONLY (BNS_ERR_ARG). */
+    char *lines; uint64_t lines_cap;                 /* page-locked or plain host memory */
+    uint64_t *line_off;
+    uint32_t lines_flags;                            /* BNS_LINES_* */
 } bns_text_out;
+#define BNS_LINES_ALL         1u    /* print unclassified units too (emit_all: `bonsai classify -a`) */
 typedef struct bns_text_info {
     uint64_t n_records, consumed[2], total_bases, names_bytes, n_runs_total;
     const uint32_t *run_tax, *run_len;               /* owned by the context, valid until its next call */
@@ -441,6 +455,9 @@ typedef struct bns_text_info {
     uint32_t why;                                    /* IRREGULAR: BNS_TEXT_WHY_* bits of the first offending stretch */
     uint32_t n_slices, n_launches;                   /* parses (one per upload piece, and more where a window filled up) / classify launches (one per ~2 M records) */
     double ms_parse, ms_classify;                    /* device time of the parse kernels / of classify (HIP events; bns_set_timing) */
+    uint64_t lines_bytes;                            /* (version 107) bytes written to out->lines */
+    double ms_lines;                                 /* out->lines: hit runs, line lengths, the read-back of the batch's byte count and the line
+                                                        bytes, first kernel to last (HIP events; bns_set_timing) */
 } bns_text_info;
 #define BNS_TEXT_WHY_CR          1u    /* (round 5: a line ends in '\r'.  Round 6 reads CRLF text on the device: not reported any more) */
 #define BNS_TEXT_WHY_LEADING     2u    /* text in front of the first header */

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Randomised end-to-end soak of `bonsai classify` (reader + GPU + device run encoding + formatter) against lines built from
 the oracle: FASTQ / FASTA / multi-line / CRLF / .gz / BGZF inputs and `bonsai pack` containers, single and paired, -a, chunk sizes that cut the input into many
-bseq_read chunks, all three layouts, -P stretches of a few KB parsed side by side.  usage: tools/fuzz_cli.py [seconds] [seed]"""
+bseq_read chunks, all three layouts, -P stretches of a few KB parsed side by side.  With `lines` every invocation runs twice, BNS_LINES_GPU=1 (Kraken lines assembled on
+the device) and =0 (the host formatter): both must equal the oracle's lines, and a difference keeps the inputs for diagnosis (the soak stops there).
+usage: tools/fuzz_cli.py [seconds] [seed] [lines]"""
 import gzip
 import os
 import subprocess
@@ -20,6 +22,8 @@ O.build()
 BIN = os.path.join(ROOT, "bonsai_amd", "bin", "bonsai")
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+lines_ab = len(sys.argv) > 3 and sys.argv[3] == "lines"
+n_dev_bytes = 0
 d = tempfile.mkdtemp(prefix="fuzzcli")
 w = synth.make_world(O, seed=3, k=31, genome_len=6000)
 db = os.path.join(d, "bns.db"); nodes = os.path.join(d, "nodes.dmp")
@@ -113,7 +117,18 @@ while time.time() - t0 < budget:
             env["BNS_BGZF_GPU_THREADS"] = str(int(rng.integers(1, 4)))
             if rng.random() < 0.5: env["BNS_GZ_THREADS"] = str(int(rng.choice([0, 0, 2])))
         if rng.random() < 0.2: env["BNS_BGZF_NO_MMAP"] = "1"
+    if lines_ab:
+        env["BNS_LINES_GPU"] = "1"; env["BNS_CLI_TIMING"] = "1"
     p = subprocess.run([BIN] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120, env=env)
+    if lines_ab:
+        import re
+        m = re.search(r"lines: \w+ formatter \((\d+) bytes from the device", p.stderr.decode(errors="replace"))
+        n_dev_bytes += int(m.group(1)) if m else 0
+        p0 = subprocess.run([BIN] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120, env=dict(env, BNS_LINES_GPU="0"))
+        if p0.returncode != p.returncode or p0.stdout != p.stdout:
+            print("LINES DIFFER (device / host formatter) seed", seed0 * 100003 + it, "args", args, "bytes", len(p.stdout), len(p0.stdout), "inputs kept in", d,
+                  "env", {k: v for k, v in env.items() if k.startswith("BNS_")})
+            sys.exit(1)
     exp = []
     for i, r in enumerate(reads1):
         t, m, a, hits = O.classify_seq(w.table, w.tax, 31, r.tobytes(), reads2[i].tobytes() if paired else None)
@@ -128,4 +143,4 @@ while time.time() - t0 < budget:
         if f.startswith(("a_", "b_")):
             os.remove(os.path.join(d, f))
     it += 1
-print("cli fuzz ok: %d invocations, %.0f s" % (it, time.time() - t0))
+print("cli fuzz ok: %d invocations, %.0f s" % (it, time.time() - t0) + ("; device lines against host lines: 0 differing, %d line bytes came from the device" % n_dev_bytes if lines_ab else ""))
