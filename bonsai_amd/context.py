@@ -131,9 +131,20 @@ class Context:
 
     def debug_set(self, bits):
         """test / profiling switches (BNS_DBG_* in bns_api.hip); not part of the public header"""
-        self.L.bns_debug_set.argtypes = [vp, C.c_int]
-        self.L.bns_debug_set.restype = C.c_int
         self._chk(self.L.bns_debug_set(self.h, bits), "bns_debug_set")
+
+    def last_classify_form(self):
+        """bns_debug_last_classify_form (a test aid, not part of the public header): what the last classify call of this context
+        launched.  "kernel": (SPACED, LAYOUT, KT, NM, SPAN, OVC, WIDE, PACKED) of the classify_kernel instantiation (None before the
+        first call); "overflow_kernel": (SPACED, LAYOUT, WIDE, PACKED) of the classify_overflow_kernel one, None when no unit went
+        there; "overflow_units" / "overflow_grid"; "chunk" (units per claim) and "grid" of classify_kernel."""
+        w = np.zeros(18, dtype=np.uint32)
+        n = self.L.bns_debug_last_classify_form(self.h, _p(w, u32p), w.size)
+        if n != w.size:
+            raise BonsaiAmdError("bns_debug_last_classify_form: %d words" % n)
+        v = [int(x) for x in w]
+        return {"kernel": tuple(v[1:9]) if v[0] else None, "overflow_kernel": tuple(v[10:14]) if v[9] else None,
+                "overflow_units": v[14], "overflow_grid": v[15], "chunk": v[16], "grid": v[17]}
 
     def load_table(self, n_buckets, flags, keys, vals, layout=_lib.LAYOUT_MINBUCKET):
         flags = np.ascontiguousarray(flags, dtype=np.uint32)

@@ -62,6 +62,15 @@ constexpr int BNS_DBG_SLICE_8K = 0x4000;            // bns_classify_batch upload
 constexpr int BNS_DBG_STREAM_CHUNK_SHIFT = 16, BNS_DBG_STREAM_CHUNK_MASK = 0x1F << 16;   // log2 of the streamed chunk (0 = 27)
 constexpr int BNS_DBG_SPACED_M_SHIFT = 24, BNS_DBG_SPACED_M_MASK = 0x1F << 24;           // spaced seeds: force the run minimizer's m
 
+// What the last classify dispatch launched (bns_debug_last_classify_form, a test aid): the template arguments of the
+// classify_kernel instantiation, of the classify_overflow_kernel one when units went there, and the launch geometry.  Written
+// by launch_classify / launch_classify_overflow from their own template arguments, so it cannot say anything but what ran.
+struct ClassifyForm {
+    enum { VALID, SPACED, LAYOUT, KT, NM, SPAN, OVC, WIDE, PACKED, OVF_LAUNCHED, OVF_SPACED, OVF_LAYOUT, OVF_WIDE, OVF_PACKED, OVF_UNITS,
+           OVF_GRID, CHUNK, GRID, N_WORDS };
+    u32 w[N_WORDS] = {0};
+};
+
 }  // namespace
 
 struct bns_text_work;                                     // bns_ingest.hip: workspace of bns_classify_text
@@ -115,6 +124,7 @@ struct bns_ctx {
     u32 table_span = 0;             // the window candidate (MIN_CANDS span: 15 / 11 / 8) the loaded table was built with; 0: none (spaced seed)
     std::string warn;               // what the last table load has to say about the table it built (bns_table_warning)
     int dbg = 0;
+    ClassifyForm last_form;     // bns_debug_last_classify_form
     u32 table_k = 0;            // k the minimizer-clustered layout was built for
     // taxonomy
     TaxNode *nodes = nullptr;
@@ -281,11 +291,31 @@ int ready(bns_ctx *ctx, bool need_table, bool need_tax)
 }  // namespace
 
 namespace {
+// Every classify_kernel / classify_overflow_kernel launch goes through these two: the instantiation launched and the one
+// recorded in the form are the same template arguments.
+template <bool SP, int LY, int KT, int NM, int SPAN, bool OVC, bool WIDE, bool PACKED>
+void launch_classify(ClassifyForm &f, const ClassifyParams &p, unsigned grid, hipStream_t st)
+{
+    f = ClassifyForm{};
+    f.w[ClassifyForm::VALID] = 1; f.w[ClassifyForm::SPACED] = SP; f.w[ClassifyForm::LAYOUT] = LY; f.w[ClassifyForm::KT] = KT;
+    f.w[ClassifyForm::NM] = NM; f.w[ClassifyForm::SPAN] = SPAN; f.w[ClassifyForm::OVC] = OVC; f.w[ClassifyForm::WIDE] = WIDE;
+    f.w[ClassifyForm::PACKED] = PACKED; f.w[ClassifyForm::CHUNK] = p.chunk; f.w[ClassifyForm::GRID] = grid;
+    hipLaunchKernelGGL((classify_kernel<SP, LY, KT, NM, SPAN, OVC, WIDE, PACKED>), dim3(grid), dim3(256), 0, st, p);
+}
+template <bool SP, int LY, bool WIDE, bool PACKED>
+void launch_classify_overflow(ClassifyForm &f, const ClassifyParams &p, u32 n_units, unsigned grid, hipStream_t st, u32 *scratch, u64 total_bases)
+{
+    f.w[ClassifyForm::OVF_LAUNCHED] = 1; f.w[ClassifyForm::OVF_SPACED] = SP; f.w[ClassifyForm::OVF_LAYOUT] = LY;
+    f.w[ClassifyForm::OVF_WIDE] = WIDE; f.w[ClassifyForm::OVF_PACKED] = PACKED; f.w[ClassifyForm::OVF_UNITS] = n_units;
+    f.w[ClassifyForm::OVF_GRID] = grid;
+    hipLaunchKernelGGL((classify_overflow_kernel<SP, LY, WIDE, PACKED>), dim3(grid), dim3(64), 0, st, p, scratch, total_bases);
+}
+
 // classify_kernel<false, MINBUCKET, KT, NM, SPAN, OVC, WIDE> for the (k, window) pairs the loader can produce with a common k.
 // FULL: every form of the overflow lookup and the minimizer identity; otherwise the usual form only (the rest falls back to the
 // generic kernel, which reads k from its arguments).
 template <int KT, int SPAN, bool FULL>
-bool launch_kt(const ClassifyParams &p, unsigned grid, hipStream_t st, bool ovc, bool wide, bool packed)
+bool launch_kt(ClassifyForm &f, const ClassifyParams &p, unsigned grid, hipStream_t st, bool ovc, bool wide, bool packed)
 {
     if ((int)p.k != KT || KT - (int)p.m != SPAN || !p.canon) return false;     // (non-canonical contiguous seeds: the generic kernel)
     if (!FULL && (ovc || wide || packed)) return false;
@@ -293,31 +323,31 @@ bool launch_kt(const ClassifyParams &p, unsigned grid, hipStream_t st, bool ovc,
     auto go = [&](auto nm) {
         constexpr int NM = decltype(nm)::value;
         if constexpr (FULL) {
-            if (packed) { hipLaunchKernelGGL((classify_kernel<false, 2, KT, NM, SPAN, false, false, true>), dim3(grid), dim3(256), 0, st, p); return; }
+            if (packed) { launch_classify<false, 2, KT, NM, SPAN, false, false, true>(f, p, grid, st); return; }
             if (wide) {
-                if (ovc) hipLaunchKernelGGL((classify_kernel<false, 2, KT, NM, SPAN, true, true>), dim3(grid), dim3(256), 0, st, p);
-                else     hipLaunchKernelGGL((classify_kernel<false, 2, KT, NM, SPAN, false, true>), dim3(grid), dim3(256), 0, st, p);
+                if (ovc) launch_classify<false, 2, KT, NM, SPAN, true, true, false>(f, p, grid, st);
+                else     launch_classify<false, 2, KT, NM, SPAN, false, true, false>(f, p, grid, st);
                 return;
             }
-            if (ovc) { hipLaunchKernelGGL((classify_kernel<false, 2, KT, NM, SPAN, true, false>), dim3(grid), dim3(256), 0, st, p); return; }
+            if (ovc) { launch_classify<false, 2, KT, NM, SPAN, true, false, false>(f, p, grid, st); return; }
         }
-        hipLaunchKernelGGL((classify_kernel<false, 2, KT, NM, SPAN, false, false>), dim3(grid), dim3(256), 0, st, p);
+        launch_classify<false, 2, KT, NM, SPAN, false, false, false>(f, p, grid, st);
     };
     if (p.nmates == 1) go(std::integral_constant<int, 1>{}); else go(std::integral_constant<int, 2>{});
     return true;
 }
 template <int KT, bool FULL>
-bool launch_k(const ClassifyParams &p, unsigned grid, hipStream_t st, bool ovc, bool wide, bool packed)
+bool launch_k(ClassifyForm &f, const ClassifyParams &p, unsigned grid, hipStream_t st, bool ovc, bool wide, bool packed)
 {
     constexpr int S0 = KT - (int)minimizer_len(KT, MIN_CANDS[0]), S1 = KT - (int)minimizer_len(KT, MIN_CANDS[1]), S2 = KT - (int)minimizer_len(KT, MIN_CANDS[2]);
-    return launch_kt<KT, S0, FULL>(p, grid, st, ovc, wide, packed) || launch_kt<KT, S1, FULL>(p, grid, st, ovc, wide, packed) ||
-           launch_kt<KT, S2, FULL>(p, grid, st, ovc, wide, packed);
+    return launch_kt<KT, S0, FULL>(f, p, grid, st, ovc, wide, packed) || launch_kt<KT, S1, FULL>(f, p, grid, st, ovc, wide, packed) ||
+           launch_kt<KT, S2, FULL>(f, p, grid, st, ovc, wide, packed);
 }
-bool launch_fixed_k(const ClassifyParams &p, unsigned grid, hipStream_t st, bool ovc, bool wide, bool packed)
+bool launch_fixed_k(ClassifyForm &f, const ClassifyParams &p, unsigned grid, hipStream_t st, bool ovc, bool wide, bool packed)
 {
-    return launch_k<31, true>(p, grid, st, ovc, wide, packed) || launch_k<21, false>(p, grid, st, ovc, wide, packed) ||
-           launch_k<25, false>(p, grid, st, ovc, wide, packed) || launch_k<27, false>(p, grid, st, ovc, wide, packed) ||
-           launch_k<32, false>(p, grid, st, ovc, wide, packed);
+    return launch_k<31, true>(f, p, grid, st, ovc, wide, packed) || launch_k<21, false>(f, p, grid, st, ovc, wide, packed) ||
+           launch_k<25, false>(f, p, grid, st, ovc, wide, packed) || launch_k<27, false>(f, p, grid, st, ovc, wide, packed) ||
+           launch_k<32, false>(f, p, grid, st, ovc, wide, packed);
 }
 }  // namespace
 
@@ -342,6 +372,17 @@ int bns_device_count(void)
  * 4: no minimizer window; BNS_ABLATION builds only) make results WRONG; the others select code paths that a small test could
  * not reach otherwise (streamed load, sliced upload, one-rank RCCL broadcast). */
 int bns_debug_set(bns_ctx *ctx, int bits) { if (!ctx) return BNS_ERR_ARG; ctx->dbg = bits; return BNS_OK; }
+/* test aid like bns_debug_set, not part of the public header: which kernels the last classify dispatch of this context launched.
+ * Copies min(n, 18) words to out and returns how many; the words, in order: valid (0 until something was classified) | SPACED,
+ * LAYOUT, KT, NM, SPAN, OVC, WIDE, PACKED of the classify_kernel instantiation | classify_overflow_kernel: launched (0 / 1), its
+ * SPACED, LAYOUT, WIDE, PACKED, the units handed to it, its grid | the units per claim (chunk) and the grid of classify_kernel. */
+int bns_debug_last_classify_form(const bns_ctx *ctx, uint32_t *out, int n)
+{
+    if (!ctx || !out || n < 0) return BNS_ERR_ARG;
+    const int c = std::min<int>(n, ClassifyForm::N_WORDS);
+    for (int i = 0; i < c; ++i) out[i] = ctx->last_form.w[i];
+    return c;
+}
 #ifdef BNS_WAVE_TIMES
 // measurement builds only: (start, end) wall-clock stamps of the 8192 wavefronts of the last classify_kernel launch
 extern "C" int bns_debug_wave_times(bns_ctx *ctx, unsigned long long *out16384)
@@ -1454,21 +1495,26 @@ static int classify_device_impl(bns_ctx *ctx, const char *d_bases, const uint64_
     const bool ovf_heavy = (ctx->dbg & BNS_DBG_OVC_ON) || (!(ctx->dbg & BNS_DBG_OVC_OFF) && ctx->n_ovf_keys * 1000ULL > ctx->n_keys);
     const bool clustered = !ctx->spaced && ctx->layout == BNS_LAYOUT_MINBUCKET;
     bool launched = false;
-    if (clustered) launched = launch_fixed_k(p, grid, st, ovf_heavy, ctx->table_wide, packed);
+    ClassifyForm &form = ctx->last_form;
+    if (clustered) launched = launch_fixed_k(form, p, grid, st, ovf_heavy, ctx->table_wide, packed);
     if (!launched && clustered && ctx->table_wide) {
-        if (packed) hipLaunchKernelGGL((classify_kernel<false, 2, 0, 0, 8, false, true, true>), dim3(grid), dim3(256), 0, st, p);
-        else        hipLaunchKernelGGL((classify_kernel<false, 2, 0, 0, 8, false, true>), dim3(grid), dim3(256), 0, st, p);
+        if (packed) launch_classify<false, 2, 0, 0, 8, false, true, true>(form, p, grid, st);
+        else        launch_classify<false, 2, 0, 0, 8, false, true, false>(form, p, grid, st);
         launched = true;
     }
     if (!launched)
         dispatch_sp_layout(ctx->spaced, ctx->layout, [&](auto sp, auto ly) {
-            auto kern = packed ? classify_kernel<decltype(sp)::value, decltype(ly)::value, 0, 0, 8, false, false, true>
-                               : classify_kernel<decltype(sp)::value, decltype(ly)::value, 0, 0>;
+            constexpr bool SP = decltype(sp)::value;
+            constexpr int LY = decltype(ly)::value;
             // persistent grid = the blocks that are resident at once (a wide probe stage takes more LDS per block than 8 per CU allow)
-            int per_cu = 8;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess || per_cu < 1) per_cu = 8;
-            const unsigned g = std::min<unsigned>(grid, (unsigned)ctx->n_cu * (unsigned)std::min(per_cu, 8));
-            hipLaunchKernelGGL(kern, dim3(g), dim3(256), 0, st, p);
+            auto go = [&](auto pk) {
+                constexpr bool PK = decltype(pk)::value;
+                int per_cu = 8;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, classify_kernel<SP, LY, 0, 0, 8, false, false, PK>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 8;
+                const unsigned g = std::min<unsigned>(grid, (unsigned)ctx->n_cu * (unsigned)std::min(per_cu, 8));
+                launch_classify<SP, LY, 0, 0, 8, false, false, PK>(form, p, g, st);
+            };
+            if (packed) go(std::true_type{}); else go(std::false_type{});
         });
     HIPCHK(ctx, hipGetLastError());
     if (ctx->timing) {
@@ -1484,15 +1530,14 @@ static int classify_device_impl(bns_ctx *ctx, const char *d_bases, const uint64_
         if (h_ovf) {
             if ((rc = ensure(ctx, ctx->scratch, (size_t)total_bases * 16)) != BNS_OK) return rc;
             const dim3 og(std::min<u32>(h_ovf, (u32)ctx->n_cu * 8));
+            u32 *const scr = (u32 *)ctx->scratch.p;
             if (clustered && ctx->table_wide) {
-                if (packed) hipLaunchKernelGGL((classify_overflow_kernel<false, 2, true, true>), og, dim3(64), 0, st, p, (u32 *)ctx->scratch.p, (u64)total_bases);
-                else        hipLaunchKernelGGL((classify_overflow_kernel<false, 2, true>), og, dim3(64), 0, st, p, (u32 *)ctx->scratch.p, (u64)total_bases);
+                if (packed) launch_classify_overflow<false, 2, true, true>(form, p, h_ovf, og.x, st, scr, (u64)total_bases);
+                else        launch_classify_overflow<false, 2, true, false>(form, p, h_ovf, og.x, st, scr, (u64)total_bases);
             } else
             dispatch_sp_layout(ctx->spaced, ctx->layout, [&](auto sp, auto ly) {
-                if (packed) hipLaunchKernelGGL((classify_overflow_kernel<decltype(sp)::value, decltype(ly)::value, false, true>), og, dim3(64), 0, st, p,
-                                               (u32 *)ctx->scratch.p, (u64)total_bases);
-                else        hipLaunchKernelGGL((classify_overflow_kernel<decltype(sp)::value, decltype(ly)::value>), og, dim3(64), 0, st, p,
-                                               (u32 *)ctx->scratch.p, (u64)total_bases);
+                if (packed) launch_classify_overflow<decltype(sp)::value, decltype(ly)::value, false, true>(form, p, h_ovf, og.x, st, scr, (u64)total_bases);
+                else        launch_classify_overflow<decltype(sp)::value, decltype(ly)::value, false, false>(form, p, h_ovf, og.x, st, scr, (u64)total_bases);
             });
             HIPCHK(ctx, hipGetLastError());
         }

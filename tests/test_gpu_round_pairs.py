@@ -9,48 +9,9 @@ import numpy as np
 import pytest
 
 import synth
+from classify_forms import kmer_buckets
 
 pytestmark = pytest.mark.gpu
-
-M32 = 0xFFFFFFFF
-CODE = np.full(256, 255, dtype=np.uint8)
-for _i, _c in enumerate(b"ACGT"):
-    CODE[_c] = _i
-    CODE[_c | 0x20] = _i
-
-
-def kmer_buckets(seq, k, m, n_mb):
-    """Home bucket of every k-mer of seq (None for one with a non-ACGT base): canonical m-mers, 32-bit identity."""
-    codes = CODE[np.frombuffer(seq.tobytes(), dtype=np.uint8)]
-    n = codes.size - k + 1
-    if n <= 0:
-        return []
-    nm = codes.size - m + 1
-    mh = []
-    for i in range(nm):
-        c = codes[i:i + m]
-        if (c == 255).any():
-            mh.append(None)
-            continue
-        fw = 0
-        rc = 0
-        for j, x in enumerate(c):
-            fw = (fw << 2) | int(x)
-            rc |= (3 - int(x)) << (2 * j)
-        x = min(fw, rc)
-        x = (x & M32) ^ (((x >> 32) << 13 | (x >> 32) >> 19) & M32) if m > 16 else x
-        mh.append((x * 0x7FEB352D) & M32)
-    out = []
-    for j in range(n):
-        win = mh[j:j + k - m + 1]
-        if any(h is None for h in win):
-            out.append(None)
-            continue
-        x = (min(win) * 0x9E3779B1) & M32
-        x ^= x >> 15
-        r = int("{:032b}".format(x)[::-1], 2)
-        out.append((r * n_mb) >> 32)
-    return out
 
 
 def pair_runs(b):
@@ -129,7 +90,7 @@ def shaped_reads(w, rng, n_per):
     return reads
 
 
-@pytest.mark.parametrize("k", [31, 21, 27, 32])
+@pytest.mark.parametrize("k", [31, 21, 25, 27, 32])
 @pytest.mark.parametrize("paired", [False, True])
 def test_round_pairs_shapes(gpu_ctx, oracle, k, paired):
     w = world(oracle, k)

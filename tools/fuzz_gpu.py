@@ -26,7 +26,7 @@ prev_cfg = None
 while time.time() - t0 < budget:
     seed = seed0 * 100003 + it
     rng = np.random.default_rng(seed)
-    k = int(rng.choice([9, 13, 19, 20, 21, 27, 28, 31, 31, 31, 32]))
+    k = int(rng.choice([9, 13, 17, 19, 20, 21, 24, 25, 25, 27, 28, 30, 31, 31, 31, 32]))
     canon = bool(rng.random() < 0.8)
     gaps = None
     if rng.random() < 0.2:
@@ -68,16 +68,19 @@ while time.time() - t0 < budget:
     bases, offsets = synth.concat(reads)
     exp = O.classify_batch(w.table, w.tax, k, bases, offsets, paired=paired, gaps=gaps, canon=canon, spaced_intended=True)
     got = ctx.classify(bases, offsets, paired=paired, want_hits=True)
+    form = ctx.last_classify_form()                           # which classify_kernel instantiation that was
     gr = ctx.classify_runs(bases, offsets, paired=paired)
     pw, pbw, pbm = bonsai_amd.pack_reads(bases, offsets, threads=int(rng.integers(1, 4)))
     gp = ctx.classify_packed(pw, pbw, pbm, offsets, paired=paired, want_hits=True)      # the packed entry point: same answers
+    form_packed = ctx.last_classify_form()
     if not all(np.array_equal(a, b) for a, b in zip(gp["hits"], got["hits"])):
-        print("PACKED HITS MISMATCH seed", seed); sys.exit(1)
+        print("PACKED HITS MISMATCH seed", seed, "form", form, "packed form", form_packed); sys.exit(1)
     for key in ("taxon", "missing", "ambig", "n_hits"):
         if not (np.array_equal(got[key], exp[key]) and np.array_equal(gr[key], exp[key]) and np.array_equal(gp[key], exp[key])):
             bad = np.flatnonzero(got[key] != exp[key])
             print("MISMATCH seed", seed, "span", span, "k", k, "canon", canon, "gaps", gaps, "layout", layout, "paired", paired, "len", length, key,
                   "units", bad[:5], "got", got[key][bad[:5]], "exp", exp[key][bad[:5]])
+            print("kernels launched: ASCII", form, "| packed", form_packed, "| table", ctx.table_geometry())
             # is it the configuration or something a previous configuration left behind in the context?
             c2 = bonsai_amd.Context(0)
             c2.set_encoder(k, gaps, canonicalize=canon, spaced_intended=True)
