@@ -99,6 +99,7 @@ def load():
         "bns_packed_words": (C.c_uint64, [C.c_uint64, C.c_uint64]),
         "bns_pack_reads": (C.c_int, [vp, u64p, C.c_uint64, u64p, u64p, u32p, C.c_uint64, u64p, C.c_int]),
         "bns_pack_reads_ptrs": (C.c_int, [vp, u32p, C.c_uint64, u64p, u64p, u64p, u32p, C.c_uint64, u64p, C.c_int]),
+        "bns_pack_reads_qual_ptrs": (C.c_int, [vp, vp, u32p, C.c_uint64, C.c_uint32, u64p, u64p, u64p, u32p, C.c_uint64, u64p, C.c_int]),
         "bns_classify_batch_packed": (C.c_int, [vp, u64p, u64p, u32p, C.c_uint64, u64p, C.c_uint64, C.c_int, u32p, u32p, u32p, u32p, u32p]),
         "bns_classify_batch_packed_runs": (C.c_int, [vp, u64p, u64p, u32p, C.c_uint64, u64p, C.c_uint64, C.c_int, u32p, u32p, u32p, u32p, u64p, u32p,
                                                      C.POINTER(u32p), C.POINTER(u32p), u64p]),
@@ -129,6 +130,7 @@ def load():
         "bns_dev_download": (C.c_int, [vp, vp, vp, C.c_size_t]),
         "bns_dev_sync": (C.c_int, [vp]),
         "bns_classify_text": (C.c_int, [vp, C.POINTER(vp), u64p, C.c_int, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(TextOut), C.POINTER(TextInfo)]),
+        "bns_set_min_base_quality": (C.c_int, [vp, C.c_uint32]),
         "bns_text_prefetch": (C.c_int, [vp, C.POINTER(vp), u64p, C.c_int]),
         "bns_text_finish": (C.c_int, [vp, C.POINTER(TextInfo)]),
         "bns_dev_copy_peer": (C.c_int, [vp, vp, vp, vp, C.c_size_t]),

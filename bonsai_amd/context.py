@@ -46,6 +46,34 @@ def pack_reads(bases, offsets, threads=1):
         cap = int(nb.value)
 
 
+def pack_reads_qual(seqs, quals, min_quality, threads=1):
+    """bns_pack_reads_qual_ptrs (host only): reads (a list of bytes) and their quality strings (bytes of the read's length, or None: a
+    read without quality; quals itself may be None) -> (words, bad_word, bad_mask, offsets): pack_reads' image with every base whose
+    quality byte is below 33 + min_quality flagged like an invalid base, its code bits 0"""
+    L = _lib.load()
+    seqs = [bytes(s) for s in seqs]
+    n = len(seqs)
+    if quals is not None:
+        quals = [None if q is None else bytes(q) for q in quals]
+        if len(quals) != n or any(q is not None and len(q) != len(s) for s, q in zip(seqs, quals)):
+            raise ValueError("pack_reads_qual: one quality string (or None) per read, as long as the read")
+    sp = (C.c_char_p * max(1, n))(*seqs)
+    qp = (C.c_char_p * max(1, n))(*quals) if quals is not None else None
+    lens = np.array([len(s) for s in seqs], dtype=np.uint32)
+    offsets = np.zeros(n + 1, dtype=np.uint64)
+    words = np.zeros(int(L.bns_packed_words(int(lens.sum()), n)), dtype=np.uint64)
+    cap = 1024
+    while True:
+        bw = np.zeros(cap, dtype=np.uint64); bm = np.zeros(cap, dtype=np.uint32); nb = C.c_uint64()
+        rc = L.bns_pack_reads_qual_ptrs(C.cast(sp, vp), C.cast(qp, vp) if qp is not None else None, _p(lens, u32p), n, int(min_quality),
+                                        _p(offsets, u64p), _p(words, u64p), _p(bw, u64p), _p(bm, u32p), cap, C.cast(C.byref(nb), u64p), int(threads))
+        if rc == 0:
+            return words, bw[:nb.value].copy(), bm[:nb.value].copy(), offsets
+        if nb.value <= cap:
+            raise BonsaiAmdError("bns_pack_reads_qual_ptrs: %s" % L.bns_strerror(rc).decode())
+        cap = int(nb.value)
+
+
 def confidence_fraction(threshold):
     """a confidence threshold (int, str, Fraction or float; a float goes through its shortest repr: 0.1 is 1/10) -> (num, den) in
     lowest terms, what bns_set_confidence takes; ValueError outside [0, 1], and when a term does not fit the C ABI's uint64_t"""
@@ -200,6 +228,11 @@ class Context:
         unit's Q probed k-mers (0 when none does); threshold 0 turns it off.  Needs a loaded taxonomy (unless 0)."""
         num, den = confidence_fraction(threshold)
         self._chk(self.L.bns_set_confidence(self.h, num, den), "bns_set_confidence")
+
+    def set_min_base_quality(self, q):
+        """bns_set_min_base_quality: classify_text() treats every base whose Phred+33 quality byte is below 33 + q like an 'N'
+        (q in [0, 93]; 0 turns it off).  FASTA records are untouched."""
+        self._chk(self.L.bns_set_min_base_quality(self.h, int(q)), "bns_set_min_base_quality")
 
     # ---- hot path (host buffers)
     def classify(self, bases, offsets, paired=False, want_hits=False):

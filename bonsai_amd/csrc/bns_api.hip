@@ -353,7 +353,7 @@ bool launch_fixed_k(ClassifyForm &f, const ClassifyParams &p, unsigned grid, hip
 
 extern "C" {
 
-int bns_version(void) { return 107; }
+int bns_version(void) { return 108; }
 
 int bns_device_pci_bus_id(int device, char *out, int cap)
 {

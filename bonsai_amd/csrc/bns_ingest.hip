@@ -38,6 +38,7 @@
 //   offsets_kernel     how many records this call takes (complete ones in front of `limit`; the minimum over a pair of files), then
 //                      sequence lengths -> base offsets, name lengths -> name offsets (look-back)
 //   pack_text_kernel   one wavefront per record: bases gathered from the record's lines -> 2-bit words + invalid-base flags; its name
+//                      (pack_text_minq_kernel behind bns_set_min_base_quality: bases of low quality flagged as well, bns_minqual.hpp)
 // then classify_device_impl on the packed words, hit_runs_kernel when the caller prints runs, and the kernels of bns_lines.hpp when he
 // takes the finished Kraken lines.
 #include <new>
@@ -529,11 +530,20 @@ __global__ __launch_bounds__(256) void offsets_kernel(ParseArgs pa, OffsetsOut o
     }
 }
 
+}  // namespace ingest
+}  // namespace bns
+#include "bns_minqual.hpp"
+namespace bns {
+namespace ingest {
+
 // ---- pack: SUB lanes per record (four records per wavefront), 64 bases a pass (4 per lane), the word layout of pack_kernel; the
 // record's name and position.  (offsets start at the slice's first record, which is record R0 of the batch's packed image: word base
 // (offset >> 5) + index)
 struct PackOut { const u64 *offsets; u32 R0; u64 *words; u32 *nmask; const u32 *name_off; u32 name_base; char *names; u64 *pos64; u32 rel[2]; };
-__global__ __launch_bounds__(256) void pack_text_kernel(ParseArgs pa, PackOut o)
+// MINQ (bns_minqual.hpp): a base whose quality byte is below qthr counts as invalid.  false: the kernel as it was -- nothing of the
+// quality is looked at, and every `if (MINQ)` below folds away.
+template <bool MINQ>
+__device__ __forceinline__ void pack_text_body(const ParseArgs &pa, const PackOut &o, const u32 qthr)
 {
     const u32 sl = threadIdx.x & (SUB - 1u);                    // lane within the record's group
     const CallInfo *ci = pa.ci;
@@ -558,6 +568,8 @@ __global__ __launch_bounds__(256) void pack_text_kernel(ParseArgs pa, PackOut o)
             noff = o.name_off[R];
             if (single == 0xFFFFFFFFu && L) { l0 = a.cand[j] + 1u; l1 = a.c_line1[j]; }
         }
+        minqual::QualCursor qc;
+        if (MINQ && live && L) qc.open(a, ci->s[s], a.c_line1[j], L);
         const u32 n_words = (L + 31u) >> 5;
         // the name (klib/kseq.h:190; trimmed in walk_kernel) and where the record starts in the caller's text
         if (live) {
@@ -572,8 +584,10 @@ __global__ __launch_bounds__(256) void pack_text_kernel(ParseArgs pa, PackOut o)
             const u32 p = ps * 64u;
             const u32 bi = p + sl * 4u;
             u32 w = 0;                                          // up to four bytes of sequence, first base in the low byte
+            u32 qw = 0xFFFFFFFFu;                               // (MINQ) their quality bytes; 0xFF: no quality, never below the threshold
             if (bi < L) {
                 const u32 nb = L - bi < 4u ? L - bi : 4u;
+                if (MINQ) qw = qc.fetch(a, bi, nb);
                 if (single != 0xFFFFFFFFu) {
                     const u32 addr = single + bi, mis = addr & 3u;
                     const u32 *ap = reinterpret_cast<const u32 *>(a.text + (addr - mis));
@@ -599,6 +613,7 @@ __global__ __launch_bounds__(256) void pack_text_kernel(ParseArgs pa, PackOut o)
                 u32 bad;
                 const u32 cd = base_code((w >> (8 * i)) & 0xFFu, bad);
                 if (bi + (u32)i >= L) bad = 1u;
+                if (MINQ && ((qw >> (8 * i)) & 0xFFu) < qthr) bad = 1u;
                 codes = (codes << 2) | (bad ? 0u : cd);
                 bads = (bads << 1) | bad;
             }
@@ -614,6 +629,9 @@ __global__ __launch_bounds__(256) void pack_text_kernel(ParseArgs pa, PackOut o)
         }
     }
 }
+__global__ __launch_bounds__(256) void pack_text_kernel(ParseArgs pa, PackOut o) { pack_text_body<false>(pa, o, 0u); }
+// `bns_set_min_base_quality`: the same with the quality bytes gathered beside the bases
+__global__ __launch_bounds__(256) void pack_text_minq_kernel(ParseArgs pa, PackOut o, u32 qthr) { pack_text_body<true>(pa, o, qthr); }
 
 }  // namespace ingest
 }  // namespace bns
@@ -649,6 +667,7 @@ struct TextWork {                                       // the context's workspa
     CallInfo *h_info = nullptr;                         // page-locked
     unsigned long long *h_cursor = nullptr;             // [0..1]: runs so far behind batch set q; [2]: line bytes so far
     struct TextCall *call = nullptr;                    // the state of the call in progress -- or, behind BNS_TEXT_DEFER, of the one that waits for bns_text_finish
+    u32 min_qual = 0;                                   // bns_set_min_base_quality (0: off)
 };
 
 // One bns_classify_text call: what it has accepted so far, the open batch, the state in front of the last classified batch.
@@ -1013,6 +1032,16 @@ static int start_upload(bns_ctx *ctx, Upload &u, const char *host, u64 bytes)
     return BNS_OK;
 }
 
+int bns_set_min_base_quality(bns_ctx *ctx, uint32_t q)
+{
+    if (!ctx || q > 93u) return BNS_ERR_ARG;
+    // (kept with the text workspace: it is the text calls' setting, and table and taxonomy reloads do not touch it)
+    if (!ctx->text_work) ctx->text_work = new (std::nothrow) bns_text_work();
+    if (!ctx->text_work) return BNS_ERR_NOMEM;
+    ctx->text_work->min_qual = q;
+    return BNS_OK;
+}
+
 int bns_text_prefetch(bns_ctx *ctx, const char *const *text, const uint64_t *text_bytes, int n_streams)
 {
     if (!ctx) return BNS_ERR_ARG;
@@ -1214,6 +1243,7 @@ int bns_classify_text(bns_ctx *ctx, const char *const *text, const uint64_t *tex
     auto flush_batch = [&]() -> int { return text_flush_batch(ctx, tw, tc); };
     const u32 lim = limit >= text_bytes[0] ? 0xFFFFFFFFu : (u32)limit + src[0].rel;
     const unsigned pgrid = (unsigned)ctx->n_cu * 8;
+    const u32 min_qual = tw.min_qual;
     // One round = one parse over [cons, hi) of every stream, hi = what piece k has brought up -- cut to the window one parse may
     // cover (of a pair of files the denser one is ahead of what its mate lets it hand over: its unparsed text waits, it does not grow
     // the window) -- whose records are appended to the open batch.  k moves on with the uploads; when they are all up the rounds go on
@@ -1266,7 +1296,8 @@ int bns_classify_text(bns_ctx *ctx, const char *const *text, const uint64_t *tex
         hipLaunchKernelGGL(walk_kernel, dim3(pgrid, ns), dim3(256), 0, st, pa);
         hipLaunchKernelGGL(compact_kernel, dim3(cgrid, ns), dim3(256), 0, st, pa, lim);
         hipLaunchKernelGGL(offsets_kernel, dim3(ogrid), dim3(256), 0, st, pa, oo);
-        hipLaunchKernelGGL(pack_text_kernel, dim3(pgrid), dim3(256), 0, st, pa, po);
+        if (min_qual) hipLaunchKernelGGL(pack_text_minq_kernel, dim3(pgrid), dim3(256), 0, st, pa, po, 33u + min_qual);
+        else hipLaunchKernelGGL(pack_text_kernel, dim3(pgrid), dim3(256), 0, st, pa, po);
         TXCHK(hipGetLastError());
         if (ctx->timing) TXCHK(hipEventRecord(tw.t1, st));
         TXCHK(hipMemcpyAsync(tw.h_info, d_ci, sizeof(CallInfo), hipMemcpyDeviceToHost, st));

@@ -31,7 +31,7 @@ PackLayout pack_layout(const PackChunkHeader &h)
 }  // namespace
 
 std::pair<u64, u64> pack_dataset(const char *fq1, const char *fq2, const char *out_path, unsigned chunk_bases, unsigned parser_threads, int threads,
-                                 bool with_names)
+                                 bool with_names, unsigned min_qual)
 {
     if (!chunk_bases) chunk_bases = 1u << 27;
     const int fd = ::open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
@@ -74,7 +74,7 @@ std::pair<u64, u64> pack_dataset(const char *fq1, const char *fq2, const char *o
     });
     struct Joiner { std::thread &t; std::mutex &m; std::condition_variable &cv; bool &done; ~Joiner() { { std::lock_guard<std::mutex> lk(m); done = true; } cv.notify_all(); if (t.joinable()) t.join(); } } joiner{writer, wmu, wcv, w_done};
     ChunkSource source(fq1, fq2, chunk_bases, parser_threads, 0);
-    std::vector<const char *> ptrs;
+    std::vector<const char *> ptrs, quals;
     std::vector<u32> lens, bad_mask;
     std::vector<u64> words, offsets, bad_word;
     std::string names;
@@ -86,25 +86,28 @@ std::pair<u64, u64> pack_dataset(const char *fq1, const char *fq2, const char *o
         if (fq2) n -= n & 1u;
         if (!n) { source.recycle(std::move(seqs)); continue; }
         ptrs.resize(n); lens.resize(n); offsets.resize(n + 1);
+        if (min_qual) quals.resize(n);
         u64 total = 0;
         names.clear();
         for (size_t i = 0; i < n; ++i) {
             const bseq1_t &b = seqs->recs[i];
             ptrs[i] = b.seq.data(); lens[i] = (u32)b.seq.size(); total += b.seq.size();
+            if (min_qual) quals[i] = b.qual.size() == b.seq.size() && !b.qual.empty() ? b.qual.data() : nullptr;     // (`pack -Q`; FASTA: none)
             if (with_names) { names.append(b.name.data(), b.name.size()); names.push_back('\0'); }
         }
         const u64 n_words = bns_packed_words(total, n);
         words.resize((size_t)n_words + 1);
         u64 n_bad = 0;
         if (bad_word.size() < 4096) { bad_word.resize(4096); bad_mask.resize(4096); }
-        int rc = bns_pack_reads_ptrs(ptrs.data(), lens.data(), n, offsets.data(), words.data(), bad_word.data(), bad_mask.data(), bad_word.size(), &n_bad,
-                                     std::max(1, threads));
+        const char *const *qp = min_qual ? quals.data() : nullptr;
+        int rc = bns_pack_reads_qual_ptrs(ptrs.data(), qp, lens.data(), n, min_qual, offsets.data(), words.data(), bad_word.data(), bad_mask.data(), bad_word.size(),
+                                          &n_bad, std::max(1, threads));
         if (rc != BNS_OK && n_bad > bad_word.size()) {
             bad_word.resize((size_t)n_bad); bad_mask.resize((size_t)n_bad);
-            rc = bns_pack_reads_ptrs(ptrs.data(), lens.data(), n, offsets.data(), words.data(), bad_word.data(), bad_mask.data(), bad_word.size(), &n_bad,
-                                     std::max(1, threads));
+            rc = bns_pack_reads_qual_ptrs(ptrs.data(), qp, lens.data(), n, min_qual, offsets.data(), words.data(), bad_word.data(), bad_mask.data(), bad_word.size(),
+                                          &n_bad, std::max(1, threads));
         }
-        if (rc != BNS_OK) die("bns_pack_reads_ptrs failed");
+        if (rc != BNS_OK) die("bns_pack_reads_qual_ptrs failed");
         PackChunkHeader h{};
         h.magic = PACK_CHUNK_MAGIC; h.n_reads = (u32)n; h.total_bases = total; h.n_words = n_words; h.n_bad = n_bad; h.names_bytes = names.size();
         const PackLayout L = pack_layout(h);
@@ -253,6 +256,7 @@ void process_dataset(ClassifierGeneric &c, const char *fq1, const char *fq2, std
     if (packed_in) {
         if (fq2) die("a read container holds both mates of a pair: give the one file");
         if (c.get_emit_fastq()) die("FASTQ-style output needs bases and qualities, which a read container does not hold (classify the FASTQ itself, or use -F)");
+        if (c.min_qual_) die("-Q needs base qualities, which a read container does not hold (classify the FASTQ itself, or mask while packing: bonsai pack -Q)");
         pfd = ::open(fq1, O_RDONLY);
         if (pfd < 0) die(std::string("Could not open ") + fq1 + " for reading.");
         PackFileHeader fh;

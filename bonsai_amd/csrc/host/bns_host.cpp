@@ -425,6 +425,12 @@ void set_confidence(ClassifierGeneric &c, u64 num, u64 den)
     for (bns_ctx *cx : c.ctxs_) chk(cx, bns_set_confidence(cx, num, den), "bns_set_confidence");
 }
 
+void set_min_base_quality(ClassifierGeneric &c, unsigned q)
+{
+    for (bns_ctx *cx : c.ctxs_) chk(cx, bns_set_min_base_quality(cx, q), "bns_set_min_base_quality");
+    c.min_qual_ = q;                                           // (pack_chunk: the host packer follows the same rule)
+}
+
 ClassifierGeneric::~ClassifierGeneric()
 {
     work_.res.release(); work_.first.release();              // (page-locked memory goes back while the contexts still exist)
@@ -570,19 +576,24 @@ void pack_chunk(ClassifierGeneric &c, bns_ctx *ctx, const bseq1_t *bs, unsigned 
     ptrs.resize(n); lens.resize(n);
     u64 total = 0;
     for (unsigned i = 0; i < n; ++i) { ptrs[i] = bs[i].seq.data(); lens[i] = (u32)bs[i].seq.size(); total += bs[i].seq.size(); }
+    // `-Q`: the records' qualities beside them (a FASTA record has none; a record the reader accepted has one as long as its sequence)
+    const unsigned min_qual = c.min_qual_;
+    std::vector<const char *> &quals = r.qual_ptrs;
+    if (min_qual) { quals.resize(n); for (unsigned i = 0; i < n; ++i) quals[i] = bs[i].qual.size() == bs[i].seq.size() && !bs[i].qual.empty() ? bs[i].qual.data() : nullptr; }
+    const char *const *qp = min_qual ? quals.data() : nullptr;
     const u64 n_words = bns_packed_words(total, n);
     u64 *words = reinterpret_cast<u64 *>(r.words.reserve(ctx, (size_t)n_words * 8 + 8));
     u64 n_bad = 0;
     if (r.bad_word.size() < 4096) { r.bad_word.resize(4096); r.bad_mask.resize(4096); }
     const double t_p0 = tnow();
-    int rc = bns_pack_reads_ptrs(ptrs.data(), lens.data(), n, r.offsets.data(), words, r.bad_word.data(), r.bad_mask.data(), r.bad_word.size(), &n_bad,
-                                 (int)std::max(1u, copy_threads));
+    int rc = bns_pack_reads_qual_ptrs(ptrs.data(), qp, lens.data(), n, min_qual, r.offsets.data(), words, r.bad_word.data(), r.bad_mask.data(), r.bad_word.size(),
+                                      &n_bad, (int)std::max(1u, copy_threads));
     if (rc != BNS_OK && n_bad > r.bad_word.size()) {           // more words with an invalid base than there was room for: once more
         r.bad_word.resize((size_t)n_bad); r.bad_mask.resize((size_t)n_bad);
-        rc = bns_pack_reads_ptrs(ptrs.data(), lens.data(), n, r.offsets.data(), words, r.bad_word.data(), r.bad_mask.data(), r.bad_word.size(), &n_bad,
-                                 (int)std::max(1u, copy_threads));
+        rc = bns_pack_reads_qual_ptrs(ptrs.data(), qp, lens.data(), n, min_qual, r.offsets.data(), words, r.bad_word.data(), r.bad_mask.data(), r.bad_word.size(),
+                                      &n_bad, (int)std::max(1u, copy_threads));
     }
-    chk(ctx, rc, "bns_pack_reads_ptrs");
+    chk(ctx, rc, "bns_pack_reads_qual_ptrs");
     r.n_bad = n_bad;
     r.t_pack = tnow() - t_p0;
 }

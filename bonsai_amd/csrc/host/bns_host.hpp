@@ -261,6 +261,7 @@ struct ChunkResult {
     std::vector<const char *> seq_ptrs;
     std::vector<u32> seq_lens, bad_mask;
     std::vector<u64> bad_word;
+    std::vector<const char *> qual_ptrs;           // (`-Q`) the records' quality strings, nullptr where a record has none
     double t_pack = 0, t_call = 0, t_copy = 0;     // stage seconds of this chunk's GPU call (BNS_CLI_TIMING)
 };
 
@@ -309,6 +310,7 @@ struct ClassifierGeneric {
     int get_emit_fastq() const { return output_flag_ & FASTQ; }
     std::FILE *taxon_out_ = nullptr;         // `bonsai classify -b`: the taxon of every unit, in input order, as raw little-endian u32
     std::FILE *report_out_ = nullptr;        // `bonsai classify -R`: the taxon report, written by write_report after the last unit
+    unsigned min_qual_ = 0;                  // `bonsai classify -Q`: set_min_base_quality (0: off)
     bool nseq_printed_ = false;              // process_dataset's "nseq:" line on stderr has been printed (by the device text path or the host one)
     u64 n_classified() const { return classified_[0]; }
     u64 n_unclassified() const { return classified_[1]; }
@@ -317,6 +319,9 @@ using Classifier = ClassifierGeneric;
 
 // `bonsai classify -t`: the confidence threshold num / den on every context of the classifier (bns_set_confidence), before the first unit
 void set_confidence(ClassifierGeneric &c, u64 num, u64 den);
+// `bonsai classify -Q`: a base whose Phred+33 quality is below q counts as 'N', on every context of the classifier
+// (bns_set_min_base_quality: the text the device parses) and in pack_chunk (the records the host parser yields), before the first unit
+void set_min_base_quality(ClassifierGeneric &c, unsigned q);
 // `bonsai classify -R`: a tally on every context of the classifier (bns_tally_enable), before the first unit ...
 void enable_tally(ClassifierGeneric &c);
 // ... and, after the last, the tallies summed over the contexts and the report written to c.report_out_ (names_dmp may be nullptr)
@@ -389,8 +394,9 @@ struct PackChunkHeader { u32 magic, n_reads; u64 total_bases, n_words, n_bad, na
 static_assert(sizeof(PackFileHeader) == 32 && sizeof(PackChunkHeader) == 64, "container headers are fixed-size");
 bool is_pack_container(const char *path);
 // reads -> container; chunk_bases = bases per chunk (0: 2^27: a chunk is one GPU call); returns (reads, bases) written
+// min_qual (`bonsai pack -Q`): bases of lower quality are flagged like 'N' in the container (which holds no qualities)
 std::pair<u64, u64> pack_dataset(const char *fq1, const char *fq2, const char *out_path, unsigned chunk_bases, unsigned parser_threads, int threads,
-                                 bool with_names = true);
+                                 bool with_names = true, unsigned min_qual = 0);
 
 // ---- db construction -------------------------------------------------------------------------
 // build_name_hash (util.h:693-722): "name<TAB>taxid" per line, later lines win

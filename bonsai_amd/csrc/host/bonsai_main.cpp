@@ -45,6 +45,8 @@ void usage(const char *exe)
                  "-n:\tnames.dmp for the report's names (scientific names; without it a taxon is named by its id).\n"
                  "-t:\tConfidence threshold in [0, 1] (digits, at most 9 after the point) [0]: a read (pair) is called at the first of its\n"
                  "\ttaxon and the taxon's ancestors whose clade holds at least that fraction of its k-mers, else unclassified.\n"
+                 "-Q:\tMinimum base quality, an integer in [0, 93] [0: off]: a base whose Phred+33 quality is lower counts as N, so no k-mer\n"
+                 "\tover it is looked up (FASTQ records; FASTA has no quality).  Not for a read container: mask with `bonsai pack -Q`.\n"
                  "<inr1.fq> may be a read container written by `bonsai pack` (2-bit reads + names): no parsing, no packing.\n",
                  exe, 1 << 24);
     std::exit(EXIT_FAILURE);
@@ -64,6 +66,17 @@ bool parse_confidence(const char *s, unsigned long long &num, unsigned long long
     return num <= den;
 }
 
+// `-Q`: an integer in [0, 93], digits only
+bool parse_min_quality(const char *s, unsigned &q)
+{
+    unsigned v = 0;
+    int n = 0;
+    for (; *s >= '0' && *s <= '9'; ++s, ++n) { v = v * 10 + (unsigned)(*s - '0'); if (v > 93) return false; }
+    if (*s || !n) return false;
+    q = v;
+    return true;
+}
+
 int classify_main(int argc, char *argv[])
 {
     int co, num_threads = std::min(4, bns::usable_cpus()), emit_kraken = 1, emit_fastq = 0, emit_all = 0, chunk_size = 1 << 24;
@@ -76,8 +89,9 @@ int classify_main(int argc, char *argv[])
     std::FILE *ofp = stdout, *taxon_fp = nullptr, *report_fp = nullptr;
     const char *names_path = nullptr;
     unsigned long long conf_num = 0, conf_den = 1;
+    unsigned min_qual = 0;
     if (argc < 4) usage(argv[0]);
-    while ((co = getopt(argc, argv, "Cc:p:o:S:afFkKg:L:NP:b:R:n:t:h?")) >= 0) {
+    while ((co = getopt(argc, argv, "Cc:p:o:S:afFkKg:L:NP:b:R:n:t:Q:h?")) >= 0) {
         switch (co) {
             case 'h': case '?': usage(argv[0]); break;
             case 'C': canonicalize = false; break;
@@ -95,6 +109,12 @@ int classify_main(int argc, char *argv[])
             case 't':
                 if (!parse_confidence(optarg, conf_num, conf_den)) {
                     std::fprintf(stderr, "[E] -t: the confidence threshold must be a decimal in [0, 1] with at most 9 digits after the point, not '%s'\n", optarg);
+                    return EXIT_FAILURE;
+                }
+                break;
+            case 'Q':
+                if (!parse_min_quality(optarg, min_qual)) {
+                    std::fprintf(stderr, "[E] -Q: the minimum base quality must be an integer in [0, 93], not '%s'\n", optarg);
                     return EXIT_FAILURE;
                 }
                 break;
@@ -169,6 +189,7 @@ int classify_main(int argc, char *argv[])
         c.taxon_out_ = taxon_fp;
         c.report_out_ = report_fp;
         if (conf_num) bns::set_confidence(c, conf_num, conf_den);
+        if (min_qual) bns::set_min_base_quality(c, min_qual);
         if (report_fp) bns::enable_tally(c);
         if (devs.size() > 1) {                                   // which collective library replicated the db over how many devices
             // (one line per device: a multi-GPU record says what it ran on)
@@ -233,27 +254,35 @@ int pack_main(int argc, char *argv[])
     int co, threads = std::min(8, bns::usable_cpus());
     unsigned parser_threads = 2, chunk = 0;
     bool names = true;
+    unsigned min_qual = 0;
     std::string out;
-    while ((co = getopt(argc, argv, "o:c:p:P:nh?")) >= 0) {
+    while ((co = getopt(argc, argv, "o:c:p:P:nQ:h?")) >= 0) {
         switch (co) {
             case 'o': out = optarg; break;
             case 'c': chunk = (unsigned)std::strtoul(optarg, nullptr, 10); break;
             case 'p': threads = std::atoi(optarg); if (threads < 1) threads = bns::usable_cpus(); break;
             case 'P': parser_threads = (unsigned)std::max(1, std::atoi(optarg)); break;
             case 'n': names = false; break;
+            case 'Q':
+                if (!parse_min_quality(optarg, min_qual)) {
+                    std::fprintf(stderr, "[E] -Q: the minimum base quality must be an integer in [0, 93], not '%s'\n", optarg);
+                    return EXIT_FAILURE;
+                }
+                break;
             default:
-                std::fprintf(stderr, "Usage: %s pack [-o out.bnsp] [-c bases per chunk (2^27)] [-p pack threads] [-P parser threads] [-n: no read names] <in1.fq> [<in2.fq>]\n", argv[0]);
+                std::fprintf(stderr, "Usage: %s pack [-o out.bnsp] [-c bases per chunk (2^27)] [-p pack threads] [-P parser threads] [-n: no read names] "
+                                     "[-Q minimum base quality: lower bases packed as N] <in1.fq> [<in2.fq>]\n", argv[0]);
                 return EXIT_FAILURE;
         }
     }
     const int npos = argc - optind;
     if ((npos != 1 && npos != 2) || out.empty()) {
-        std::fprintf(stderr, "Usage: %s pack -o out.bnsp [-c bases per chunk] [-p threads] [-P parser threads] [-n] <in1.fq> [<in2.fq>]\n", argv[0]);
+        std::fprintf(stderr, "Usage: %s pack -o out.bnsp [-c bases per chunk] [-p threads] [-P parser threads] [-n] [-Q min quality] <in1.fq> [<in2.fq>]\n", argv[0]);
         return EXIT_FAILURE;
     }
     try {
         const auto t0 = std::chrono::steady_clock::now();
-        const auto r = bns::pack_dataset(argv[optind], npos == 2 ? argv[optind + 1] : nullptr, out.c_str(), chunk, parser_threads, threads, names);
+        const auto r = bns::pack_dataset(argv[optind], npos == 2 ? argv[optind + 1] : nullptr, out.c_str(), chunk, parser_threads, threads, names, min_qual);
         std::fprintf(stderr, "Packed %llu reads, %llu bases in %.2f s\n", (unsigned long long)r.first, (unsigned long long)r.second,
                      std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     } catch (const std::exception &e) {

@@ -250,6 +250,13 @@ int bns_pack_reads(const char *bases, const uint64_t *offsets, uint64_t n_reads,
                    uint32_t *bad_mask, uint64_t bad_cap, uint64_t *n_bad, int threads);
 int bns_pack_reads_ptrs(const char *const *seqs, const uint32_t *lens, uint64_t n_reads, uint64_t *offsets, uint64_t *words,
                         uint64_t *bad_word, uint32_t *bad_mask, uint64_t bad_cap, uint64_t *n_bad, int threads);
+/* (version 108) bns_pack_reads_ptrs with a quality string per read: quals[r] has lens[r] bytes, or is NULL (a read without quality;
+ * quals itself may be NULL).  A base whose quality byte is below 33 + min_quality (unsigned; min_quality in [0, 93], else BNS_ERR_ARG) is
+ * flagged like an invalid base and its code bits are 0 -- the image bns_pack_reads_ptrs makes of the same reads with 'N' in those places.
+ * min_quality = 0: bns_pack_reads_ptrs. */
+int bns_pack_reads_qual_ptrs(const char *const *seqs, const char *const *quals, const uint32_t *lens, uint64_t n_reads, uint32_t min_quality,
+                             uint64_t *offsets, uint64_t *words, uint64_t *bad_word, uint32_t *bad_mask, uint64_t bad_cap, uint64_t *n_bad,
+                             int threads);
 int bns_classify_batch_packed(bns_ctx *ctx, const uint64_t *words, const uint64_t *bad_word, const uint32_t *bad_mask, uint64_t n_bad,
                               const uint64_t *offsets, uint64_t n_reads, int paired,
                               uint32_t *taxon, uint32_t *missing, uint32_t *ambig, uint32_t *n_hits, uint32_t *hits);
@@ -482,6 +489,18 @@ int bns_text_prefetch(bns_ctx *ctx, const char *const *text, const uint64_t *tex
  * first half reported: the caller's run arrays were too small -- call bns_classify_text again on the same text with larger ones (the records
  * and consumed[] will be the same).  Replaces nothing in the reference: its classify_seqs (classifier.h:269-287) returns when a chunk is done. */
 int bns_text_finish(bns_ctx *ctx, bns_text_info *info);
+/* ---- minimum base quality (what `bonsai classify -Q` sets; version 108) ---------------------------------------------------------
+ * No reference counterpart: Kraken 2's --minimum-base-quality, as defined in DESIGN.md.  q in [0, 93], Phred+33.  For a record that has
+ * quality (kseq_read returned a quality string: a '+' line), base i of the sequence is MASKED when byte i of the quality string -- both as
+ * kseq_read yields them -- is below 33 + q, unsigned.  A masked base is an invalid base: its flag is set and its code bits are 0 in the
+ * packed image, so every k-mer over it is skipped like one over an 'N'; missing, ambig, the hits, runs, lines, the tally and the
+ * confidence walk follow from the image.  FASTA records are untouched.  Only flags change: seq_len, names, rec_pos, consumed[], status and
+ * why are those of the same call with q = 0.  bns_classify_text applies it while it packs (pack_text_minq_kernel: the quality bytes are
+ * gathered beside the bases from text that lies in HBM already), so behind BNS_TEXT_DEFER it is the first half's setting that counts;
+ * out->words / out->nmask hold the masked image.  Per context; table and taxonomy reloads keep it.  q > 93: BNS_ERR_ARG.  q = 0 turns it
+ * off (the default): nothing is launched, allocated or read that was not before.  bns_classify_batch* take no quality: a caller that holds
+ * one masks with bns_pack_reads_qual_ptrs. */
+int bns_set_min_base_quality(bns_ctx *ctx, uint32_t q);
 /* device -> device copy on the context's stream (a caller that keeps text in HBM moves the unconsumed tail in front of the next batch) */
 int bns_dev_copy(bns_ctx *ctx, void *dst, const void *src, size_t bytes);
 /* ... and between two contexts, src in src_ctx's device memory, dst in dst_ctx's (one device or two: the unconsumed tail of a block that
