@@ -229,6 +229,21 @@ class Context:
         num, den = confidence_fraction(threshold)
         self._chk(self.L.bns_set_confidence(self.h, num, den), "bns_set_confidence")
 
+    def sketch_enable(self, max_taxa=65536):
+        """bns_sketch_enable: a HyperLogLog sketch (4096 one-byte registers) of the distinct k-mers every classify call looks up, per
+        taxon bin, for up to max_taxa bins; 0 frees them and turns it off.  Needs a loaded taxonomy (unless 0)."""
+        self._chk(self.L.bns_sketch_enable(self.h, int(max_taxa)), "bns_sketch_enable")
+
+    def sketch(self, reset=False):
+        """bns_sketch_read -> (bins uint32[s] ascending, registers uint8[s, 4096], n_dropped_bins)"""
+        s = C.c_uint32(); dropped = C.c_uint32()
+        self._chk(self.L.bns_sketch_read(self.h, None, None, 0, C.byref(s), C.byref(dropped), 0), "bns_sketch_read")
+        bins = np.zeros(s.value, dtype=np.uint32)
+        regs = np.zeros((s.value, 4096), dtype=np.uint8)
+        self._chk(self.L.bns_sketch_read(self.h, _p(bins, u32p), regs.ctypes.data_as(C.c_void_p), s.value, C.byref(s), C.byref(dropped),
+                                         int(bool(reset))), "bns_sketch_read")
+        return bins, regs, int(dropped.value)
+
     def set_min_base_quality(self, q):
         """bns_set_min_base_quality: classify_text() treats every base whose Phred+33 quality byte is below 33 + q like an 'N'
         (q in [0, 93]; 0 turns it off).  FASTA records are untouched."""

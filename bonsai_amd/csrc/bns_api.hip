@@ -4,6 +4,7 @@
 #include "bns_kernels.hip"
 #include "bns_tally.hpp"
 #include "bns_confidence.hpp"
+#include "bns_sketch.hpp"
 
 #include <dlfcn.h>
 #if defined(__x86_64__)
@@ -136,6 +137,10 @@ struct bns_ctx {
     // bns_set_confidence: theta = conf_num / conf_den (0: off); conf_hits: the hit stream of a launch whose caller wants none
     u64 conf_num = 0, conf_den = 1;
     DevBuf conf_hits;
+    // bns_sketch_enable: one HyperLogLog sketch per bin a sample touches (bns_sketch.hpp); sketch_cap = max_taxa, 0: off.  While it is on
+    // the hit stream of a launch whose caller wants none goes to conf_hits as well
+    u32 sketch_cap = 0;
+    DevBuf sk_regs, sk_slot_of, sk_slot_bin, sk_seen, sk_state;
     // workspace (grow-only)
     DevBuf words, nmask, ovf_list, scratch, small, records;      // small: ovf_count + misc counters
     DevBuf st_bases, st_offsets, st_out[4], st_hits, st_kmers, st_aux, st_runs[4], st_words, st_nmask, st_bad;   // st_words..: packed host batches   // st_runs: run_start, n_runs, run_tax, run_len
@@ -486,7 +491,8 @@ void bns_destroy(bns_ctx *ctx)
     DevBuf *bufs[] = {&ctx->words, &ctx->nmask, &ctx->ovf_list, &ctx->scratch, &ctx->small, &ctx->records, &ctx->st_bases, &ctx->st_offsets,
                       &ctx->st_out[0], &ctx->st_out[1], &ctx->st_out[2], &ctx->st_out[3], &ctx->st_hits, &ctx->st_kmers, &ctx->st_aux,
                       &ctx->st_runs[0], &ctx->st_runs[1], &ctx->st_runs[2], &ctx->st_runs[3], &ctx->st_words, &ctx->st_nmask, &ctx->st_bad,
-                      &ctx->tally_direct, &ctx->tally_clade, &ctx->tally_scan, &ctx->conf_hits};
+                      &ctx->tally_direct, &ctx->tally_clade, &ctx->tally_scan, &ctx->conf_hits,
+                      &ctx->sk_regs, &ctx->sk_slot_of, &ctx->sk_slot_bin, &ctx->sk_seen, &ctx->sk_state};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->peer_stage) (void)hipHostFree(ctx->peer_stage);
     if (ctx->h_run_tax) (void)hipHostFree(ctx->h_run_tax);
@@ -1264,6 +1270,57 @@ int tally_units(bns_ctx *ctx, const u32 *d_taxon, u64 n_units, hipStream_t st, b
     HIPCHK(ctx, hipGetLastError());
     return BNS_OK;
 }
+// registers, seen and slots of the context's sketches allocated for the loaded taxonomy (kept when large enough) and zeroed
+int sketch_zero(bns_ctx *ctx)
+{
+    const size_t n_bins = (size_t)ctx->n_nodes + 1;
+    int rc;
+    if ((rc = ensure(ctx, ctx->sk_regs, (size_t)ctx->sketch_cap * SKETCH_M)) != BNS_OK) return rc;
+    if ((rc = ensure(ctx, ctx->sk_slot_bin, (size_t)ctx->sketch_cap * 4)) != BNS_OK) return rc;
+    if ((rc = ensure(ctx, ctx->sk_slot_of, n_bins * 4)) != BNS_OK) return rc;
+    if ((rc = ensure(ctx, ctx->sk_seen, n_bins)) != BNS_OK) return rc;
+    if ((rc = ensure(ctx, ctx->sk_state, SKETCH_ST_WORDS * 4)) != BNS_OK) return rc;
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemsetAsync(ctx->sk_regs.p, 0, (size_t)ctx->sketch_cap * SKETCH_M, st));
+    HIPCHK(ctx, hipMemsetAsync(ctx->sk_slot_of.p, 0xFF, n_bins * 4, st));           // SKETCH_NO_SLOT
+    HIPCHK(ctx, hipMemsetAsync(ctx->sk_seen.p, 0, n_bins, st));
+    HIPCHK(ctx, hipMemsetAsync(ctx->sk_state.p, 0, SKETCH_ST_WORDS * 4, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return BNS_OK;
+}
+
+// the k-mers of one classify launch into the sketches, on the launch's stream behind it.  p: the launch's parameters (offsets, units,
+// mates, hit stream, records; packed input: its words and flags); ASCII input is packed first, as bns_encode_batch_device does.
+int sketch_units(bns_ctx *ctx, ClassifyParams p, const char *d_bases, u64 n_reads, u64 total_bases, hipStream_t st)
+{
+    const u32 n_bins = ctx->n_nodes + 1u;
+    hipLaunchKernelGGL(sketch_seen_kernel, dim3(grid_for(ctx, p.n_units, 4)), dim3(256), 0, st, (const u32 *)p.hits, p.offsets, (u32)p.nmates,
+                       (const uint4 *)p.records, (u64)p.n_units, (const TaxNode *)ctx->nodes, ctx->n_nodes, (u8 *)ctx->sk_seen.p);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(sketch_assign_kernel, dim3(1), dim3(SKETCH_SCAN_BLOCK), 0, st, (const u8 *)ctx->sk_seen.p, (u32 *)ctx->sk_slot_of.p,
+                       (u32 *)ctx->sk_slot_bin.p, n_bins, ctx->sketch_cap, (u32 *)ctx->sk_state.p);
+    HIPCHK(ctx, hipGetLastError());
+    if (d_bases) {
+        const int rc = pack_reads(ctx, d_bases, p.offsets, n_reads, total_bases, st);
+        if (rc != BNS_OK) return rc;
+        p.words = (const u64 *)ctx->words.p; p.nmask = (const u32 *)ctx->nmask.p;
+    }
+    const unsigned grid = grid_for(ctx, p.n_units, 4);
+    const u32 *slot_of = (const u32 *)ctx->sk_slot_of.p;
+    u8 *regs = (u8 *)ctx->sk_regs.p;
+    const bool whole_key = ctx->table_canon && ctx->table_shift == 0 && ctx->table_len == ctx->table_k;    // (bns_probe_device's dispatch)
+    dispatch_sp_layout(ctx->spaced, ctx->layout, [&](auto sp, auto ly) {
+        constexpr bool SP = decltype(sp)::value;
+        constexpr int LY = decltype(ly)::value;
+        if constexpr (LY == 2) {
+            if (!whole_key)           hipLaunchKernelGGL((sketch_kernel<SP, 2, 1>), dim3(grid), dim3(256), 0, st, p, slot_of, regs);
+            else if (ctx->table_wide) hipLaunchKernelGGL((sketch_kernel<SP, 2, 2>), dim3(grid), dim3(256), 0, st, p, slot_of, regs);
+            else                      hipLaunchKernelGGL((sketch_kernel<SP, 2, 0>), dim3(grid), dim3(256), 0, st, p, slot_of, regs);
+        } else hipLaunchKernelGGL((sketch_kernel<SP, LY, 0>), dim3(grid), dim3(256), 0, st, p, slot_of, regs);
+    });
+    HIPCHK(ctx, hipGetLastError());
+    return BNS_OK;
+}
 }  // namespace
 extern "C" {
 
@@ -1323,13 +1380,77 @@ int bns_set_confidence(bns_ctx *ctx, uint64_t num, uint64_t den)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (num == 0) {
         if (ctx->conf_num) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        release(ctx->conf_hits);
+        if (!ctx->sketch_cap) release(ctx->conf_hits);  // (shared with the sketch pass)
         ctx->conf_num = 0; ctx->conf_den = 1;
         return BNS_OK;
     }
     if (!ctx->nodes) return fail(ctx, BNS_ERR_STATE, "no taxonomy loaded (bns_load_taxonomy)");
     const u64 g = std::gcd(num, den);                // (the same theta; small terms keep the device's exact ceil on its short path)
     ctx->conf_num = num / g; ctx->conf_den = den / g;
+    return BNS_OK;
+}
+
+int bns_sketch_enable(bns_ctx *ctx, uint32_t max_taxa)
+{
+    if (!ctx) return BNS_ERR_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (max_taxa == 0) {
+        if (ctx->sketch_cap) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        release(ctx->sk_regs); release(ctx->sk_slot_of); release(ctx->sk_slot_bin); release(ctx->sk_seen); release(ctx->sk_state);
+        if (!ctx->conf_num) release(ctx->conf_hits);
+        ctx->sketch_cap = 0;
+        return BNS_OK;
+    }
+    if (!ctx->nodes) return fail(ctx, BNS_ERR_STATE, "no taxonomy loaded (bns_load_taxonomy)");
+    if (max_taxa > (1u << 20)) return fail(ctx, BNS_ERR_ARG, "max_taxa > 2^20 (4 GiB of sketches)");
+    if (ctx->sketch_cap) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->sketch_cap = max_taxa;
+    const int rc = sketch_zero(ctx);
+    if (rc != BNS_OK) {                                  // (no room: off, with nothing held)
+        const std::string why = ctx->err;
+        (void)bns_sketch_enable(ctx, 0);
+        ctx->err = why;
+    }
+    return rc;
+}
+
+int bns_sketch_read(bns_ctx *ctx, uint32_t *bins, uint8_t *registers, uint32_t cap, uint32_t *n_sketched, uint32_t *n_dropped_bins, int reset)
+{
+    if (!ctx) return BNS_ERR_ARG;
+    if (!ctx->sketch_cap) return fail(ctx, BNS_ERR_STATE, "sketches not enabled (bns_sketch_enable)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    u32 state[SKETCH_ST_WORDS] = {0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(state, ctx->sk_state.p, sizeof(state), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const u32 s = state[SKETCH_ST_USED];
+    if (n_sketched) *n_sketched = s;
+    if (n_dropped_bins) *n_dropped_bins = state[SKETCH_ST_DROPPED];
+    if ((bins || registers) && cap < s) return fail(ctx, BNS_ERR_ARG, "cap is smaller than the number of sketched bins");
+    if ((bins || registers) && s) {
+        // slots were given launch by launch, ascending inside a launch only: the caller gets them in ascending bin order
+        std::vector<u32> slot_bin(s), order(s);
+        HIPCHK(ctx, hipMemcpyAsync(slot_bin.data(), ctx->sk_slot_bin.p, (size_t)s * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        std::iota(order.begin(), order.end(), 0u);
+        std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return slot_bin[a] < slot_bin[b]; });
+        if (bins) for (u32 i = 0; i < s; ++i) bins[i] = slot_bin[order[i]];
+        if (registers) {
+            // runs of slots that are already in order come back in one copy each (one launch: one run)
+            for (u32 i = 0; i < s;) {
+                u32 j = i + 1;
+                while (j < s && order[j] == order[j - 1] + 1u) ++j;
+                HIPCHK(ctx, hipMemcpyAsync(registers + (size_t)i * SKETCH_M, (const u8 *)ctx->sk_regs.p + (size_t)order[i] * SKETCH_M,
+                                           (size_t)(j - i) * SKETCH_M, hipMemcpyDeviceToHost, st));
+                i = j;
+            }
+            HIPCHK(ctx, hipStreamSynchronize(st));
+        }
+    }
+    if (reset) {
+        const int rc = sketch_zero(ctx);
+        if (rc != BNS_OK) return rc;
+    }
     return BNS_OK;
 }
 
@@ -1395,7 +1516,11 @@ int bns_load_taxonomy(bns_ctx *ctx, const uint32_t *parent, uint32_t n)
     HIPCHK(ctx, hipMemcpy(d, nodes.data(), (size_t)n * sizeof(TaxNode), hipMemcpyHostToDevice));
     if (ctx->nodes) (void)hipFree(ctx->nodes);
     ctx->nodes = d; ctx->n_nodes = n; ctx->tax_clock = clock;
-    return ctx->tally_on ? tally_zero(ctx) : BNS_OK;      // a new taxonomy, new bins: the tally starts again
+    if (ctx->sketch_cap) {                                // a new taxonomy, new bins: sketches and tally start again
+        const int rc = sketch_zero(ctx);
+        if (rc != BNS_OK) return rc;
+    }
+    return ctx->tally_on ? tally_zero(ctx) : BNS_OK;
 }
 
 int bns_set_timing(bns_ctx *ctx, int enabled)
@@ -1469,7 +1594,7 @@ static int classify_device_impl(bns_ctx *ctx, const char *d_bases, const uint64_
     p.offsets = d_offsets; p.n_units = n_units; p.nmates = nm; p.bases = (const u8 *)d_bases;
     if (packed) { p.words = (const u64 *)d_words; p.nmask = (const u32 *)d_nmask; }
     p.taxon = d_taxon; p.missing = d_missing; p.ambig = d_ambig; p.n_hits = d_n_hits; p.hits = d_hits;
-    if (ctx->conf_num && !d_hits) {                  // the confidence pass reads the hit stream: into a buffer of ours when the caller takes none
+    if ((ctx->conf_num || ctx->sketch_cap) && !d_hits) {   // the confidence and sketch passes read the hit stream: into a buffer of ours when the caller takes none
         if ((rc = ensure(ctx, ctx->conf_hits, (size_t)total_bases * 4 + 4)) != BNS_OK) return rc;
         p.hits = (u32 *)ctx->conf_hits.p;
     }
@@ -1551,7 +1676,8 @@ static int classify_device_impl(bns_ctx *ctx, const char *d_bases, const uint64_
     hipLaunchKernelGGL(unpack_kernel, dim3(grid_for(ctx, n_units, 256)), dim3(256), 0, st, (const uint4 *)ctx->records.p, (u64)n_units,
                        d_taxon, d_missing, d_ambig, d_n_hits);
     HIPCHK(ctx, hipGetLastError());
-    return tally_units(ctx, d_taxon, n_units, st);       // (every classifying entry point comes through here, once per unit)
+    if ((rc = tally_units(ctx, d_taxon, n_units, st)) != BNS_OK || !ctx->sketch_cap) return rc;   // (every classifying entry point comes through here, once per unit)
+    return sketch_units(ctx, p, d_bases, n_reads, total_bases, st);
 }
 
 int bns_classify_batch_device(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_reads,

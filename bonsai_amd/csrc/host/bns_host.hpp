@@ -95,6 +95,17 @@ std::unordered_map<u32, std::string> read_scientific_names(const char *names_dmp
 // coded ancestor followed by the steps from it (a strain under a species: S1), "-" when no ancestor has one.
 std::string format_report(const u64 *direct, const u64 *clade, u32 n, const u32 *parent, const std::vector<std::string> &ranks,
                           const std::unordered_map<u32, std::string> &names);
+// The distinct k-mer column of `bonsai classify -R -u` (HyperLogLog, p = 12; definition in DESIGN "Defined behaviour").
+// hll_estimate: reg[HLL_M] one-byte registers -> alpha m^2 / sum(2^-reg[j]) with alpha = 0.7213 / (1 + 1.079 / m); m ln(m / V) instead when
+// that is <= 2.5 m and V > 0 registers are 0; floor(E + 0.5); 0 for an all-zero sketch.  (The sum runs rank by rank, 0 upwards.)
+constexpr u32 HLL_M = 4096;
+u64 hll_estimate(const u8 *reg);
+// format_report with one more column after the direct count, "%6.2f\t%llu\t%llu\t%llu\t%s\t%u\t%s%s\n": the estimate of the node's clade
+// sketch = the register-wise maximum over the sketched bins in its subtree (sketch_bins ascending and distinct, sketch_regs HLL_M bytes
+// each, already merged over the contexts; 0 when the subtree has none).  0 on the "unclassified" line, bin n's own estimate on
+// "(not in taxonomy)".  The same lines in the same order as the seven-column report.
+std::string format_report(const u64 *direct, const u64 *clade, u32 n, const u32 *parent, const std::vector<std::string> &ranks,
+                          const std::unordered_map<u32, std::string> &names, const u32 *sketch_bins, const u8 *sketch_regs, u32 n_sketched);
 
 // ---- reads --------------------------------------------------------------------------------------------
 struct bseq1_t {                // kseq_declare.h:40-44; the fields are VIEWS into memory owned by a ReadChunk (below)
@@ -310,6 +321,7 @@ struct ClassifierGeneric {
     int get_emit_fastq() const { return output_flag_ & FASTQ; }
     std::FILE *taxon_out_ = nullptr;         // `bonsai classify -b`: the taxon of every unit, in input order, as raw little-endian u32
     std::FILE *report_out_ = nullptr;        // `bonsai classify -R`: the taxon report, written by write_report after the last unit
+    bool sketch_on_ = false;                 // `-u` (enable_sketch): the report carries the distinct k-mer column
     unsigned min_qual_ = 0;                  // `bonsai classify -Q`: set_min_base_quality (0: off)
     bool nseq_printed_ = false;              // process_dataset's "nseq:" line on stderr has been printed (by the device text path or the host one)
     u64 n_classified() const { return classified_[0]; }
@@ -324,6 +336,10 @@ void set_confidence(ClassifierGeneric &c, u64 num, u64 den);
 void set_min_base_quality(ClassifierGeneric &c, unsigned q);
 // `bonsai classify -R`: a tally on every context of the classifier (bns_tally_enable), before the first unit ...
 void enable_tally(ClassifierGeneric &c);
+// `bonsai classify -R -u`: sketches of the distinct k-mers per taxon on every context (bns_sketch_enable), before the first unit;
+// write_report then reads them, merges equal bins over the contexts and writes the eight-column report (bins without a sketch: a
+// warning on stderr)
+void enable_sketch(ClassifierGeneric &c, u32 max_taxa);
 // ... and, after the last, the tallies summed over the contexts and the report written to c.report_out_ (names_dmp may be nullptr)
 void write_report(ClassifierGeneric &c, const std::vector<u32> &parent, const char *nodes_dmp, const char *names_dmp);
 

@@ -1,12 +1,15 @@
 // bns_report.cpp -- the per-sample taxon report of `bonsai classify -R` (Kraken 2's standard report layout): nodes.dmp ranks,
 // names.dmp scientific names, the text, and the read-out of the device tallies.  The counting itself runs on the device
 // (bns_tally_enable / bns_tally_read: tally_kernel, clade_kernel).  No reference counterpart: the reference counts classified and
-// unclassified reads (classifier.h:138,238) and prints neither.
+// unclassified reads (classifier.h:138,238) and prints neither.  `-u` adds a column: the distinct k-mers of each node's clade, estimated
+// from the device's HyperLogLog sketches (bns_sketch_enable / bns_sketch_read), merged up the taxonomy here.
 #include "bns_host_internal.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <fstream>
+#include <map>
 
 namespace bns {
 namespace {
@@ -43,18 +46,80 @@ const char *rank_letter(const std::string &r)
     return "";
 }
 
-void report_line(std::string &out, u64 clade, u64 direct, u64 total, const std::string &code, u32 taxid, unsigned depth, const std::string &name)
+// distinct: the extra column of the `-u` report (nullptr: the seven-column line)
+void report_line(std::string &out, u64 clade, u64 direct, const u64 *distinct, u64 total, const std::string &code, u32 taxid, unsigned depth,
+                 const std::string &name)
 {
-    char head[128];
+    char head[160];
     const double pct = total ? 100.0 * (double)clade / (double)total : 0.0;
-    std::snprintf(head, sizeof(head), "%6.2f\t%llu\t%llu\t%s\t%u\t", pct, (unsigned long long)clade, (unsigned long long)direct, code.c_str(), taxid);
+    if (distinct)
+        std::snprintf(head, sizeof(head), "%6.2f\t%llu\t%llu\t%llu\t%s\t%u\t", pct, (unsigned long long)clade, (unsigned long long)direct,
+                      (unsigned long long)*distinct, code.c_str(), taxid);
+    else
+        std::snprintf(head, sizeof(head), "%6.2f\t%llu\t%llu\t%s\t%u\t", pct, (unsigned long long)clade, (unsigned long long)direct, code.c_str(), taxid);
     out += head;
     out.append((size_t)depth * 2, ' ');
     out += name;
     out += '\n';
 }
 
+// distinct[v], v in [0, n]: the estimate of the register-wise maximum over the sketched bins in v's subtree (0: none there); bin n its own,
+// bin 0 left at 0 (the unclassified line has no k-mers).  The nodes that matter are the sketched bins and their ancestors: each is
+// visited once, children before parents (a node is ready when its last child with a sketch has been merged into it), and each sketch is
+// merged into its parent's once -- no sketch walks its whole chain.
+std::vector<u64> clade_distinct(const u32 *bins, const u8 *regs, u32 n_sk, u32 n, const u32 *parent)
+{
+    std::vector<u64> distinct((size_t)n + 1, 0);
+    std::vector<u32> idx(n, 0xFFFFFFFFu);                  // node -> its entry in the three vectors below
+    std::vector<u32> node, pending;
+    std::vector<std::vector<u8>> sk;
+    auto up = [&](u32 v) -> u32 { const u32 p = parent[v]; return (p == 0 || p >= n || p == v) ? 0u : p; };
+    for (u32 i = 0; i < n_sk; ++i) {
+        const u32 b = bins[i];
+        const u8 *r = regs + (size_t)i * HLL_M;
+        if (b == n) { distinct[n] = hll_estimate(r); continue; }
+        if (b == 0 || b > n) continue;
+        for (u32 v = b, prev = 0xFFFFFFFFu; v; v = up(v)) {            // b and its ancestors, up to the first one already known
+            const bool known = idx[v] != 0xFFFFFFFFu;
+            if (!known) { idx[v] = (u32)node.size(); node.push_back(v); pending.push_back(0); sk.emplace_back(); }
+            if (prev != 0xFFFFFFFFu) ++pending[idx[v]];
+            prev = v;
+            if (known || node.size() > n) break;
+        }
+        sk[idx[b]].assign(r, r + HLL_M);
+    }
+    std::vector<u32> ready;
+    for (u32 e = 0; e < node.size(); ++e) if (!pending[e]) ready.push_back(e);
+    while (!ready.empty()) {
+        const u32 e = ready.back();
+        ready.pop_back();
+        const u32 v = node[e], p = up(v);
+        if (!sk[e].empty()) distinct[v] = hll_estimate(sk[e].data());
+        if (p && idx[p] != 0xFFFFFFFFu) {
+            std::vector<u8> &ps = sk[idx[p]];
+            if (ps.empty()) ps.swap(sk[e]);
+            else if (!sk[e].empty()) for (u32 j = 0; j < HLL_M; ++j) ps[j] = std::max(ps[j], sk[e][j]);
+            if (--pending[idx[p]] == 0) ready.push_back(idx[p]);
+        }
+        std::vector<u8>().swap(sk[e]);                     // (merged: only the frontier's sketches are held)
+    }
+    return distinct;
+}
+
 }  // namespace
+
+u64 hll_estimate(const u8 *reg)
+{
+    u32 cnt[64] = {0};
+    for (u32 j = 0; j < HLL_M; ++j) ++cnt[reg[j] & 63u];
+    if (cnt[0] == HLL_M) return 0;
+    const double m = (double)HLL_M;
+    double sum = 0.0;                                      // sum of 2^-reg[j], rank by rank in ascending order (a fixed order: reproducible)
+    for (int r = 0; r < 64; ++r) sum += (double)cnt[r] * std::ldexp(1.0, -r);
+    double e = 0.7213 / (1.0 + 1.079 / m) * m * m / sum;
+    if (e <= 2.5 * m && cnt[0]) e = m * std::log(m / (double)cnt[0]);
+    return e < 18446744073709549568.0 ? (u64)std::floor(e + 0.5) : ~0ULL;      // (every register near 53: past what a u64 holds)
+}
 
 std::vector<std::string> read_node_ranks(const char *nodes_dmp)
 {
@@ -88,13 +153,15 @@ std::unordered_map<u32, std::string> read_scientific_names(const char *names_dmp
     return names;
 }
 
-std::string format_report(const u64 *direct, const u64 *clade, u32 n, const u32 *parent, const std::vector<std::string> &ranks,
-                          const std::unordered_map<u32, std::string> &names)
+namespace {
+std::string format_report_impl(const u64 *direct, const u64 *clade, u32 n, const u32 *parent, const std::vector<std::string> &ranks,
+                               const std::unordered_map<u32, std::string> &names, const u64 *distinct)
 {
+    const u64 zero = 0;
     u64 total = 0;
     for (u32 v = 0; v <= n; ++v) total += direct[v];
     std::string out;
-    if (direct[0]) report_line(out, direct[0], direct[0], total, "U", 0u, 0u, "unclassified");
+    if (direct[0]) report_line(out, direct[0], direct[0], distinct ? &zero : nullptr, total, "U", 0u, 0u, "unclassified");
     // children lists of the nodes with a count, in print order: clade descending, ties by taxid ascending
     std::vector<u32> child_cnt(n + 1, 0);
     std::vector<u32> roots;
@@ -131,17 +198,37 @@ std::string format_report(const u64 *direct, const u64 *clade, u32 n, const u32 
             if (!own.empty()) { f.base = own; f.steps = 0; }
             else if (!f.base.empty()) ++f.steps;
             const std::string code = f.base.empty() ? std::string("-") : f.steps ? f.base + std::to_string(f.steps) : f.base;
-            report_line(out, clade[f.v], direct[f.v], total, code, f.v, f.depth, name_of(f.v));
+            report_line(out, clade[f.v], direct[f.v], distinct ? distinct + f.v : nullptr, total, code, f.v, f.depth, name_of(f.v));
             for (u32 i = off[f.v + 1]; i-- > off[f.v];) st.push_back({kids[i], f.depth + 1, f.steps, f.base});   // (first child on top)
         }
     }
-    if (direct[n]) report_line(out, direct[n], direct[n], total, "-", 0xFFFFFFFFu, 0u, "(not in taxonomy)");
+    if (direct[n]) report_line(out, direct[n], direct[n], distinct ? distinct + n : nullptr, total, "-", 0xFFFFFFFFu, 0u, "(not in taxonomy)");
     return out;
+}
+}  // namespace
+
+std::string format_report(const u64 *direct, const u64 *clade, u32 n, const u32 *parent, const std::vector<std::string> &ranks,
+                          const std::unordered_map<u32, std::string> &names)
+{
+    return format_report_impl(direct, clade, n, parent, ranks, names, nullptr);
+}
+
+std::string format_report(const u64 *direct, const u64 *clade, u32 n, const u32 *parent, const std::vector<std::string> &ranks,
+                          const std::unordered_map<u32, std::string> &names, const u32 *sketch_bins, const u8 *sketch_regs, u32 n_sketched)
+{
+    const std::vector<u64> distinct = clade_distinct(sketch_bins, sketch_regs, n_sketched, n, parent);
+    return format_report_impl(direct, clade, n, parent, ranks, names, distinct.data());
 }
 
 void enable_tally(ClassifierGeneric &c)
 {
     for (bns_ctx *cx : c.ctxs_) chk(cx, bns_tally_enable(cx, 1), "bns_tally_enable");
+}
+
+void enable_sketch(ClassifierGeneric &c, u32 max_taxa)
+{
+    for (bns_ctx *cx : c.ctxs_) chk(cx, bns_sketch_enable(cx, max_taxa), "bns_sketch_enable");
+    c.sketch_on_ = true;
 }
 
 void write_report(ClassifierGeneric &c, const std::vector<u32> &parent, const char *nodes_dmp, const char *names_dmp)
@@ -154,7 +241,34 @@ void write_report(ClassifierGeneric &c, const std::vector<u32> &parent, const ch
     }
     const std::vector<std::string> ranks = read_node_ranks(nodes_dmp);
     const std::unordered_map<u32, std::string> names = names_dmp ? read_scientific_names(names_dmp) : std::unordered_map<u32, std::string>{};
-    const std::string text = format_report(direct.data(), clade.data(), n, parent.data(), ranks, names);
+    std::string text;
+    if (c.sketch_on_) {
+        // one set of sketches per context: equal bins merge by the register-wise maximum (bins come back ascending)
+        std::map<u32, std::vector<u8>> merged;
+        u64 dropped = 0;
+        for (bns_ctx *cx : c.ctxs_) {
+            u32 s = 0, dr = 0;
+            chk(cx, bns_sketch_read(cx, nullptr, nullptr, 0, &s, &dr, 0), "bns_sketch_read");
+            std::vector<u32> bins(s);
+            std::vector<u8> regs((size_t)s * HLL_M);
+            chk(cx, bns_sketch_read(cx, bins.data(), regs.data(), s, &s, &dr, 0), "bns_sketch_read");
+            dropped += dr;
+            for (u32 i = 0; i < s; ++i) {
+                const u8 *r = regs.data() + (size_t)i * HLL_M;
+                std::vector<u8> &m = merged[bins[i]];
+                if (m.empty()) m.assign(r, r + HLL_M);
+                else for (u32 j = 0; j < HLL_M; ++j) m[j] = std::max(m[j], r[j]);
+            }
+        }
+        if (dropped)
+            std::fprintf(stderr, "[W] -u: %llu taxon bins got no sketch (-U sets how many there are): the distinct k-mer column is a lower bound for their clades\n",
+                         (unsigned long long)dropped);
+        std::vector<u32> bins;
+        std::vector<u8> regs;
+        bins.reserve(merged.size()); regs.reserve(merged.size() * HLL_M);
+        for (const auto &kv : merged) { bins.push_back(kv.first); regs.insert(regs.end(), kv.second.begin(), kv.second.end()); }
+        text = format_report(direct.data(), clade.data(), n, parent.data(), ranks, names, bins.data(), regs.data(), (u32)bins.size());
+    } else text = format_report(direct.data(), clade.data(), n, parent.data(), ranks, names);
     if (!c.report_out_ || std::fwrite(text.data(), 1, text.size(), c.report_out_) != text.size()) die("Could not write the report");
 }
 

@@ -43,6 +43,9 @@ void usage(const char *exe)
                  "-R:\tAlso write a taxon report to this path after the last read (Kraken 2's standard report layout: percent of all\n"
                  "\treads, clade count, direct count, rank code, taxid, indented name), tallied on the GPU(s).\n"
                  "-n:\tnames.dmp for the report's names (scientific names; without it a taxon is named by its id).\n"
+                 "-u:\tWith -R: one more column after the direct count, the number of distinct k-mers of the db that the reads covered in the\n"
+                 "\ttaxon's clade (HyperLogLog estimate, 4096 registers: 1.6 %% standard error), by the k-mers' own taxa.\n"
+                 "-U:\tTaxa that can have a sketch per GPU context, 4 KiB each [65536]; beyond that a taxon's k-mers are not counted (a warning says so).\n"
                  "-t:\tConfidence threshold in [0, 1] (digits, at most 9 after the point) [0]: a read (pair) is called at the first of its\n"
                  "\ttaxon and the taxon's ancestors whose clade holds at least that fraction of its k-mers, else unclassified.\n"
                  "-Q:\tMinimum base quality, an integer in [0, 93] [0: off]: a base whose Phred+33 quality is lower counts as N, so no k-mer\n"
@@ -90,8 +93,10 @@ int classify_main(int argc, char *argv[])
     const char *names_path = nullptr;
     unsigned long long conf_num = 0, conf_den = 1;
     unsigned min_qual = 0;
+    bool distinct = false;
+    long sketch_taxa = 65536;
     if (argc < 4) usage(argv[0]);
-    while ((co = getopt(argc, argv, "Cc:p:o:S:afFkKg:L:NP:b:R:n:t:Q:h?")) >= 0) {
+    while ((co = getopt(argc, argv, "Cc:p:o:S:afFkKg:L:NP:b:R:n:t:Q:uU:h?")) >= 0) {
         switch (co) {
             case 'h': case '?': usage(argv[0]); break;
             case 'C': canonicalize = false; break;
@@ -106,6 +111,16 @@ int classify_main(int argc, char *argv[])
             case 'b': taxon_fp = std::fopen(optarg, "wb"); if (!taxon_fp) { std::fprintf(stderr, "Could not open taxon file\n"); return EXIT_FAILURE; } break;
             case 'R': report_fp = std::fopen(optarg, "w"); if (!report_fp) { std::fprintf(stderr, "Could not open report file\n"); return EXIT_FAILURE; } break;
             case 'n': names_path = optarg; break;
+            case 'u': distinct = true; break;
+            case 'U': {
+                char *end = nullptr;
+                sketch_taxa = std::strtol(optarg, &end, 10);
+                if (!*optarg || *end || sketch_taxa < 1 || sketch_taxa > (1L << 20)) {
+                    std::fprintf(stderr, "[E] -U: the number of sketched taxa must be an integer in [1, 1048576], not '%s'\n", optarg);
+                    return EXIT_FAILURE;
+                }
+                break;
+            }
             case 't':
                 if (!parse_confidence(optarg, conf_num, conf_den)) {
                     std::fprintf(stderr, "[E] -t: the confidence threshold must be a decimal in [0, 1] with at most 9 digits after the point, not '%s'\n", optarg);
@@ -136,6 +151,7 @@ int classify_main(int argc, char *argv[])
         }
     }
     if (!ofp) { std::fprintf(stderr, "Could not open output file\n"); return EXIT_FAILURE; }
+    if (distinct && !report_fp) { std::fprintf(stderr, "[E] -u adds a column to the taxon report: it needs -R <path>\n"); return EXIT_FAILURE; }
     const int npos = argc - optind;
     if (npos != 3 && npos != 4) usage(argv[0]);
     const auto t_start = std::chrono::steady_clock::now();
@@ -191,6 +207,7 @@ int classify_main(int argc, char *argv[])
         if (conf_num) bns::set_confidence(c, conf_num, conf_den);
         if (min_qual) bns::set_min_base_quality(c, min_qual);
         if (report_fp) bns::enable_tally(c);
+        if (distinct) bns::enable_sketch(c, (bns::u32)sketch_taxa);
         if (devs.size() > 1) {                                   // which collective library replicated the db over how many devices
             // (one line per device: a multi-GPU record says what it ran on)
             for (size_t i = 0; i < devs.size(); ++i) {

@@ -55,6 +55,10 @@ def lib():
         L.bnsh_format_report.restype = C.c_int
         L.bnsh_format_report.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_char_p,
                                          C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.bnsh_hll_estimate.restype = C.c_uint64; L.bnsh_hll_estimate.argtypes = [C.c_void_p]
+        L.bnsh_format_report_distinct.restype = C.c_int
+        L.bnsh_format_report_distinct.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_char_p,
+                                                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -87,9 +91,18 @@ def read_scientific_names(path):
     return {int(i): x.decode() for i, x in zip(idv, names)}
 
 
-def format_report(direct, clade, parent, ranks=None, names=None):
+def hll_estimate(registers):
+    """bns::hll_estimate: the distinct-key estimate of one HyperLogLog sketch (4096 one-byte registers)"""
+    registers = np.ascontiguousarray(registers, dtype=np.uint8)
+    if registers.size != 4096:
+        raise ValueError("a sketch has 4096 registers")
+    return int(lib().bnsh_hll_estimate(registers.ctypes.data))
+
+
+def format_report(direct, clade, parent, ranks=None, names=None, sketch_bins=None, sketch_registers=None):
     """the `bonsai classify -R` report text (bns::format_report) from the tallies (n + 1 entries each), parent[] (n), ranks (list by
-    taxid) and names ({taxid: name})"""
+    taxid) and names ({taxid: name}); with sketch_bins (ascending) and sketch_registers ([s, 4096], merged over the contexts) the `-u`
+    report with the distinct k-mer column"""
     direct = np.ascontiguousarray(direct, dtype=np.uint64); clade = np.ascontiguousarray(clade, dtype=np.uint64)
     parent = np.ascontiguousarray(parent, dtype=np.uint32)
     n = parent.size
@@ -101,6 +114,17 @@ def format_report(direct, clade, parent, ranks=None, names=None):
     ids = np.array([i for i, _ in items], dtype=np.uint32)
     nb = b"".join(x.encode() + b"\0" for _, x in items)
     out, ob = C.c_void_p(), C.c_uint64()
+    if sketch_bins is not None:
+        sb = np.ascontiguousarray(sketch_bins, dtype=np.uint32)
+        sr = np.ascontiguousarray(sketch_registers, dtype=np.uint8)
+        if sr.size != sb.size * 4096:
+            raise ValueError("sketch_registers needs 4096 bytes per bin")
+        if lib().bnsh_format_report_distinct(direct.ctypes.data, clade.ctypes.data, n, parent.ctypes.data, rb if ranks else None, len(ranks),
+                                             ids.ctypes.data if items else None, nb if items else None, len(items),
+                                             sb.ctypes.data if sb.size else None, sr.ctypes.data if sb.size else None, sb.size,
+                                             C.byref(out), C.byref(ob)) != 0:
+            raise HostIOError(lib().bnsh_last_error().decode())
+        return _take_blob(out, ob.value).decode()
     if lib().bnsh_format_report(direct.ctypes.data, clade.ctypes.data, n, parent.ctypes.data, rb if ranks else None, len(ranks),
                                 ids.ctypes.data if items else None, nb if items else None, len(items), C.byref(out), C.byref(ob)) != 0:
         raise HostIOError(lib().bnsh_last_error().decode())

@@ -191,6 +191,33 @@ int bns_tally_read(bns_ctx *ctx, uint64_t *direct, uint64_t *clade, uint32_t len
  * nothing is launched or allocated.  Reloading the taxonomy keeps the setting.  bns_resolve_batch and bns_probe* are not affected. */
 int bns_set_confidence(bns_ctx *ctx, uint64_t num, uint64_t den);
 
+/* ---- distinct k-mers per taxon (what `bonsai classify -R -u` reports) --------------------------------------------------------------
+ * No reference counterpart (Kraken 2's --report-minimizer-data, KrakenUniq); defined in DESIGN.md.  One HyperLogLog sketch per bin.
+ * What is counted: every unit a classify launch processes (the entry points bns_tally_enable lists), every k-mer classify looks up:
+ * each k-window of a read made only of unmasked A/C/G/T -- window = k whatever bns_set_window says, the canonical form when the
+ * encoder is canonical, the spaced key when it is spaced, nothing for a spaced seed without spaced_intended, both mates of a pair.
+ * A key found with value t goes to the sketch of bin t for a taxon t < n whose chain reaches a root, bin 0 for t = 0, bin n otherwise
+ * (bns_tally_enable's bins): by the k-mer's own value, not the read's call, so bns_set_confidence does not change it; a minimum
+ * base quality does (the masked image).  Units classified twice (a text call that rolls a batch back) change nothing.
+ * Sketch: m = 4096 registers of one byte.  For key x (uint64_t): h = fmix64(x), MurmurHash3's finaliser (x ^= x >> 33;
+ * x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33); register j = h >> 52; w = h << 12; rho = 53 when w == 0,
+ * else clz(w) + 1; reg[j] = max(reg[j], rho).  No arrival order enters: the bytes are exactly reproducible.
+ * Estimate (host, double): alpha = 0.7213 / (1 + 1.079 / m); E = alpha m^2 / sum(2^-reg[j]); when E <= 2.5 m and V > 0 registers are 0,
+ * E = m ln(m / V); the result is floor(E + 0.5); 0 for an all-zero sketch.  A clade's (or several contexts') sketch is the
+ * register-wise maximum of its bins'; bins 0 and n have no subtree.
+ * bns_sketch_enable(ctx, max_taxa): needs a loaded taxonomy, else BNS_ERR_STATE; allocates max_taxa sketches of 4 KiB, uint32_t
+ * slot_of[n + 1] and seen[n + 1], all zero.  Behind every classify launch, on its stream: the bins of the launch's hits are marked,
+ * those seen for the first time take the next free sketches in ascending bin order, then the k-mers are looked up again and added.
+ * When the sketches run out the remaining bins get none and their k-mers are not sketched (n_dropped_bins counts them): which bins
+ * those are is decided by the sequence of launches alone.  A call that takes no hits has them written to a buffer of the context's
+ * (4 bytes per base, shared with bns_set_confidence).  max_taxa = 0 frees everything and turns it off (the default): nothing is
+ * launched, allocated or read.  Reloading the taxonomy zeroes the sketches.
+ * bns_sketch_read: bins[cap] receives the sketched bins in ascending order, registers[4096 * cap] their sketches in the same order;
+ * either may be NULL (both: only the counts).  cap < *n_sketched: BNS_ERR_ARG, with *n_sketched set.  reset: registers, seen and slots
+ * back to zero after reading.  Runs on the context's stream, like bns_tally_read. */
+int bns_sketch_enable(bns_ctx *ctx, uint32_t max_taxa);
+int bns_sketch_read(bns_ctx *ctx, uint32_t *bins, uint8_t *registers, uint32_t cap, uint32_t *n_sketched, uint32_t *n_dropped_bins, int reset);
+
 /* ---- hot path --------------------------------------------------------------------------------- */
 /* Replaces: the kt_forpool fan-out in classify_seqs (classifier.h:275) over classify_seq
  * (classifier.h:212-251), i.e. per read (or mate pair): Encoder::for_each -> kh_get(c) ->
