@@ -112,6 +112,7 @@ __device__ __forceinline__ u64 lanemask_lt() { return (1ULL << lane_id()) - 1ULL
 struct ProbeResult { u32 val; bool found; };
 #ifdef BNS_COUNT_FETCHES                        // measurement builds only (tools/measure.sh)
 __device__ unsigned long long g_fetch_count[8];      // buckets fetched, probe passes, lanes sent to the overflow table, rounds with such lanes, quad-probe iterations
+                                                     // [5..7] later passes of the two-key probe by cause: runs beyond the stage, chain walks, both
 #endif
 
 // kh_get on the untouched khash arrays (khash64.h:250-263): triangular probing, 2-bit flags
@@ -614,12 +615,19 @@ __device__ __forceinline__ ProbeResult probe_minbucket(const MinBucket *__restri
 // against half A's lane 63 and the group that straddles the two rounds is one run, fetched once; half B's ranks start at half
 // A's leader count.  Everything else -- stage, chain walk, home / tag bits, MINB_N_IN_OVF, the overflow table, runs ranked NB
 // and beyond left for a later pass -- is probe_minbucket's (TAGS = false, OVF_COOP = false, NB = 16), once per half.
+// The stage of a pass is nb buckets, wave-uniform and the caller's choice per call: 16, or MINB_NB_WIDE = 24 where the caller owns a
+// third KiB directly behind the 16-bucket stage and does not need it now (classify_kernel: the counter's LDS arrays, dead while a
+// unit has at most 64 distinct taxa).  A pair of rounds of a 150-bp read has 15.0 +- 1.9 run leaders: more than 16 in one pair out
+// of five, more than 24 in fewer than one out of 10^4 -- the third load, issued only when there are leaders for it, saves those
+// pairs their second pass.  (nb formed from the counter's size inside every pass instead -- no value of its own live through the
+// probe, four spilled SGPRs fewer -- measured slower: configs[1] -2.7 % instead of -3.3 %, 100-bp reads +1.9 % instead of +0.8 %.)
+constexpr int MINB_NB_WIDE = 24;
 template <bool KEY_MAY_BE_ONES = true, int NB = 16>
 __device__ __forceinline__ void probe_minbucket2(const MinBucket *__restrict__ buckets, u64 keyA, u32 bA, bool activeA, u64 keyB, u32 bB,
                                                  bool activeB, u32 *aux, const Slot *__restrict__ ovf_slots, u64 ovf_mask,
-                                                 ProbeResult &ra, ProbeResult &rb)
+                                                 ProbeResult &ra, ProbeResult &rb, u32 nb = 16u)
 {
-    static_assert(NB == 16, "the two-key probe stages 16 buckets (two 1 KiB loads)");
+    static_assert(NB == 16, "the two-key probe is built on a 16-bucket stage (two 1 KiB loads; nb = 24 adds a third)");
     const int lane = lane_id();
     u32 *list = aux;
     uint4 *stage = reinterpret_cast<uint4 *>(aux + MINB_LIST_U32);
@@ -631,7 +639,7 @@ __device__ __forceinline__ void probe_minbucket2(const MinBucket *__restrict__ b
     // one half's lookup in the stage and its verdict (probe_minbucket's, TAGS = false); returns "walks on"
     auto look = [&](auto first_tag, u32 &bkt, u32 rank, u32 xf, u64 key, u32 &found, u32 &val, u32 home, u32 &hx) -> bool {
         constexpr bool FIRST = decltype(first_tag)::value;
-        const bool mine = bkt != MINB_NONE && rank < (u32)NB;
+        const bool mine = bkt != MINB_NONE && rank < nb;
         const char *B = reinterpret_cast<const char *>(stage) + (mine ? rank : 0u) * (16u * MINB_STRIDE);
         const uint2 hdr = *reinterpret_cast<const uint2 *>(B + 120);
         const u32 slot = mph_slot(xf, hdr.y);
@@ -658,6 +666,9 @@ __device__ __forceinline__ void probe_minbucket2(const MinBucket *__restrict__ b
         home = cont ? cur >> 1 : home;
     };
     bool more = true;
+#ifdef BNS_COUNT_FETCHES
+    u32 why_later = 4u;
+#endif
     auto pass = [&](auto first_tag) -> bool {
         // run leaders over the 128 positions: half B's lane 0 continues half A's lane 63
         const u32 a63 = readlane(bktA, 63);
@@ -669,13 +680,17 @@ __device__ __forceinline__ void probe_minbucket2(const MinBucket *__restrict__ b
         const u32 nA = (u32)__popcll(leadA);
         const int n_lead = (int)nA + __popcll(leadB);
 #ifdef BNS_COUNT_FETCHES
-        if (lane == 0) { atomicAdd(&g_fetch_count[0], (unsigned long long)(n_lead < NB ? n_lead : NB)); atomicAdd(&g_fetch_count[1], 1ULL); }
+        if (lane == 0) {
+            atomicAdd(&g_fetch_count[0], (unsigned long long)((u32)n_lead < nb ? (u32)n_lead : nb)); atomicAdd(&g_fetch_count[1], 1ULL);
+            // why a later pass was entered: runs ranked beyond the stage (slot 5), lanes down their chains only (slot 6), both (slot 7)
+            if (!decltype(first_tag)::value) atomicAdd(&g_fetch_count[why_later], 1ULL);
+        }
 #endif
         const u32 rankA = __builtin_amdgcn_mbcnt_hi((u32)(leadA >> 33), __builtin_amdgcn_mbcnt_lo((u32)(leadA >> 1), (u32)(leadA & 1ULL) - 1u));
         const u32 rankB = __builtin_amdgcn_mbcnt_hi((u32)(leadB >> 33), __builtin_amdgcn_mbcnt_lo((u32)(leadB >> 1), nA + (u32)(leadB & 1ULL) - 1u));
-        // (the list has 64 entries: half A's ranks are below 64, half B's reach 127 -- and only the first NB are fetched)
+        // (the list has 64 entries: half A's ranks are below 64, half B's reach 127 -- and only the first nb are fetched)
         if (pendA & chgA) list[rankA] = bktA;
-        if ((pendB & chgB) && rankB < (u32)NB) list[rankB] = bktB;
+        if ((pendB & chgB) && rankB < nb) list[rankB] = bktB;
         __builtin_amdgcn_wave_barrier();
         {
             const u32 last = (u32)n_lead - 1u, slot = (u32)lane >> 3;
@@ -686,6 +701,10 @@ __device__ __forceinline__ void probe_minbucket2(const MinBucket *__restrict__ b
             if (last >= 8u) {
                 const u32 b1 = list[slot + 8u < last ? slot + 8u : last];
                 __builtin_amdgcn_global_load_lds((gptr_t)(base + ((u64)b1 * 8 + (u64)(lane & 7))), (lptr_t)(stage + 64), 16, 0, 2);
+                if (last >= 16u && nb > 16u) {         // (wave-uniform) the third KiB: leaders 16..23 (last >= 16: slot + 16 <= 23 and list[last] are written)
+                    const u32 b2 = list[slot + 16u < last ? slot + 16u : last];
+                    __builtin_amdgcn_global_load_lds((gptr_t)(base + ((u64)b2 * 8 + (u64)(lane & 7))), (lptr_t)(stage + 128), 16, 0, 2);
+                }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -694,7 +713,10 @@ __device__ __forceinline__ void probe_minbucket2(const MinBucket *__restrict__ b
         const bool contA = look(first_tag, bktA, rankA, xfA, keyA, foundA, valA, homeA, hxA);
         const bool contB = look(first_tag, bktB, rankB, xfB, keyB, foundB, valB, homeB, hxB);
         const u64 cA = ballot64(contA), cB = ballot64(contB);
-        more = n_lead > NB || (cA | cB) != 0ULL;
+        more = (u32)n_lead > nb || (cA | cB) != 0ULL;
+#ifdef BNS_COUNT_FETCHES
+        why_later = 4u + ((u32)n_lead > nb ? 1u : 0u) + ((cA | cB) != 0ULL ? 2u : 0u);
+#endif
         if (cA) walk(first_tag, contA, hxA, bktA, foundA, homeA);                  // uncommon: walk on down the chain
         if (cB) walk(first_tag, contB, hxB, bktB, foundB, homeB);
         __builtin_amdgcn_wave_barrier();

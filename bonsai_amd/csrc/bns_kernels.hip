@@ -875,7 +875,9 @@ __device__ __forceinline__ u32 resolve_regs(u32 ckey, u32 ccnt, u32 D, const Tax
 // NM > 0 fixes the number of mates per unit the same way (1 = single-end: no mate loop, no third offset).
 // offv = offsets of the unit's reads, one per lane (lanes 0..nmates); (have0, r_lo, r_hi) = prefetched pass 0 of mate 0.
 // ob = lane of offv that holds the unit's first offset (the caller keeps a whole chunk's offsets in one register pair)
-template <bool SPACED, int LAYOUT, int KT, int NM, int NB = 16, int SPAN = 8, bool OVC = false, bool WIDE = false, bool PACKED = false>
+// STAGE3: keys / cnt lie directly behind the 16-bucket stage of aux (the PAIRS instantiations of classify_kernel), so the two-round
+// probe may stage 24 buckets while the counter has nothing in them.
+template <bool SPACED, int LAYOUT, int KT, int NM, int NB = 16, int SPAN = 8, bool OVC = false, bool WIDE = false, bool PACKED = false, bool STAGE3 = false>
 __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u64 offv, u32 ob, bool have0, const Prefetch &pre0,
                                               u32 *keys, u32 *cnt, u32 *tin, u32 *tout, u32 cap, bool record_overflow, u32 *ring, u32 *aux, u64 *pk,
                                               uint4 &rec_out, bool &rec_valid)
@@ -969,7 +971,10 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
                         u32 bB;
                         const bool vB = key_round(rd + 1u, keyB, bB);
                         ProbeResult pa, pb;
-                        probe_minbucket2<(KT == 32), NB>(p.minb, keyA, bA, vA, keyB, bB, vB, aux, p.slots, p.ovf_mask, pa, pb);
+                        // (the counter's LDS arrays lie directly behind the stage -- classify_kernel -- and are dead while every entry is in
+                        // a register: until the unit's 65th taxon they are the stage's third KiB)
+                        probe_minbucket2<(KT == 32), NB>(p.minb, keyA, bA, vA, keyB, bB, vB, aux, p.slots, p.ovf_mask, pa, pb,
+                                                         (STAGE3 && D <= 64u) ? (u32)MINB_NB_WIDE : 16u);
                         const u64 fa = tally(pa, vA), fb = tally(pb, vB);
                         vote2(fa, pa.val, fb, pb.val);
                     } else {                                          // an odd last round: the one-round probe
@@ -1090,10 +1095,15 @@ template <bool SPACED, int LAYOUT, int KT, int NM, int SPAN = 8, bool OVC = fals
 __global__ __launch_bounds__(256, (LAYOUT == 1 && !SPACED) ? 7 : ClassifyCfg<SPACED>::WAVES) void classify_kernel(ClassifyParams p)
 {
     constexpr int NB = LAYOUT == 2 ? ClassifyCfg<SPACED>::NB : 16;
-    constexpr int AUX_U32 = minb_aux_u32(NB);
+    // the forms that probe two rounds at a time (classify_unit: PAIRS) keep the counter's arrays in the row of the stage, right behind
+    // its 16 buckets: list 64, stage 16 x 32, keys 128, counts 128 u32 = minb_aux_u32(24), the same bytes as the separate arrays
+    constexpr bool PAIRS = !SPACED && LAYOUT == 2 && KT != 0 && !OVC && !WIDE;
+    constexpr int AUX_U32 = PAIRS ? minb_aux_u32(MINB_NB_WIDE) : minb_aux_u32(NB);
+    // (the two-mate ASCII forms sit at 63 VGPRs and take the third load only with 12 bytes of scratch: they keep the 16-bucket stage)
+    constexpr bool STAGE3 = PAIRS && !(NM == 2 && !PACKED);
+    static_assert(!PAIRS || (NB == 16 && minb_aux_u32(MINB_NB_WIDE) == minb_aux_u32(16) + 2 * (int)LDS_CAP), "the counter is the stage's third KiB");
     // per wave: counter keys/counts (1 KB), minimizer ring + bucket list + bucket stage (3.1 KB; the stage doubles as the
-    // tin/tout scratch of resolve_wave, which runs when no probe is in flight), packed chunk image (1 KB): 19.8 KB / block
-    __shared__ u32 s_keys[4][LDS_CAP], s_cnt[4][LDS_CAP];
+    // tin/tout scratch of resolve_wave -- its first KiB -- which runs when no probe is in flight), packed chunk image (1 KB): 19.8 KB / block
     // (ring, list + stage and chunk image are separate arrays: the stage is written by the fetch itself (LDS DMA), and the compiler
     // puts a vmcnt wait in front of any LDS access it cannot tell apart from it)
     // (the ring holds 64 + window - 1 <= 79 entries: 32-bit hashes, or 64-bit identities for a table with the wide minimizer identity)
@@ -1102,6 +1112,13 @@ __global__ __launch_bounds__(256, (LAYOUT == 1 && !SPACED) ? 7 : ClassifyCfg<SPA
     __shared__ u64 s_pk[4][IMG_U64];
     static_assert(AUX_U32 - MINB_LIST_U32 >= 2 * (int)LDS_CAP, "stage must hold tin/tout");
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // wave-uniform: keeps the unit loop scalar
+    u32 *ctr_keys, *ctr_cnt;
+    if constexpr (PAIRS) {
+        ctr_keys = s_mh[wv] + minb_aux_u32(16); ctr_cnt = ctr_keys + LDS_CAP;
+    } else {
+        __shared__ u32 s_keys[4][LDS_CAP], s_cnt[4][LDS_CAP];
+        ctr_keys = s_keys[wv]; ctr_cnt = s_cnt[wv];
+    }
     const int lane = lane_id();
 #ifdef BNS_WAVE_TIMES                        // measurement builds only: when does each wavefront start and finish?
     const unsigned long long t_start = wall_clock64();
@@ -1162,7 +1179,7 @@ __global__ __launch_bounds__(256, (LAYOUT == 1 && !SPACED) ? 7 : ClassifyCfg<SPA
             // The previous unit's record is stored HERE, next to the prefetch loads: gfx9 has one counter for loads and stores,
             // so the first wait after a store waits for its acknowledgement too -- this way that is the first bucket fetch.
             if (pend_valid && lane == 0) cold_params()->records[pend_u] = pend;
-            classify_unit<SPACED, LAYOUT, KT, NM, NB, SPAN, OVC, WIDE, PACKED>(p, base + j, offs, j * nm, true, pre, s_keys[wv], s_cnt[wv], s_mh[wv] + MINB_LIST_U32,
+            classify_unit<SPACED, LAYOUT, KT, NM, NB, SPAN, OVC, WIDE, PACKED, STAGE3>(p, base + j, offs, j * nm, true, pre, ctr_keys, ctr_cnt, s_mh[wv] + MINB_LIST_U32,
                                           s_mh[wv] + MINB_LIST_U32 + LDS_CAP, LDS_CAP, true, s_ring[wv], s_mh[wv], s_pk[wv], pend, pend_valid);
             pend_u = base + j;
             pre = npre;
