@@ -865,7 +865,8 @@ Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &
     chk(ctx, bns_dev_upload(ctx, d_off.p, offsets.data(), offsets.size() * 8), "upload");
     chk(ctx, bns_dev_upload(ctx, d_tx.p, taxids.data(), taxids.size() * 4), "upload");
 
-    auto pow2_for = [](u64 keys) { u64 nb = 4; while ((u64)(nb * 0.77 + 0.5) <= keys) nb <<= 1; return nb; };
+    // khash grows when n_occupied has REACHED upper_bound and another key comes (khash64.h:330): upper_bound keys still fit
+    auto pow2_for = [](u64 keys) { u64 nb = 4; while ((u64)(nb * 0.77 + 0.5) < keys) nb <<= 1; return nb; };
     // windowed dbs keep roughly 2/(ws+1) of the positions; start there and grow on BNS_ERR_TABLE
     const u64 ws = w - c + 1;
     u64 nb = pow2_for(ws > 1 ? std::max<u64>(1024, upper * 3 / (ws + 1)) : upper);

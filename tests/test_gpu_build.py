@@ -1,4 +1,8 @@
-"""Windowed minimizers and device db construction (8f-1) against the oracle."""
+"""Windowed minimizers and device db construction (8f-1) against the oracle.
+
+The device build on hard inputs -- N runs, lower case, sequences shorter than the comb or the window, keys a hundred sequences
+fold into over a deep tree, key 0, every build form, tables of 4 to 16 buckets, the load-factor boundary, the argument refusals
+-- is tests/test_gpu_build_edges.py, over the worlds of tests/build_cases.py; device_build and present_pairs below are shared."""
 import numpy as np
 import pytest
 

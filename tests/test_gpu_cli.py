@@ -221,6 +221,86 @@ def test_cli_build_then_classify(oracle, small_world, tmp_path, flags, w, score)
     assert got_out == b"".join(lines)
 
 
+@pytest.mark.parametrize("flags,w,score", [([], 31, 0), (["-w", "50", "-e"], 50, 1), (["-C", "-w", "50", "-e"], 50, 1)])
+def test_cli_build_draft_assembly(oracle, tmp_path, flags, w, score):
+    """`bonsai build` over what a draft assembly looks like: three files (one gzip) of several records each, lines of 60, lower-case
+    stretches, N runs of 1 and 40, records of 20 and of exactly 31 bases, two files under one taxid, one file whose first record is
+    not in the name map (get_taxid: taxid 1, util.h:924) -- against the oracle's map, built record by record.  Then a file of 33
+    bases: a db of three keys in four buckets, as khash sizes it."""
+    import build_cases as bc
+    from bonsai_amd import hostio
+    wld = bc.make_edge_world(oracle)
+    k = 31
+    rng = np.random.default_rng(21)
+    t_a, t_b = list(dict.fromkeys(t for t in wld.taxids if wld.depth[t] >= 3))[:2]
+    nodes = str(tmp_path / "nodes.dmp")
+    synth.write_nodes_dmp(nodes, wld.pairs)
+    core = synth.rand_seq(rng, 3000)
+
+    def rec(parts):
+        return np.concatenate([np.frombuffer(p, dtype=np.uint8) if isinstance(p, bytes) else p for p in parts]).copy()
+    a1 = rec([core[:700], b"N", core[701:1000], b"N" * 40, core[1040:1500]])
+    a1[200:500] |= 0x20
+    b1 = rec([core[500:1500], synth.rand_seq(rng, 800)])
+    b2 = rec([synth.rand_seq(rng, 450), b"N", synth.rand_seq(rng, 449)])
+    c1 = rec([synth.rand_seq(rng, 300), core[900:1500], b"N" * 40, synth.rand_seq(rng, 200)])
+    c2 = synth.rand_seq(rng, 700) | 0x20
+    files = [("a.fna", t_a, [("NC_A.1 contig one", a1), ("NC_A.1_2", synth.rand_seq(rng, 20)), ("NC_A.1_3", synth.rand_seq(rng, k)),
+                             ("NC_A.1_4", core[1400:2300])]),
+             ("b.fna.gz", t_a, [("NC_B.1 second file of the genome", b1), ("NC_B.1_2", b2), ("NC_B.1_3", b"")]),
+             ("c.fna", 1, [("unplaced_scaffold_7 no entry in the map", c1), ("NC_C.1_2", c2)])]
+    names = str(tmp_path / "nameidmap.txt")
+    with open(names, "w") as nf:
+        nf.write("NC_A.1\t%d\nNC_B.1\t%d\nNC_C.1_2\t%d\n" % (t_a, t_a, t_b))        # (only a file's FIRST record names its genome)
+    paths = []
+    for fn, _, recs in files:
+        body = b""
+        for name, s in recs:
+            s = s if isinstance(s, bytes) else s.tobytes()
+            body += b">" + name.encode() + b"\n" + b"".join(s[j:j + 60] + b"\n" for j in range(0, len(s), 60))
+        p = str(tmp_path / fn)
+        (gzip.open(p, "wb") if fn.endswith(".gz") else open(p, "wb")).write(body)
+        paths.append(p)
+    out = str(tmp_path / "draft.db")
+    pr = subprocess.run([BIN, "build", "-k", str(k), "-T", nodes, "-M", names] + flags + [out, "unused"] + paths, stderr=subprocess.PIPE, timeout=300)
+    assert pr.returncode == 0, pr.stderr.decode()
+    d = hostio.read_db(out)
+    assert (d["k"], d["w"]) == (k, w) and d["gaps"].tolist() == [0] * 30
+    assert d["upper_bound"] == int(d["n_buckets"] * 0.77 + 0.5) and d["size"] <= d["upper_bound"]
+    assert d["n_buckets"] < 4 or int((d["n_buckets"] // 2) * 0.77 + 0.5) <= d["size"]      # as compact as khash grows it
+    canon = "-C" not in flags
+    exp_t = oracle.Table()
+    for _, tx, recs in files:
+        for _, s in recs:
+            s = s if isinstance(s, bytes) else s.tobytes()
+            if w > k:
+                oracle.lca_map_add_windowed(exp_t, wld.tax, k, w, score, s, tx, canon=canon)
+            else:
+                oracle.lca_map_add(exp_t, wld.tax, k, s, tx, canon=canon)
+    ek, ev = bc.table_pairs(exp_t)
+    exp = dict(zip(ek.tolist(), ev.tolist()))
+    i = np.arange(d["n_buckets"])
+    m = ((d["flags"][i >> 4] >> ((i & 15) << 1)) & 3) == 0
+    got = dict(zip(d["keys"][m].tolist(), d["vals"][m].tolist()))
+    assert got == exp
+    assert d["size"] == len(exp) and d["n_buckets"] == exp_t.n_buckets
+    assert {t_a, 1} <= set(exp.values()) and t_b not in exp.values()
+    # 33 bases, three keys: four buckets
+    tiny = str(tmp_path / "tiny.fna")
+    s33 = synth.rand_seq(rng, 33).tobytes()
+    open(tiny, "wb").write(b">NC_A.1\n" + s33 + b"\n")
+    out2 = str(tmp_path / "tiny.db")
+    pr = subprocess.run([BIN, "build", "-k", str(k), "-T", nodes, "-M", names] + (["-C"] if not canon else []) + [out2, "unused", tiny],
+                        stderr=subprocess.PIPE, timeout=300)
+    assert pr.returncode == 0, pr.stderr.decode()
+    d = hostio.read_db(out2)
+    assert (d["n_buckets"], d["size"], d["n_occupied"], d["upper_bound"]) == (4, 3, 3, 3) and d["flags"].size == 1
+    st = (int(d["flags"][0]) >> (2 * np.arange(16))) & 3
+    assert (st[4:] == 2).all() and int((st[:4] == 0).sum()) == 3
+    assert sorted(d["keys"][st[:4] == 0].tolist()) == np.unique(oracle.encode(s33, k, canon=canon)).tolist()
+    assert (d["vals"][st[:4] == 0] == t_a).all() and not d["keys"][st[:4] == 2].any()
+
+
 def test_cli_build_errors(tmp_path):
     p = subprocess.run([BIN, "build", "-k", "31", "out.db", "x", "nofile.fna"], stderr=subprocess.PIPE)
     assert p.returncode != 0 and b"seq2taxpath required" in p.stderr

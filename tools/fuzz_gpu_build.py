@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle_lib as O          # noqa: E402   (the checker)
 import synth                    # noqa: E402
+import build_cases as bc        # noqa: E402
 import bonsai_amd               # noqa: E402
 from test_gpu_build import device_build, present_pairs   # noqa: E402
 
@@ -63,23 +64,24 @@ while time.time() - t0 < budget:
     for s, g in zip(seqs, rgot):
         if not np.array_equal(g, O.rolling_hash(s, rk, rcanon, tabs, w=rw)):
             print("ROLLING MISMATCH seed", seed, "k", rk, "canon", rcanon, "w", rw, "len", len(s)); sys.exit(1)
-    # device build (optionally windowed) vs the oracle's sequential update_lca_map
-    if (canon or (windowed and not spaced)) and k >= 9 and score != 2:
-        wld = synth.make_world(O, seed=seed, k=k, genome_len=int(rng.choice([600, 2500])), gaps=gaps, canon=canon)
-        exp_t = O.Table()
-        for leaf, g in wld.genomes.items():
-            if windowed:
-                O.lca_map_add_windowed(exp_t, wld.tax, k, w, score, g.tobytes(), leaf, gaps=gaps, canon=canon)
-            else:
-                O.lca_map_add(exp_t, wld.tax, k, g.tobytes(), leaf, gaps=gaps, canon=canon)
-        ef, ek, ev = exp_t.arrays()
-        exp_keys, exp_vals = present_pairs(ef, ek, ev, exp_t.n_buckets)
-        ctx.load_taxonomy(wld.parent)
-        nb = 1 << 16
-        hdr, flags, keys, vals = device_build(ctx, list(wld.genomes.values()), list(wld.genomes.keys()), nb)
+    # device build (optionally windowed) vs the oracle's sequential update_lca_map: half of the time over the six genomes of
+    # synth.make_world, half over the world of the suite's edge tests (tests/build_cases.py) for this seed, comb and window
+    if canon or (windowed and not spaced):
+        case = bc.Case("fuzz", k, tuple(gaps) if gaps else None, w, score if windowed else 0, canon)
+        if rng.random() < 0.5:
+            bc._WORLDS.clear()
+            ew = bc.make_edge_world(O, seed, comb, w)
+            tax, parent, bseqs, btax = ew.tax, ew.parent, ew.seqs, ew.taxids
+        else:
+            wld = synth.make_world(O, seed=seed, k=k, genome_len=int(rng.choice([600, 2500])), gaps=gaps, canon=canon)
+            tax, parent, bseqs, btax = wld.tax, wld.parent, [g.tobytes() for g in wld.genomes.values()], list(wld.genomes.keys())
+        exp_keys, exp_vals = bc.table_pairs(bc.oracle_table(O, tax, case, bseqs, btax))
+        ctx.load_taxonomy(parent)
+        nb = max(1 << 10, bc.buckets_for(exp_keys.size))
+        hdr, flags, keys, vals = device_build(ctx, [np.frombuffer(b, dtype=np.uint8) for b in bseqs], btax, nb)
         gk, gv = present_pairs(flags, keys, vals, nb)
         if not (np.array_equal(gk, exp_keys) and np.array_equal(gv, exp_vals)):
-            print("BUILD MISMATCH seed", seed, "k", k, "w", w, "score", score, gk.size, exp_keys.size)
+            print("BUILD MISMATCH seed", seed, "k", k, "gaps", gaps, "canon", canon, "w", w, "score", score, "sequences", len(bseqs), gk.size, exp_keys.size)
             sys.exit(1)
     ctx.set_encoder(k, gaps, canonicalize=canon, spaced_intended=True)     # clears the window
     it += 1
