@@ -89,10 +89,12 @@ __global__ __launch_bounds__(256) void pack_kernel(const u8 *__restrict__ bases,
 // fetched.  A chunk = 64 words = 2048 bases = up to 8 passes of 256 bases (4 per lane); pass 0 of a unit's first
 // chunk is prefetched one unit ahead by the caller (raw_load) so its HBM latency hides behind the previous unit.
 // Requirement on the caller's buffer: `bases` 4-byte aligned and readable up to the next 4-byte boundary past its end.
+// ZEROED: lo and hi arrive as zeroes the caller has pinned in their registers (prefetch_clear), and only the loads are issued here.
+template <bool ZEROED = false>
 __device__ __forceinline__ void raw_load(const u8 *__restrict__ bases, u64 o, u32 L, u32 first_base, u32 &lo, u32 &hi)
 {
     const u32 bi = first_base + (u32)lane_id() * 4u;
-    lo = 0; hi = 0;
+    if (!ZEROED) { lo = 0; hi = 0; }
     if (bi < L) {
         const u64 addr = o + bi;
         const u32 mis = (u32)(addr & 3u);
@@ -176,11 +178,20 @@ __device__ __forceinline__ bool pack_chunk_lds(const u8 *__restrict__ bases, u64
 // What is in flight for the unit after the current one: ASCII: the first 256 bases (4 per lane); packed: the first 64 words and
 // their flag words.
 struct Prefetch { u32 lo, hi, m; };
+// A prefetch in two steps, so that a group of them (and a store) can be issued back to back: first every zero into its register,
+// then the loads.  A zero written BEHIND a load, into a register the compiler cannot prove free of an older load, costs a vmcnt(0)
+// -- a wait for whatever was issued just before it; in front of the group the same wait finds nothing outstanding.
 template <bool PACKED>
-__device__ __forceinline__ void prefetch_read(const ClassifyParams &p, u64 r, u64 o, u32 L, Prefetch &f)
+__device__ __forceinline__ void prefetch_clear(Prefetch &f)
 {
     f.lo = 0; f.hi = 0; f.m = 0;
-    if (!PACKED) { raw_load(p.bases, o, L, 0u, f.lo, f.hi); return; }
+    if (PACKED) asm volatile("" : "+v"(f.lo), "+v"(f.hi), "+v"(f.m));
+    else        asm volatile("" : "+v"(f.lo), "+v"(f.hi));
+}
+template <bool PACKED>
+__device__ __forceinline__ void prefetch_issue(const ClassifyParams &p, u64 r, u64 o, u32 L, Prefetch &f)
+{
+    if (!PACKED) { raw_load<true>(p.bases, o, L, 0u, f.lo, f.hi); return; }
     const u32 lane = (u32)lane_id();
     if (lane < ((L + 31u) >> 5)) {
         const u64 wi = (o >> 5) + r + lane;
@@ -877,13 +888,15 @@ __device__ __forceinline__ u32 resolve_regs(u32 ckey, u32 ccnt, u32 D, const Tax
 // ob = lane of offv that holds the unit's first offset (the caller keeps a whole chunk's offsets in one register pair)
 // STAGE3: keys / cnt lie directly behind the 16-bucket stage of aux (the PAIRS instantiations of classify_kernel), so the two-round
 // probe may stage 24 buckets while the counter has nothing in them.
-template <bool SPACED, int LAYOUT, int KT, int NM, int NB = 16, int SPAN = 8, bool OVC = false, bool WIDE = false, bool PACKED = false, bool STAGE3 = false>
+// issue_next: the caller's loads and stores that have nothing to do with this unit (classify_kernel: the next unit's prefetch and the
+// previous unit's record; it may read rec_out / rec_valid, which are written only at the end).  Called exactly once: directly behind
+// the unit's first pack -- whose wait for pre0 it would otherwise sit in front of -- or, by a unit that packs nothing, on its own.
+template <bool SPACED, int LAYOUT, int KT, int NM, int NB = 16, int SPAN = 8, bool OVC = false, bool WIDE = false, bool PACKED = false, bool STAGE3 = false, class IssueNext>
 __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u64 offv, u32 ob, bool have0, const Prefetch &pre0,
                                               u32 *keys, u32 *cnt, u32 *tin, u32 *tout, u32 cap, bool record_overflow, u32 *ring, u32 *aux, u64 *pk,
-                                              uint4 &rec_out, bool &rec_valid)
+                                              uint4 &rec_out, bool &rec_valid, IssueNext &&issue_next)
 {
     const int lane = lane_id();
-    rec_valid = false;
     const u32 rdesc = SPACED ? run_desc(p) : 0u;
     const u32 k = KT ? (u32)KT : p.k, c = KT ? (u32)KT : p.c;
     const u32 mlen = KT ? (u32)(KT - SPAN) : p.m;                 // (a compile-time k comes with its window: m = k - SPAN)
@@ -901,11 +914,12 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
     u32 n_mb = p.n_mb;
     asm volatile("" : "+s"(n_mb));
 
-    // the second mate's first 256 bases are asked for now and arrive while the first mate is classified (contiguous seeds: -2 %;
-    // the spaced instantiations have no registers to spare for it)
+    // the second mate's first 256 bases are asked for behind the first mate's first pack and arrive while the first mate is classified
+    // (contiguous seeds: -2 %; the spaced instantiations have no registers to spare for it)
     Prefetch pre1{0u, 0u, 0u};
     const bool have1 = !SPACED && NM == 2 && !OVC;            // (the k = 31 instantiations; the generic ones and the cooperative-overflow form have no registers to spare)
-    if (have1) prefetch_read<PACKED>(p, u * (u64)nm + 1u, readlane64(offv, (int)ob + 1), readlane((u32)offv, (int)ob + 2) - readlane((u32)offv, (int)ob + 1), pre1);
+    // (gfx9 counts loads and stores in one counter and retires them in order: issued in front of the unit's first pack, this load and
+    // the caller's issue_next are what the pack's wait for pre0 -- long arrived -- waits for)
 #ifdef BNS_PAD_UNIT                                             // marginal-cost experiments: N extra instructions per unit
     { u32 pv = (u32)lane; for (int q = 0; q < BNS_PAD_UNIT; ++q) asm volatile("v_mul_lo_u32 %0, %0, %0" : "+v"(pv)); asm volatile("" :: "v"(pv)); }
 #endif
@@ -936,14 +950,27 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
             if (!counter_insert(ckey, ccnt, dmask, keys, cnt, cap, D, t, c)) { overflow = true; break; }
         }
     };
+    // pack a chunk into the per-wave LDS image; is any base inside the read not A/C/G/T?  (wave-uniform)
+    auto pack = [&](int m, u32 L, u32 j0, bool have, const Prefetch &pre) __attribute__((always_inline)) -> bool {
+        return PACKED ? load_chunk_packed<!SPACED>(p, u * (u64)nm + (u64)m, readlane64(offv, (int)ob + m), L, j0, have, pre, pk)
+                      : pack_chunk_lds<!SPACED>(p.bases, offv, (int)ob + m, L, j0, have, pre.lo, pre.hi, pk);
+    };
+    auto n_kmers = [&](u32 L) -> u32 { return (L >= c && !(SPACED && p.emit_none)) ? L - c + 1u : 0u; };     // (emit_none: spaced seeds only)
+    // The unit's first pack -- mate 0, chunk 0, when it has one (not shorter than c, not empty, not emit_none) -- stands in front of the
+    // loops, and what is asked of memory for later goes out between it and them, on every path once.
+    bool clean0 = true;
+    {
+        const u32 L = readlane((u32)offv, (int)ob + 1) - readlane((u32)offv, (int)ob);
+        if (n_kmers(L)) clean0 = pack(0, L, 0u, have0, pre0);
+        if (have1) prefetch_clear<PACKED>(pre1);
+        issue_next();
+        if (have1) prefetch_issue<PACKED>(p, u * (u64)nm + 1u, readlane64(offv, (int)ob + 1), readlane((u32)offv, (int)ob + 2) - readlane((u32)offv, (int)ob + 1), pre1);
+    }
     for (int m = 0; m < nm; ++m) {
         const u32 L = readlane((u32)offv, (int)ob + m + 1) - readlane((u32)offv, (int)ob + m);     // (reads are < 4 GiB: the low words suffice)
-        const u32 nk = (L >= c && !(SPACED && p.emit_none)) ? L - c + 1u : 0u;     // (emit_none: spaced seeds only)
+        const u32 nk = n_kmers(L);
         for (u32 j0 = 0; j0 < nk; j0 += rounds_per_chunk * 64u) {
-            // pack the chunk into the per-wave LDS image; is any base inside the read not A/C/G/T?  (wave-uniform)
-            const bool have = (m == 0 ? have0 : have1) && j0 == 0;
-            const bool clean = PACKED ? load_chunk_packed<!SPACED>(p, u * (u64)nm + (u64)m, readlane64(offv, (int)ob + m), L, j0, have, m == 0 ? pre0 : pre1, pk)
-                                      : pack_chunk_lds<!SPACED>(p.bases, offv, (int)ob + m, L, j0, have, m == 0 ? pre0.lo : pre1.lo, m == 0 ? pre0.hi : pre1.hi, pk);
+            const bool clean = (m == 0 && j0 == 0u) ? clean0 : pack(m, L, j0, have1 && m != 0 && j0 == 0u, pre1);
             u64 W = 0; u32 M = 0xFFFFFFFFu;                        // register image: only the spaced paths use it
             if (SPACED) {
                 const u32 n_written = PACKED ? 64u : ((L - j0 >= 2048u ? 2048u : L - j0) + 255u) / 256u * 8u;    // words the passes wrote
@@ -1054,6 +1081,7 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
             u64 *ol = kp->ovf_list;
             if (ol) { const u32 slot = atomicAdd(oc, 1u); ol[slot] = u; }
         }
+        rec_valid = false;
         return;                                                // the overflow kernel recomputes this unit
     }
     u32 taxon;
@@ -1151,7 +1179,8 @@ __global__ __launch_bounds__(256, (LAYOUT == 1 && !SPACED) ? 7 : ClassifyCfg<SPA
     Prefetch pre;
     {
         const u64 o0 = readlane64(offs, 0);
-        prefetch_read<PACKED>(p, (u64)base * nm, o0, readlane((u32)offs, 1) - (u32)o0, pre);
+        prefetch_clear<PACKED>(pre);
+        prefetch_issue<PACKED>(p, (u64)base * nm, o0, readlane((u32)offs, 1) - (u32)o0, pre);
     }
     uint4 pend = make_uint4(0, 0, 0, 0);
     u32 pend_u = 0;
@@ -1167,20 +1196,32 @@ __global__ __launch_bounds__(256, (LAYOUT == 1 && !SPACED) ? 7 : ClassifyCfg<SPA
                 nbase = (u32)__builtin_amdgcn_readfirstlane((int)next_v);
                 if (nbase < n_units) noffs = load_offs(nbase);
             }
-            // first 256 bases of the unit after this one: the next of the chunk, or the first of the next chunk
-            Prefetch npre{0u, 0u, 0u};
-            if (j + 1u < cnt) {
-                const u64 n0 = readlane64(offs, (int)((j + 1u) * nm));
-                prefetch_read<PACKED>(p, (u64)(base + j + 1u) * nm, n0, readlane((u32)offs, (int)((j + 1u) * nm + 1u)) - (u32)n0, npre);
-            } else if (nbase < n_units) {
-                const u64 n0 = readlane64(noffs, 0);
-                prefetch_read<PACKED>(p, (u64)nbase * nm, n0, readlane((u32)noffs, 1) - (u32)n0, npre);
-            }
-            // The previous unit's record is stored HERE, next to the prefetch loads: gfx9 has one counter for loads and stores,
-            // so the first wait after a store waits for its acknowledgement too -- this way that is the first bucket fetch.
-            if (pend_valid && lane == 0) cold_params()->records[pend_u] = pend;
+            Prefetch npre;
+            // Issued by classify_unit behind the unit's first pack, so that the pack's wait for `pre` (here since the previous unit's
+            // last probe) is not a wait for these, and the first wait that covers them is the first bucket fetch's own:
+            auto issue_next = [&]() __attribute__((always_inline)) {
+                // first 256 bases of the unit after this one: the next of the chunk, or the first of the next chunk
+                // (one load site for both: two, merged behind the branches, come out as loads into different registers and a copy --
+                // with a vmcnt(0) in front of it)
+                prefetch_clear<PACKED>(npre);
+                u64 n0 = 0, nr = 0;
+                u32 nL = 0;                                          // (no unit after this one: a read of no bases loads nothing)
+                if (j + 1u < cnt) {
+                    n0 = readlane64(offs, (int)((j + 1u) * nm));
+                    nL = readlane((u32)offs, (int)((j + 1u) * nm + 1u)) - (u32)n0;
+                    nr = (u64)(base + j + 1u) * nm;
+                } else if (nbase < n_units) {
+                    n0 = readlane64(noffs, 0);
+                    nL = readlane((u32)noffs, 1) - (u32)n0;
+                    nr = (u64)nbase * nm;
+                }
+                prefetch_issue<PACKED>(p, nr, n0, nL, npre);
+                // The previous unit's record is stored next to the prefetch loads: gfx9 has one counter for loads and stores, so the
+                // first wait after a store waits for its acknowledgement too.
+                if (pend_valid && lane == 0) cold_params()->records[pend_u] = pend;
+            };
             classify_unit<SPACED, LAYOUT, KT, NM, NB, SPAN, OVC, WIDE, PACKED, STAGE3>(p, base + j, offs, j * nm, true, pre, ctr_keys, ctr_cnt, s_mh[wv] + MINB_LIST_U32,
-                                          s_mh[wv] + MINB_LIST_U32 + LDS_CAP, LDS_CAP, true, s_ring[wv], s_mh[wv], s_pk[wv], pend, pend_valid);
+                                          s_mh[wv] + MINB_LIST_U32 + LDS_CAP, LDS_CAP, true, s_ring[wv], s_mh[wv], s_pk[wv], pend, pend_valid, issue_next);
             pend_u = base + j;
             pre = npre;
         }
@@ -1208,7 +1249,7 @@ __global__ __launch_bounds__(64) void classify_overflow_kernel(ClassifyParams p,
         bool ok;
         const u64 offv = (threadIdx.x & 63u) == 0 ? b0 : ((threadIdx.x & 63u) == 1 ? bm : b1);
         classify_unit<SPACED, LAYOUT, 0, 0, 16, 8, false, WIDE, PACKED>(p, u, offv, 0u, false, Prefetch{0u, 0u, 0u}, scratch + b0, scratch + total_bases + b0,
-                                      scratch + 2 * total_bases + b0, scratch + 3 * total_bases + b0, (u32)(b1 - b0), false, s_ring, s_mh, s_pk, rec, ok);
+                                      scratch + 2 * total_bases + b0, scratch + 3 * total_bases + b0, (u32)(b1 - b0), false, s_ring, s_mh, s_pk, rec, ok, [] {});
         if (ok && threadIdx.x == 0) p.records[u] = rec;
     }
 }
