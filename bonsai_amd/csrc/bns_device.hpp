@@ -79,6 +79,15 @@ __device__ __forceinline__ u64 revcomp_top(u64 win, u32 k)
     return (((u64)hi << 32) | lo) & (~0ULL >> (64u - (k << 1)));
 }
 
+// The reverse complement of all 32 bases of `win`.  Its low 2k bits are revcomp_top(win, k); shifted right by 2 they are the reverse
+// complement of the k-mer that starts one base further on (k <= 31): one reversal serves two adjacent k-mers.
+__device__ __forceinline__ u64 revcomp64(u64 win)
+{
+    const u32 a = __builtin_bitreverse32((u32)(win >> 32)), b = __builtin_bitreverse32((u32)win);
+    const u32 lo = pairswap_not(a), hi = pairswap_not(b);
+    return ((u64)hi << 32) | lo;
+}
+
 __device__ __forceinline__ u64 canonical(u64 kmer, u32 k)
 {
     const u64 rc = revcomp(kmer, k);
@@ -621,8 +630,12 @@ __device__ __forceinline__ ProbeResult probe_minbucket(const MinBucket *__restri
 // of five, more than 24 in fewer than one out of 10^4 -- the third load, issued only when there are leaders for it, saves those
 // pairs their second pass.  (nb formed from the counter's size inside every pass instead -- no value of its own live through the
 // probe, four spilled SGPRs fewer -- measured slower: configs[1] -2.7 % instead of -3.3 %, 100-bp reads +1.9 % instead of +0.8 %.)
+// ADJ: the two halves are ADJACENT k-mers instead of consecutive rounds -- lane l holds positions 2 l (half A) and 2 l + 1 (half B)
+// of a double round of 128 (classify_unit).  Ranks stay "leaders before me in k-mer order"; only the lane mapping differs: half B's
+// predecessor is the lane's own half A, half A's is the previous lane's half B, and half A's ranks reach 126 (half B's 127, as
+// before), so both write the 64-entry list under rank < nb.
 constexpr int MINB_NB_WIDE = 24;
-template <bool KEY_MAY_BE_ONES = true, int NB = 16>
+template <bool KEY_MAY_BE_ONES = true, int NB = 16, bool ADJ = false>
 __device__ __forceinline__ void probe_minbucket2(const MinBucket *__restrict__ buckets, u64 keyA, u32 bA, bool activeA, u64 keyB, u32 bB,
                                                  bool activeB, u32 *aux, const Slot *__restrict__ ovf_slots, u64 ovf_mask,
                                                  ProbeResult &ra, ProbeResult &rb, u32 nb = 16u)
@@ -670,14 +683,23 @@ __device__ __forceinline__ void probe_minbucket2(const MinBucket *__restrict__ b
     u32 why_later = 4u;
 #endif
     auto pass = [&](auto first_tag) -> bool {
-        // run leaders over the 128 positions: half B's lane 0 continues half A's lane 63
-        const u32 a63 = readlane(bktA, 63);
-        const u32 prevA = (u32)__builtin_amdgcn_update_dpp((int)~bktA, (int)bktA, DPP_WAVE_SHR1, 0xf, 0xf, false);
-        const u32 prevB = (u32)__builtin_amdgcn_update_dpp((int)a63, (int)bktB, DPP_WAVE_SHR1, 0xf, 0xf, false);
-        const bool pendA = bktA != MINB_NONE, chgA = bktA != prevA, pendB = bktB != MINB_NONE, chgB = bktB != prevB;
-        const u64 leadA = ballot64(pendA) & ballot64(chgA), leadB = ballot64(pendB) & ballot64(chgB);
+        bool pendA, chgA, pendB, chgB;
+        u64 leadA, leadB;
+        u32 nA;
+        if constexpr (ADJ) {
+            // run leaders in position order: 2 l - 1 is the previous lane's half B (lane 0 sees ~bktA, which always differs)
+            const u32 prevA = (u32)__builtin_amdgcn_update_dpp((int)~bktA, (int)bktB, DPP_WAVE_SHR1, 0xf, 0xf, false);
+            pendA = bktA != MINB_NONE; chgA = bktA != prevA; pendB = bktB != MINB_NONE; chgB = bktB != bktA;
+        } else {
+            // run leaders over the 128 positions: half B's lane 0 continues half A's lane 63
+            const u32 a63 = readlane(bktA, 63);
+            const u32 prevA = (u32)__builtin_amdgcn_update_dpp((int)~bktA, (int)bktA, DPP_WAVE_SHR1, 0xf, 0xf, false);
+            const u32 prevB = (u32)__builtin_amdgcn_update_dpp((int)a63, (int)bktB, DPP_WAVE_SHR1, 0xf, 0xf, false);
+            pendA = bktA != MINB_NONE; chgA = bktA != prevA; pendB = bktB != MINB_NONE; chgB = bktB != prevB;
+        }
+        leadA = ballot64(pendA) & ballot64(chgA); leadB = ballot64(pendB) & ballot64(chgB);
         if (!(leadA | leadB)) return false;
-        const u32 nA = (u32)__popcll(leadA);
+        nA = (u32)__popcll(leadA);
         const int n_lead = (int)nA + __popcll(leadB);
 #ifdef BNS_COUNT_FETCHES
         if (lane == 0) {
@@ -686,10 +708,20 @@ __device__ __forceinline__ void probe_minbucket2(const MinBucket *__restrict__ b
             if (!decltype(first_tag)::value) atomicAdd(&g_fetch_count[why_later], 1ULL);
         }
 #endif
-        const u32 rankA = __builtin_amdgcn_mbcnt_hi((u32)(leadA >> 33), __builtin_amdgcn_mbcnt_lo((u32)(leadA >> 1), (u32)(leadA & 1ULL) - 1u));
-        const u32 rankB = __builtin_amdgcn_mbcnt_hi((u32)(leadB >> 33), __builtin_amdgcn_mbcnt_lo((u32)(leadB >> 1), nA + (u32)(leadB & 1ULL) - 1u));
-        // (the list has 64 entries: half A's ranks are below 64, half B's reach 127 -- and only the first nb are fetched)
-        if (pendA & chgA) list[rankA] = bktA;
+        u32 rankA, rankB;
+        if constexpr (ADJ) {
+            // half A: the leaders at positions <= 2 l, less one = half A's up to and including this lane and half B's below it;
+            // half B: the same plus its own leader bit
+            const u32 upA = __builtin_amdgcn_mbcnt_hi((u32)(leadA >> 33), __builtin_amdgcn_mbcnt_lo((u32)(leadA >> 1), (u32)(leadA & 1ULL) - 1u));
+            rankA = __builtin_amdgcn_mbcnt_hi((u32)(leadB >> 32), __builtin_amdgcn_mbcnt_lo((u32)leadB, upA));
+            rankB = rankA + ((pendB & chgB) ? 1u : 0u);
+        } else {
+            rankA = __builtin_amdgcn_mbcnt_hi((u32)(leadA >> 33), __builtin_amdgcn_mbcnt_lo((u32)(leadA >> 1), (u32)(leadA & 1ULL) - 1u));
+            rankB = __builtin_amdgcn_mbcnt_hi((u32)(leadB >> 33), __builtin_amdgcn_mbcnt_lo((u32)(leadB >> 1), nA + (u32)(leadB & 1ULL) - 1u));
+        }
+        // (the list has 64 entries and only the first nb are fetched.  Rounds in lanes l / l: half A's ranks are below 64, half B's reach
+        // 127.  ADJ: half A's reach 126, half B's 127 -- both are written under rank < nb)
+        if ((pendA & chgA) && (!ADJ || rankA < nb)) list[rankA] = bktA;
         if ((pendB & chgB) && rankB < nb) list[rankB] = bktB;
         __builtin_amdgcn_wave_barrier();
         {

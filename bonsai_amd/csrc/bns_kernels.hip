@@ -245,9 +245,9 @@ __device__ __forceinline__ bool load_chunk_packed(const ClassifyParams &p, u64 r
 // b = 64 rd + lane is taken from the three dwords that begin with the one holding base b - 1 (the lead dword for b = 0), so the
 // shift n = 30 - 2 ((b + 15) & 15) is never 32: hi:lo = two v_alignbit_b32, full rate.  Dword index and shift are lane constants
 // (64 rd is a multiple of 16).
-__device__ __forceinline__ void extract_lds32(const u64 *pk, u32 rd, u32 k, bool clean, u64 &win, bool &valid)
+// (lane: the lane id, handed in by a caller that does not want the lane constants formed here kept in registers across its loop)
+__device__ __forceinline__ void extract_lds32(const u64 *pk, u32 rd, u32 k, bool clean, u64 &win, bool &valid, u32 lane = (u32)lane_id())
 {
-    const u32 lane = (u32)lane_id();
     const u32 *img = reinterpret_cast<const u32 *>(pk);
     const u32 g = 4u * rd + ((lane + 15u) >> 4), n = 30u - 2u * ((lane + 15u) & 15u);
     const u32 w0 = img[g], w1 = img[g + 1u], w2 = img[g + 2u];
@@ -317,9 +317,8 @@ __device__ __forceinline__ u32 row_suffix_min(u32 x)
 }
 // head = round 0 only, lanes 0 .. 14: the hash of the FIRST m-mer of k-mers 0 .. 14 (positions 0 .. 14); mine = the hash of the
 // lane's own m-mer (position 15 + lane).  ring: 15 + 64 entries.
-__device__ __forceinline__ u32 window16_min(u32 mine, u32 head, u32 rd, u32 *ring)
+__device__ __forceinline__ u32 window16_min(u32 mine, u32 head, u32 rd, u32 *ring, u32 lane = (u32)lane_id())
 {
-    const u32 lane = (u32)lane_id();
     if (rd == 0) {
         asm volatile("");                                     // (keeps this a scalar branch: see round_minhash)
         const u32 sh = row_suffix_min(lane < 15u ? head : 0xFFFFFFFFu);
@@ -334,6 +333,131 @@ __device__ __forceinline__ u32 window16_min(u32 mine, u32 head, u32 rd, u32 *rin
     return min(P, sprev);
 }
 
+// ---- two adjacent k-mers per lane (classify_unit's double round: lane l holds k-mers 2 l and 2 l + 1 of 128) ----------------
+// The window of the double round that starts at base b0 = 128 q of the chunk: the 32 bases from b0 + 2 lane on, extract_lds32's scheme
+// at that base (dword (b + 15) >> 4, shift 30 - 2 ((b + 15) & 15): 2 lane + 15 is odd, so the shift is one of 28, 24 .. 0).  The top
+// 2k bits are k-mer 2 l, the 2k bits below the first base k-mer 2 l + 1 (k <= 31).  The furthest dword read, 8 q + 10, is the one lane
+// 63 of round 2 q + 1 reads in extract_lds32.  okA / okB: no N in the k-mer, from ONE window of the N image (not read when the
+// chunk is clean).
+__device__ __forceinline__ void extract_lds32_adj(const u64 *pk, u32 q, u32 k, bool clean, u64 &win, bool &okA, bool &okB)
+{
+    const u32 lane = (u32)lane_id();
+    const u32 *img = reinterpret_cast<const u32 *>(pk);
+    const u32 g = 8u * q + ((2u * lane + 15u) >> 4), n = 30u - 2u * ((2u * lane + 15u) & 15u);
+    const u32 w0 = img[g], w1 = img[g + 1u], w2 = img[g + 2u];
+    win = ((u64)__builtin_amdgcn_alignbit(w0, w1, n) << 32) | __builtin_amdgcn_alignbit(w1, w2, n);
+    okA = true; okB = true;
+    if (!clean) {
+        const u32 m0 = img[IMG_N32 + g], m1 = img[IMG_N32 + g + 1u], m2 = img[IMG_N32 + g + 2u];
+        const u64 mw = ((u64)__builtin_amdgcn_alignbit(m0, m1, n) << 32) | __builtin_amdgcn_alignbit(m1, m2, n);
+        okA = (mw >> (64u - 2u * k)) == 0;
+        okB = ((mw << 2) >> (64u - 2u * k)) == 0;
+    }
+}
+
+// Inclusive prefix / suffix minima inside blocks of 8 lanes, DPP only: two quad_perm steps in which lanes without a source read
+// themselves, then the lower (upper) quad's total into the upper (lower) quad of its block: row_shr:4 under bank mask 0b1010
+// (row_shl:4 under 0b0101), the other quads keeping what they have.  (quad_perm gives every lane a source: dpp<>, which needs no
+// value for the others, leaves the compiler no register to preset.)
+__device__ __forceinline__ u32 blk8_prefix_min(u32 x)
+{
+    x = min(x, dpp<0x90>(x));                                 // quad_perm:[0,0,1,2]
+    x = min(x, dpp<0x44>(x));                                 // quad_perm:[0,1,0,1]
+    const u32 t = dpp<0xFF>(x);                               // quad_perm:[3,3,3,3]: the quad's total
+    return min(x, (u32)__builtin_amdgcn_update_dpp(-1, (int)t, 0x114, 0xf, 0xa, false));  // row_shr:4
+}
+__device__ __forceinline__ u32 blk8_suffix_min(u32 x)
+{
+    x = min(x, dpp<0xF9>(x));                                 // quad_perm:[1,2,3,3]
+    x = min(x, dpp<0xEE>(x));                                 // quad_perm:[2,3,2,3]
+    const u32 t = dpp<0x00>(x);                               // quad_perm:[0,0,0,0]
+    return min(x, (u32)__builtin_amdgcn_update_dpp(-1, (int)t, 0x104, 0xf, 0x5, false));  // row_shl:4
+}
+// The exclusive forms of the two from the inclusive ones: the neighbour's value (row_shr:1 / row_shl:1), and the identity in the
+// lanes that start / end a block, picked by a constant lane mask (set in vcc inside the statement: no SGPR pair held across the
+// round).  Half of those lanes start / end a row and have no neighbour: dpp<> reads 0 there, which the mask replaces as well.
+__device__ __forceinline__ u32 blk8_exclusive(u32 inc, bool prefix)
+{
+    u32 r;
+    if (prefix) {
+        const u32 t = dpp<0x111>(inc);
+        asm("s_mov_b32 vcc_lo, 0x01010101\n\ts_mov_b32 vcc_hi, 0x01010101\n\tv_cndmask_b32_e64 %0, %1, -1, vcc" : "=v"(r) : "v"(t) : "vcc");
+    } else {
+        const u32 t = dpp<0x101>(inc);
+        asm("s_mov_b32 vcc_lo, 0x80808080\n\ts_mov_b32 vcc_hi, 0x80808080\n\tv_cndmask_b32_e64 %0, %1, -1, vcc" : "=v"(r) : "v"(t) : "vcc");
+    }
+    return r;
+}
+
+// The 16-entry windows of BOTH k-mers of a lane in one pass (k - m = 15).  Positions are those of the double round's m-mers: k-mer j
+// owns j .. j + 15.  h0 / h1 = the hashes of the lane's own last m-mers, positions 2 l + 15 and 2 l + 16; pm = min(h0, h1) is one
+// lane's pair, and 16 positions are 8 lanes: van Herk / Gil-Werman over blocks of 8 lanes, P / S = inclusive prefix / suffix minima
+// of pm inside the lane's block, Pex / Sex the exclusive ones.
+//   k-mer 2 l + 1: positions 2 l + 1 .. 2 l + 16 = the pairs of lanes l - 7 .. l              = min(S[l - 7], P[l])
+//   k-mer 2 l:     positions 2 l .. 2 l + 15     = h1[l - 8], the pairs of l - 7 .. l - 1, h0[l] = min3(min(h1, Sex)[l - 8], Pex[l], h0[l])
+// The two values from lanes l - 8 and l - 7 go through the ring: entries 2 (v + 8), 2 (v + 8) + 1 hold X = min(h1, Sex) and S of lane
+// v, one 8-byte write and one ds_read2_b32 per lane.  Lanes -8 .. -1 are the head: positions 0 .. 14, the FIRST m-mers of k-mers
+// 0 .. 14, which lanes 0 .. 7 hold (g0 = position 2 l, g1 = position 2 l + 1; lane l stands for v = l - 8).  There X[v] = positions
+// 2 l .. 14 and S[v] = positions 2 l - 1 .. 14.  Position 15 (lane 7's g1) may be taken into both -- every window that reads a head
+// entry holds it -- so X is the plain suffix minimum of min(g0, g1) and S adds the lower neighbour's g1 (lane 0 has none and reads
+// 0: entry 1, S of lane -8, is the one nobody reads).  Every lane writes its head pair first and its own pair 16 entries on second
+// (a wave's LDS operations retire in order), so entries 0 .. 15 keep the head and nothing is predicated.
+// Every double round computes its own head: no carry in the ring between rounds.  ring: 16 + 128 entries.
+__device__ __forceinline__ void window16_min2(u32 h0, u32 h1, u32 g0, u32 g1, u32 *ring, u32 &wA, u32 &wB)
+{
+    const u32 lane = (u32)lane_id();
+    uint2 *ring2 = reinterpret_cast<uint2 *>(ring);
+    const u32 Xv = blk8_suffix_min(min(g0, g1));
+    ring2[lane] = make_uint2(Xv, min(Xv, dpp<0x111>(g1)));
+    __builtin_amdgcn_wave_barrier();
+    const u32 pm = min(h0, h1);
+    const u32 P = blk8_prefix_min(pm), S = blk8_suffix_min(pm);
+    ring2[8u + lane] = make_uint2(min(h1, blk8_exclusive(S, false)), S);
+    __builtin_amdgcn_wave_barrier();
+    const u32 xin = ring[2u * lane], sin = ring[2u * lane + 3u];
+    __builtin_amdgcn_wave_barrier();
+    wA = min(min(xin, blk8_exclusive(P, true)), h0);
+    wB = min(sin, P);
+}
+
+// Minimizer hashes of the two adjacent k-mers of a lane (k-mer 2 l: kfA / rcA, k-mer 2 l + 1: kfB / rcB; contiguous seeds, k <= 31):
+// round_minhash for the double round.  The ring is indexed by m-mer position and every double round fills it afresh: the lane's FIRST
+// m-mers are positions 2 l and 2 l + 1, its last ones 2 l + span and 2 l + span + 1, so positions 0 .. 127 + span are all written (a
+// position written twice gets the same hash twice).  Of the span + 2 positions of its two windows the lane holds four itself; it reads
+// the others, 2 l + 2 .. 2 l + span - 1, as 8-byte pairs (lane-consecutive: no bank conflict; an odd span's last pair ends on 2 l + span,
+// the lane's own h0 once more), and the span positions the two windows share are reduced once.  A window of 3 m-mers reads nothing.
+// SPAN == 15: window16_min2.
+template <int SPAN>
+__device__ __forceinline__ void round2_minhash(u64 kfA, u64 rcA, u64 kfB, u64 rcB, u32 m, u32 *ring, u32 &hA, u32 &hB)
+{
+    static_assert(SPAN >= 2, "a window of at least three m-mers");
+    const u32 lane = (u32)lane_id();
+    const u64 mmask = ~0ULL >> (64u - 2u * m);
+    auto canon_hash = [&](u64 a, u64 b) -> u32 {                // (a, b: an m-mer and its reverse complement, 2m bits each)
+        if (m <= 16u) return mmer_mix(min((u32)a, (u32)b));
+        return mmer_hash(a < b ? a : b);
+    };
+    const u32 g0 = canon_hash(kfA >> (2u * SPAN), rcA & mmask), g1 = canon_hash(kfB >> (2u * SPAN), rcB & mmask);
+    const u32 h0 = canon_hash(kfA & mmask, rcA >> (2u * SPAN)), h1 = canon_hash(kfB & mmask, rcB >> (2u * SPAN));
+    if (SPAN == 15) { window16_min2(h0, h1, g0, g1, ring, hA, hB); return; }
+    u32 c = min(g1, h0);                                         // positions 2 l + 1 .. 2 l + span: both windows have them
+    constexpr u32 NP = ((u32)SPAN - 1u) / 2u;                    // pairs to read: positions 2 l + 2 .. 2 l + 1 + 2 NP
+    if (NP) {
+        uint2 *ring2 = reinterpret_cast<uint2 *>(ring);
+        ring2[lane] = make_uint2(g0, g1);
+        ring[2u * lane + (u32)SPAN] = h0; ring[2u * lane + (u32)SPAN + 1u] = h1;
+        __builtin_amdgcn_wave_barrier();
+        uint2 h[NP ? NP : 1u];
+#pragma unroll
+        for (u32 i = 0; i < NP; ++i) h[i] = ring2[lane + 1u + i];
+#pragma unroll
+        for (u32 i = 0; i < NP; ++i) c = min(min(c, h[i].x), h[i].y);
+        __builtin_amdgcn_wave_barrier();
+    }
+    hA = min(c, g0);
+    hB = min(c, h1);
+}
+
 // Minimizer hash of every k-mer of round rd (contiguous seeds).  The m-mers of k-mer j sit at positions j..j+span
 // (span = k-m).  Each lane hashes only the LAST m-mer of its own forward k-mer (position lane+span; its reverse
 // complement is the top of the k-mer's reverse complement, so no extra bit reversal), the first `span` positions of a
@@ -342,9 +466,9 @@ __device__ __forceinline__ u32 window16_min(u32 mine, u32 head, u32 rd, u32 *rin
 // complement coincide.  Garbage from N / past-the-end positions only reaches k-mers that are invalid anyway.
 // W = entries of the unrolled window: span + 1 when the span is a compile-time constant, BNS_MAX_SPAN + 1 (tail masked) otherwise.
 template <int W, bool VH = false>
-__device__ __forceinline__ u32 round_minhash(u64 kf, u64 rc, u32 rd, u32 k, u32 m, u32 *ring)
+__device__ __forceinline__ u32 round_minhash(u64 kf, u64 rc, u32 rd, u32 k, u32 m, u32 *ring, u32 lane_ = (u32)lane_id())
 {
-    const int lane = lane_id();
+    const int lane = (int)lane_;
     const u32 span = k - m;
     const u64 mmask = ~0ULL >> (64u - 2u * m);
     if (span == 0) { const u64 a = kf & mmask, b = rc & mmask; return mmer_hash(a < b ? a : b); }
@@ -360,7 +484,7 @@ __device__ __forceinline__ u32 round_minhash(u64 kf, u64 rc, u32 rd, u32 k, u32 
             const u64 a = kf & mmask, b = rc >> 30;
             mine = mmer_hash(a < b ? a : b);
         }
-        return window16_min(mine, head, rd, ring);
+        return window16_min(mine, head, rd, ring, lane_);
     }
     if (m <= 16u) {
         // m-mers that fit a word: the canonical m-mer is a v_min_u32 of two words (the low word of the k-mer, the top of its
@@ -891,6 +1015,12 @@ __device__ __forceinline__ u32 resolve_regs(u32 ckey, u32 ccnt, u32 D, const Tax
 // issue_next: the caller's loads and stores that have nothing to do with this unit (classify_kernel: the next unit's prefetch and the
 // previous unit's record; it may read rec_out / rec_valid, which are written only at the end).  Called exactly once: directly behind
 // the unit's first pack -- whose wait for pre0 it would otherwise sit in front of -- or, by a unit that packs nothing, on its own.
+// Which of the forms that probe two rounds at a time (PAIRS) take them as double rounds of adjacent k-mers.  k = 32 cannot: two
+// 32-mers are 33 bases.
+constexpr bool adjacent_kmers(int kt, int span) { return kt != 0 && kt <= 31 && span >= 2; }
+// u32 entries of the minimizer ring per wave: 64 + window - 1 <= 79 hashes round by round, 128 + span + 1 <= 144 for a double round
+// (SPAN == 15: 16 + 128), 64-bit identities for a table with the wide minimizer identity
+constexpr int ring_u32(bool wide, bool adj) { return wide ? 160 : (adj ? 144 : 96); }
 template <bool SPACED, int LAYOUT, int KT, int NM, int NB = 16, int SPAN = 8, bool OVC = false, bool WIDE = false, bool PACKED = false, bool STAGE3 = false, class IssueNext>
 __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u64 offv, u32 ob, bool have0, const Prefetch &pre0,
                                               u32 *keys, u32 *cnt, u32 *tin, u32 *tout, u32 cap, bool record_overflow, u32 *ring, u32 *aux, u64 *pk,
@@ -926,6 +1056,9 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
     // Contiguous seeds on the minbucket layout with a compile-time k (the usual form: no tags, no wide identity) go through the probe
     // two rounds at a time (probe_minbucket2): one probe pass and one vote for the 120 k-mers of a 150-bp read instead of two.
     constexpr bool PAIRS = !SPACED && LAYOUT == 2 && KT != 0 && !OVC && !WIDE;
+    // ... and, where two k-mers fit one 64-bit window (k <= 31), as DOUBLE rounds: lane l takes the adjacent k-mers 2 l and 2 l + 1 of 128
+    // from one window and one reverse complement instead of k-mers l and l + 64 from two (adjacent_kmers(): the forms that take it)
+    constexpr bool ADJ = PAIRS && adjacent_kmers(KT, SPAN);
     // a round's found / valid lanes into missing, n_hits and the hit stream (k-mer order); returns the found mask
     auto tally = [&](const ProbeResult &pr, bool valid) -> u64 {
         const u64 fm = ballot64(pr.found), vm = ballot64(valid);
@@ -941,6 +1074,32 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
         while (ra | rb) {
             const bool inA = ra != 0ULL;
             const int l = __builtin_ctzll(inA ? ra : rb);
+            const u32 t = readlane(inA ? va : vb, l);
+            const u64 ma = ballot64(va == t) & ra, mb = ballot64(vb == t) & rb;
+            ra &= ~ma; rb &= ~mb;
+            const u32 c = (u32)(__popcll(ma) + __popcll(mb));
+            const bool eq = ckey == t;
+            if (ballot64(eq) & dmask) { ccnt = eq ? ccnt + c : ccnt; continue; }
+            if (!counter_insert(ckey, ccnt, dmask, keys, cnt, cap, D, t, c)) { overflow = true; break; }
+        }
+    };
+    // The same two for a double round, whose k-mer order is lane l's half A, lane l's half B, lane l + 1's half A ...
+    auto tally_adj = [&](const ProbeResult &pa, bool vA, const ProbeResult &pb, bool vB, u64 &fa, u64 &fb) {
+        fa = ballot64(pa.found); fb = ballot64(pb.found);
+        missing += (u32)(__popcll(ballot64(vA) & ~fa) + __popcll(ballot64(vB) & ~fb));
+        if (want_hits && (pa.found || pb.found)) {
+            u32 *hp = cold_params()->hits + (readlane64(offv, (int)ob) + n_hits + (u32)(__popcll(fa & lanemask_lt()) + __popcll(fb & lanemask_lt())));
+            if (pa.found) hp[0] = pa.val;
+            if (pb.found) hp[pa.found ? 1 : 0] = pb.val;
+        }
+        n_hits += (u32)(__popcll(fa) + __popcll(fb));
+    };
+    // (the next taxon is the one at the lowest remaining position: the serial insertion order)
+    auto vote_adj = [&](u64 fa, u32 va, u64 fb, u32 vb) {
+        u64 ra = fa, rb = fb;
+        while (ra | rb) {
+            const int l = __builtin_ctzll(ra | rb);
+            const bool inA = ((ra >> l) & 1ULL) != 0ULL;
             const u32 t = readlane(inA ? va : vb, l);
             const u64 ma = ballot64(va == t) & ra, mb = ballot64(vb == t) & rb;
             ra &= ~ma; rb &= ~mb;
@@ -983,12 +1142,49 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
                 auto key_round = [&](u32 rd, u64 &key, u32 &bkt) -> bool {
                     u64 win = 0;
                     bool valid;
-                    extract_lds32(pk, rd, k, clean, win, valid);
+                    // (ADJ: the single round is a chunk's last, taken by k-mer counts of 128 q + 1 .. 64 only: its lane constants -- window
+                    // dword and shift, ring addresses -- are formed in it, not kept in registers beside the double round's, which
+                    // cost these forms 12 bytes of scratch)
+                    u32 lq = (u32)lane;
+                    if (ADJ) asm volatile("" : "+v"(lq));
+                    extract_lds32(pk, rd, k, clean, win, valid, lq);
                     const u64 kf = win >> (64u - 2u * k), krc = revcomp_top(win, k);
                     key = kf < krc ? kf : krc;
-                    bkt = bucket_of(round_minhash<MW, SPAN == 15>(kf, krc, rd, k, mlen, ring), n_mb);
-                    return valid && rd * 64u + (u32)lane < chunk_nk;
+                    // (ADJ: no double round leaves a carry in the ring: round 0's head path)
+                    bkt = bucket_of(round_minhash<MW, SPAN == 15>(kf, krc, ADJ ? 0u : rd, k, mlen, ring, lq), n_mb);
+                    return valid && rd * 64u + lq < chunk_nk;
                 };
+                if constexpr (ADJ) {
+                    for (u32 rd = 0; rd * 64u < chunk_nk; rd += 2u) {
+                        if ((rd + 1u) * 64u < chunk_nk) {             // (wave-uniform) more than 64 k-mers left: a double round
+                            u64 win;
+                            bool okA, okB;
+                            extract_lds32_adj(pk, rd >> 1, k, clean, win, okA, okB);
+                            const u64 kmask = ~0ULL >> (64u - 2u * k);
+                            const u64 rcw = revcomp64(win);
+                            const u64 kfA = win >> (64u - 2u * k), kfB = (win << 2) >> (64u - 2u * k);
+                            const u64 rcA = rcw & kmask, rcB = (rcw >> 2) & kmask;
+                            const u64 keyA = kfA < rcA ? kfA : rcA, keyB = kfB < rcB ? kfB : rcB;
+                            u32 hA, hB;
+                            round2_minhash<SPAN>(kfA, rcA, kfB, rcB, mlen, ring, hA, hB);
+                            const u32 left = chunk_nk - rd * 64u;             // (more than 64)
+                            const bool vA = okA && 2u * (u32)lane < left, vB = okB && 2u * (u32)lane < left - 1u;
+                            ProbeResult pa, pb;
+                            probe_minbucket2<false, NB, true>(p.minb, keyA, bucket_of(hA, n_mb), vA, keyB, bucket_of(hB, n_mb), vB, aux, p.slots, p.ovf_mask,
+                                                              pa, pb, (STAGE3 && D <= 64u) ? (u32)MINB_NB_WIDE : 16u);
+                            u64 fa, fb;
+                            tally_adj(pa, vA, pb, vB, fa, fb);
+                            vote_adj(fa, pa.val, fb, pb.val);
+                        } else {                                          // at most 64 left: the one-round probe
+                            u64 keyA;
+                            u32 bA;
+                            const bool vA = key_round(rd, keyA, bA);
+                            const ProbeResult pa = probe_minbucket<false, NB>(p.minb, keyA, bA, vA, aux, p.slots, p.ovf_mask);
+                            vote2(tally(pa, vA), pa.val, 0ULL, 0u);
+                        }
+                    }
+                    continue;
+                }
                 for (u32 rd = 0; rd * 64u < chunk_nk; rd += 2u) {
                     u64 keyA;
                     u32 bA;
@@ -1131,11 +1327,12 @@ __global__ __launch_bounds__(256, (LAYOUT == 1 && !SPACED) ? 7 : ClassifyCfg<SPA
     constexpr bool STAGE3 = PAIRS && !(NM == 2 && !PACKED);
     static_assert(!PAIRS || (NB == 16 && minb_aux_u32(MINB_NB_WIDE) == minb_aux_u32(16) + 2 * (int)LDS_CAP), "the counter is the stage's third KiB");
     // per wave: counter keys/counts (1 KB), minimizer ring + bucket list + bucket stage (3.1 KB; the stage doubles as the
-    // tin/tout scratch of resolve_wave -- its first KiB -- which runs when no probe is in flight), packed chunk image (1 KB): 19.8 KB / block
+    // tin/tout scratch of resolve_wave -- its first KiB -- which runs when no probe is in flight), packed chunk image (1 KB): 18.6 KB / block (19 008 B;
+    // 19 776 B with the double round's ring, 20 032 B with the wide identity's: eight blocks per CU -- 20 480 B each -- in every case)
     // (ring, list + stage and chunk image are separate arrays: the stage is written by the fetch itself (LDS DMA), and the compiler
     // puts a vmcnt wait in front of any LDS access it cannot tell apart from it)
-    // (the ring holds 64 + window - 1 <= 79 entries: 32-bit hashes, or 64-bit identities for a table with the wide minimizer identity)
-    __shared__ __attribute__((aligned(8))) u32 s_ring[4][WIDE ? 160 : 96];
+    // (ring_u32: 64 + window - 1 <= 79 32-bit hashes round by round, 128 + 16 for a double round, 64-bit identities for the wide identity)
+    __shared__ __attribute__((aligned(8))) u32 s_ring[4][ring_u32(WIDE, PAIRS && adjacent_kmers(KT, SPAN))];
     __shared__ __attribute__((aligned(16))) u32 s_mh[4][AUX_U32];
     __shared__ u64 s_pk[4][IMG_U64];
     static_assert(AUX_U32 - MINB_LIST_U32 >= 2 * (int)LDS_CAP, "stage must hold tin/tout");
