@@ -1008,24 +1008,92 @@ __device__ __forceinline__ u32 resolve_regs(u32 ckey, u32 ccnt, u32 D, const Tax
 // KT > 0 fixes k at compile time (contiguous seeds only): shift counts, masks and the minimizer span become immediates,
 // which also frees the SGPRs those loop-invariant values would occupy.  KT == 0 reads k from the arguments.
 // NM > 0 fixes the number of mates per unit the same way (1 = single-end: no mate loop, no third offset).
-// offv = offsets of the unit's reads, one per lane (lanes 0..nmates); (have0, r_lo, r_hi) = prefetched pass 0 of mate 0.
-// ob = lane of offv that holds the unit's first offset (the caller keeps a whole chunk's offsets in one register pair)
-// STAGE3: keys / cnt lie directly behind the 16-bucket stage of aux (the PAIRS instantiations of classify_kernel), so the two-round
-// probe may stage 24 buckets while the counter has nothing in them.
-// issue_next: the caller's loads and stores that have nothing to do with this unit (classify_kernel: the next unit's prefetch and the
-// previous unit's record; it may read rec_out / rec_valid, which are written only at the end).  Called exactly once: directly behind
-// the unit's first pack -- whose wait for pre0 it would otherwise sit in front of -- or, by a unit that packs nothing, on its own.
+#ifndef BNS_WAVES_PER_SIMD
+#define BNS_WAVES_PER_SIMD 8
+#endif
+// Spaced seeds have no minimizer locality (every lookup its own bucket), so their rounds are bound by the random-gather rate
+// of the memory system (41 G fetches/s reached, 44 G/s is the part's ceiling); a 32-bucket stage at 6 waves/SIMD measured
+// 6 % faster than 16 buckets at 8 (two passes per round instead of four), a 64-bucket stage at 3-4 waves 9 % slower.
+#ifndef BNS_SPACED_NB
+#define BNS_SPACED_NB 32         // buckets staged per probe pass for spaced seeds (16 / 32 / 64)
+#endif
+#ifndef BNS_SPACED_WAVES
+#define BNS_SPACED_WAVES 6       // waves per SIMD the spaced instantiations are compiled for
+#endif
 // Which of the forms that probe two rounds at a time (PAIRS) take them as double rounds of adjacent k-mers.  k = 32 cannot: two
 // 32-mers are 33 bases.
 constexpr bool adjacent_kmers(int kt, int span) { return kt != 0 && kt <= 31 && span >= 2; }
-// u32 entries of the minimizer ring per wave: 64 + window - 1 <= 79 hashes round by round, 128 + span + 1 <= 144 for a double round
-// (SPAN == 15: 16 + 128), 64-bit identities for a table with the wide minimizer identity
-constexpr int ring_u32(bool wide, bool adj) { return wide ? 160 : (adj ? 144 : 96); }
-template <bool SPACED, int LAYOUT, int KT, int NM, int NB = 16, int SPAN = 8, bool OVC = false, bool WIDE = false, bool PACKED = false, bool STAGE3 = false, class IssueNext>
+// One compiled form of classify: what follows from its flags, computed here and nowhere else.  UNIT1: the overflow kernel's form
+// (one wavefront per block, the counter in global memory, a 16-bucket stage whatever the seed).
+template <bool SPACED, int LAYOUT, int KT, int NM, int SPAN = 8, bool OVC = false, bool WIDE = false, bool PACKED = false, bool UNIT1 = false>
+struct ClassifyTraits {
+    // Contiguous seeds on the minbucket layout with a compile-time k (the usual form: no tags, no wide identity) go through the probe
+    // two rounds at a time (probe_minbucket2): one probe pass and one vote for the 120 k-mers of a 150-bp read instead of two.
+    static constexpr bool PAIRS = !SPACED && LAYOUT == 2 && KT != 0 && !OVC && !WIDE;
+    // ... and, where two k-mers fit one 64-bit window (k <= 31), as DOUBLE rounds: lane l takes the adjacent k-mers 2 l and 2 l + 1 of 128
+    // from one window and one reverse complement instead of k-mers l and l + 64 from two
+    static constexpr bool ADJ = PAIRS && adjacent_kmers(KT, SPAN);
+    // The PAIRS forms keep the counter's arrays directly behind the 16-bucket stage of aux, so the two-round probe may stage 24 buckets
+    // while the counter has nothing in them.
+    // (the two-mate ASCII forms sit at 63 VGPRs and take the third load only with 12 bytes of scratch: they keep the 16-bucket stage)
+    static constexpr bool STAGE3 = PAIRS && !(NM == 2 && !PACKED);
+    static constexpr int NB = (LAYOUT == 2 && SPACED && !UNIT1) ? BNS_SPACED_NB : 16;        // buckets staged per probe pass
+    // list 64, stage 16 x 32, keys 128, counts 128 u32 = minb_aux_u32(24), the same bytes as the separate arrays
+    static constexpr int AUX_U32 = PAIRS ? minb_aux_u32(MINB_NB_WIDE) : minb_aux_u32(NB);
+    // u32 entries of the minimizer ring per wave: 64 + window - 1 <= 79 hashes round by round, 128 + span + 1 <= 144 for a double round
+    // (SPAN == 15: 16 + 128), 64-bit identities for a table with the wide minimizer identity
+    static constexpr int RING_U32 = WIDE ? 160 : (ADJ ? 144 : 96);
+    // waves per SIMD (the 64-byte bucket layout stages four 16-byte slots per lane -- sixteen registers: 7 waves per SIMD, no scratch)
+    static constexpr int WAVES = (LAYOUT == 1 && !SPACED) ? 7 : (SPACED ? BNS_SPACED_WAVES : BNS_WAVES_PER_SIMD);
+    static_assert(!PAIRS || (NB == 16 && minb_aux_u32(MINB_NB_WIDE) == minb_aux_u32(16) + 2 * (int)LDS_CAP), "the counter is the stage's third KiB");
+    static_assert(AUX_U32 - MINB_LIST_U32 >= 2 * (int)LDS_CAP, "stage must hold tin/tout");
+};
+// Marginal-cost experiments (tools/pad.sh): N extra instructions per unit (BNS_PAD_UNIT) or per round of the round-by-round loop, by
+// instruction class.  Nothing in a default build.
+#ifndef BNS_PAD_UNIT
+#define BNS_PAD_UNIT 0
+#endif
+#ifndef BNS_PAD_VALU
+#define BNS_PAD_VALU 0
+#endif
+#ifndef BNS_PAD_VFAST
+#define BNS_PAD_VFAST 0
+#endif
+#ifndef BNS_PAD_SALU
+#define BNS_PAD_SALU 0
+#endif
+#ifndef BNS_PAD_LDS
+#define BNS_PAD_LDS 0
+#endif
+template <int N> __device__ __forceinline__ void pad_valu(int lane)
+{
+    if constexpr (N > 0) { u32 pv = (u32)lane; for (int q = 0; q < N; ++q) asm volatile("v_mul_lo_u32 %0, %0, %0" : "+v"(pv)); asm volatile("" :: "v"(pv)); }
+}
+template <int N> __device__ __forceinline__ void pad_vfast(int lane)
+{
+    if constexpr (N > 0) { u32 pv = (u32)lane; for (int q = 0; q < N; ++q) asm volatile("v_add_u32 %0, %0, %0" : "+v"(pv)); asm volatile("" :: "v"(pv)); }
+}
+template <int N> __device__ __forceinline__ void pad_salu()
+{
+    if constexpr (N > 0) { for (int q = 0; q < N; ++q) asm volatile("s_add_u32 s20, s20, 3" ::: "s20", "scc"); }
+}
+template <int N> __device__ __forceinline__ void pad_lds(int lane)
+{
+    if constexpr (N > 0) { u32 pv; for (int q = 0; q < N; ++q) asm volatile("ds_read_b32 %0, %1" : "=v"(pv) : "v"((u32)lane * 4u)); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+}
+// offv = offsets of the unit's reads, one per lane (lanes 0..nmates); (have0, r_lo, r_hi) = prefetched pass 0 of mate 0.
+// ob = lane of offv that holds the unit's first offset (the caller keeps a whole chunk's offsets in one register pair)
+// issue_next: the caller's loads and stores that have nothing to do with this unit (classify_kernel: the next unit's prefetch and the
+// previous unit's record; it may read rec_out / rec_valid, which are written only at the end).  Called exactly once: directly behind
+// the unit's first pack -- whose wait for pre0 it would otherwise sit in front of -- or, by a unit that packs nothing, on its own.
+template <bool SPACED, int LAYOUT, int KT, int NM, int SPAN = 8, bool OVC = false, bool WIDE = false, bool PACKED = false, bool UNIT1 = false, class IssueNext>
 __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u64 offv, u32 ob, bool have0, const Prefetch &pre0,
                                               u32 *keys, u32 *cnt, u32 *tin, u32 *tout, u32 cap, bool record_overflow, u32 *ring, u32 *aux, u64 *pk,
                                               uint4 &rec_out, bool &rec_valid, IssueNext &&issue_next)
 {
+    using T = ClassifyTraits<SPACED, LAYOUT, KT, NM, SPAN, OVC, WIDE, PACKED, UNIT1>;
+    constexpr bool PAIRS = T::PAIRS, ADJ = T::ADJ, STAGE3 = T::STAGE3;
+    constexpr int NB = T::NB;
     const int lane = lane_id();
     const u32 rdesc = SPACED ? run_desc(p) : 0u;
     const u32 k = KT ? (u32)KT : p.k, c = KT ? (u32)KT : p.c;
@@ -1050,15 +1118,7 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
     const bool have1 = !SPACED && NM == 2 && !OVC;            // (the k = 31 instantiations; the generic ones and the cooperative-overflow form have no registers to spare)
     // (gfx9 counts loads and stores in one counter and retires them in order: issued in front of the unit's first pack, this load and
     // the caller's issue_next are what the pack's wait for pre0 -- long arrived -- waits for)
-#ifdef BNS_PAD_UNIT                                             // marginal-cost experiments: N extra instructions per unit
-    { u32 pv = (u32)lane; for (int q = 0; q < BNS_PAD_UNIT; ++q) asm volatile("v_mul_lo_u32 %0, %0, %0" : "+v"(pv)); asm volatile("" :: "v"(pv)); }
-#endif
-    // Contiguous seeds on the minbucket layout with a compile-time k (the usual form: no tags, no wide identity) go through the probe
-    // two rounds at a time (probe_minbucket2): one probe pass and one vote for the 120 k-mers of a 150-bp read instead of two.
-    constexpr bool PAIRS = !SPACED && LAYOUT == 2 && KT != 0 && !OVC && !WIDE;
-    // ... and, where two k-mers fit one 64-bit window (k <= 31), as DOUBLE rounds: lane l takes the adjacent k-mers 2 l and 2 l + 1 of 128
-    // from one window and one reverse complement instead of k-mers l and l + 64 from two (adjacent_kmers(): the forms that take it)
-    constexpr bool ADJ = PAIRS && adjacent_kmers(KT, SPAN);
+    pad_valu<BNS_PAD_UNIT>(lane);
     // a round's found / valid lanes into missing, n_hits and the hit stream (k-mer order); returns the found mask
     auto tally = [&](const ProbeResult &pr, bool valid) -> u64 {
         const u64 fm = ballot64(pr.found), vm = ballot64(valid);
@@ -1154,7 +1214,7 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
                     bkt = bucket_of(round_minhash<MW, SPAN == 15>(kf, krc, ADJ ? 0u : rd, k, mlen, ring, lq), n_mb);
                     return valid && rd * 64u + lq < chunk_nk;
                 };
-                if constexpr (ADJ) {
+                if constexpr (ADJ) {                                  // double rounds: 128 adjacent k-mers at a time, two per lane
                     for (u32 rd = 0; rd * 64u < chunk_nk; rd += 2u) {
                         if ((rd + 1u) * 64u < chunk_nk) {             // (wave-uniform) more than 64 k-mers left: a double round
                             u64 win;
@@ -1183,85 +1243,77 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
                             vote2(tally(pa, vA), pa.val, 0ULL, 0u);
                         }
                     }
-                    continue;
-                }
-                for (u32 rd = 0; rd * 64u < chunk_nk; rd += 2u) {
-                    u64 keyA;
-                    u32 bA;
-                    const bool vA = key_round(rd, keyA, bA);
-                    if ((rd + 1u) * 64u < chunk_nk) {                 // (wave-uniform) rounds rd and rd + 1: one probe, one vote
-                        u64 keyB;
-                        u32 bB;
-                        const bool vB = key_round(rd + 1u, keyB, bB);
-                        ProbeResult pa, pb;
-                        // (the counter's LDS arrays lie directly behind the stage -- classify_kernel -- and are dead while every entry is in
-                        // a register: until the unit's 65th taxon they are the stage's third KiB)
-                        probe_minbucket2<(KT == 32), NB>(p.minb, keyA, bA, vA, keyB, bB, vB, aux, p.slots, p.ovf_mask, pa, pb,
-                                                         (STAGE3 && D <= 64u) ? (u32)MINB_NB_WIDE : 16u);
-                        const u64 fa = tally(pa, vA), fb = tally(pb, vB);
-                        vote2(fa, pa.val, fb, pb.val);
-                    } else {                                          // an odd last round: the one-round probe
-                        const ProbeResult pa = probe_minbucket<(KT == 32), NB>(p.minb, keyA, bA, vA, aux, p.slots, p.ovf_mask);
-                        vote2(tally(pa, vA), pa.val, 0ULL, 0u);
+                } else {                                              // pairs of rounds (k = 32): rounds rd and rd + 1 in lanes l / l
+                    for (u32 rd = 0; rd * 64u < chunk_nk; rd += 2u) {
+                        u64 keyA;
+                        u32 bA;
+                        const bool vA = key_round(rd, keyA, bA);
+                        if ((rd + 1u) * 64u < chunk_nk) {                 // (wave-uniform) rounds rd and rd + 1: one probe, one vote
+                            u64 keyB;
+                            u32 bB;
+                            const bool vB = key_round(rd + 1u, keyB, bB);
+                            ProbeResult pa, pb;
+                            // (the counter's LDS arrays lie directly behind the stage -- classify_kernel -- and are dead while every entry is in
+                            // a register: until the unit's 65th taxon they are the stage's third KiB)
+                            probe_minbucket2<(KT == 32), NB>(p.minb, keyA, bA, vA, keyB, bB, vB, aux, p.slots, p.ovf_mask, pa, pb,
+                                                             (STAGE3 && D <= 64u) ? (u32)MINB_NB_WIDE : 16u);
+                            const u64 fa = tally(pa, vA), fb = tally(pb, vB);
+                            vote2(fa, pa.val, fb, pb.val);
+                        } else {                                          // an odd last round: the one-round probe
+                            const ProbeResult pa = probe_minbucket<(KT == 32), NB>(p.minb, keyA, bA, vA, aux, p.slots, p.ovf_mask);
+                            vote2(tally(pa, vA), pa.val, 0ULL, 0u);
+                        }
                     }
                 }
-                continue;
-            }
-            for (u32 rd = 0; rd * 64u < chunk_nk; ++rd) {
-                const u32 jl = rd * 64u + (u32)lane;
-                u64 kmer, win = 0;
-                bool valid;
-                if (SPACED) valid = p.n_runs ? extract_spaced_lds(pk, rd, p, rdesc, kmer, clean) : extract_spaced(W, M, rd, k, rdesc, kmer);
-                else        { extract_lds32(pk, rd, k, clean, win, valid); kmer = win >> (64u - 2u * k); }
-                valid = valid && jl < chunk_nk;
-#ifdef BNS_PAD_VALU                                            // marginal-cost experiments (tools/pad.sh): N extra instructions per round
-                { u32 pv = (u32)lane; for (int q = 0; q < BNS_PAD_VALU; ++q) asm volatile("v_mul_lo_u32 %0, %0, %0" : "+v"(pv)); asm volatile("" :: "v"(pv)); }
-#endif
-#ifdef BNS_PAD_VFAST
-                { u32 pv = (u32)lane; for (int q = 0; q < BNS_PAD_VFAST; ++q) asm volatile("v_add_u32 %0, %0, %0" : "+v"(pv)); asm volatile("" :: "v"(pv)); }
-#endif
-#ifdef BNS_PAD_SALU
-                { for (int q = 0; q < BNS_PAD_SALU; ++q) asm volatile("s_add_u32 s20, s20, 3" ::: "s20", "scc"); }
-#endif
-#ifdef BNS_PAD_LDS
-                { u32 pv; for (int q = 0; q < BNS_PAD_LDS; ++q) asm volatile("ds_read_b32 %0, %1" : "=v"(pv) : "v"((u32)lane * 4u)); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-#endif
-                const u64 kf = kmer;
-                const u64 krc = SPACED ? 0ULL : revcomp_top(win, k);
-                if (!SPACED && (KT != 0 || p.canon)) kmer = kf < krc ? kf : krc;      // (the fixed-k instantiations are canonical-only: launch_kt)
-                ProbeResult pr;
+            } else {                                                  // round by round: every other form
+                for (u32 rd = 0; rd * 64u < chunk_nk; ++rd) {
+                    const u32 jl = rd * 64u + (u32)lane;
+                    u64 kmer, win = 0;
+                    bool valid;
+                    if (SPACED) valid = p.n_runs ? extract_spaced_lds(pk, rd, p, rdesc, kmer, clean) : extract_spaced(W, M, rd, k, rdesc, kmer);
+                    else        { extract_lds32(pk, rd, k, clean, win, valid); kmer = win >> (64u - 2u * k); }
+                    valid = valid && jl < chunk_nk;
+                    pad_valu<BNS_PAD_VALU>(lane);
+                    pad_vfast<BNS_PAD_VFAST>(lane);
+                    pad_salu<BNS_PAD_SALU>();
+                    pad_lds<BNS_PAD_LDS>(lane);
+                    const u64 kf = kmer;
+                    const u64 krc = SPACED ? 0ULL : revcomp_top(win, k);
+                    if (!SPACED && (KT != 0 || p.canon)) kmer = kf < krc ? kf : krc;      // (the fixed-k instantiations are canonical-only: launch_kt)
+                    ProbeResult pr;
 #ifdef BNS_ABLATION                                           // profiling builds only (tools/ablate.sh): results are wrong
-                if (p.dbg & 1) { pr.found = valid && (kmer & 1); pr.val = 1000u + (u32)(kmer & 3); }
-                else
+                    if (p.dbg & 1) { pr.found = valid && (kmer & 1); pr.val = 1000u + (u32)(kmer & 3); }
+                    else
 #endif
-                if (LAYOUT == 2) {
-                    u32 minh;
-                    if (SPACED) minh = key_minhash(kmer, k, MinSpec{p.m, p.min_len, p.min_shift, p.min_canon, 0u});
-                    else if (WIDE) minh = wide_bucket_in(round_minhash_wide<MW>(kf, krc, rd, k, mlen, reinterpret_cast<u64 *>(ring)), mlen);
-                    else minh = round_minhash<MW, (KT != 0 && SPAN == 15)>(kf, krc, rd, k, mlen, ring);
+                    if (LAYOUT == 2) {
+                        u32 minh;
+                        if (SPACED) minh = key_minhash(kmer, k, MinSpec{p.m, p.min_len, p.min_shift, p.min_canon, 0u});
+                        else if (WIDE) minh = wide_bucket_in(round_minhash_wide<MW>(kf, krc, rd, k, mlen, reinterpret_cast<u64 *>(ring)), mlen);
+                        else minh = round_minhash<MW, (KT != 0 && SPAN == 15)>(kf, krc, rd, k, mlen, ring);
 #ifdef BNS_ABLATION
-                    if (p.dbg & 4) minh = (u32)wang64(kmer);
+                        if (p.dbg & 4) minh = (u32)wang64(kmer);
 #endif
-                    // (crowded tables: the lane's group tag goes along, and a miss leaves its home bucket only when that group spilled)
-                    pr = probe_minbucket<(KT == 0 || KT == 32), NB, OVC, true, OVC>(p.minb, kmer, bucket_of(minh, n_mb), valid, aux, p.slots, p.ovf_mask,
-                                                                                     OVC ? minb_tagbit(minh) : 0u);
-                } else if (LAYOUT == 1) pr = probe_bucket(p.slots, p.bucket_mask, kmer, valid);
-                else                  pr = probe_khash(p.kflags, p.kkeys, p.kvals, p.kh_nb, kmer, valid);
-                const u64 fm = tally(pr, valid);
+                        // (crowded tables: the lane's group tag goes along, and a miss leaves its home bucket only when that group spilled)
+                        pr = probe_minbucket<(KT == 0 || KT == 32), NB, OVC, true, OVC>(p.minb, kmer, bucket_of(minh, n_mb), valid, aux, p.slots, p.ovf_mask,
+                                                                                         OVC ? minb_tagbit(minh) : 0u);
+                    } else if (LAYOUT == 1) pr = probe_bucket(p.slots, p.bucket_mask, kmer, valid);
+                    else                  pr = probe_khash(p.kflags, p.kkeys, p.kvals, p.kh_nb, kmer, valid);
+                    const u64 fm = tally(pr, valid);
 #ifdef BNS_ABLATION
-                u64 rem = (p.dbg & 2) ? 0ULL : fm;
+                    u64 rem = (p.dbg & 2) ? 0ULL : fm;
 #else
-                u64 rem = fm;
+                    u64 rem = fm;
 #endif
-                while (rem) {
-                    const int l = __builtin_ctzll(rem);
-                    const u32 t = readlane(pr.val, l);
-                    const u64 mm = ballot64(pr.val == t) & fm;
-                    rem &= ~mm;
-                    const u32 c = (u32)__popcll(mm);
-                    const bool eq = ckey == t;
-                    if (ballot64(eq) & dmask) { ccnt = eq ? ccnt + c : ccnt; continue; }     // the usual case: a taxon seen before
-                    if (!counter_insert(ckey, ccnt, dmask, keys, cnt, cap, D, t, c)) { overflow = true; break; }
+                    while (rem) {
+                        const int l = __builtin_ctzll(rem);
+                        const u32 t = readlane(pr.val, l);
+                        const u64 mm = ballot64(pr.val == t) & fm;
+                        rem &= ~mm;
+                        const u32 c = (u32)__popcll(mm);
+                        const bool eq = ckey == t;
+                        if (ballot64(eq) & dmask) { ccnt = eq ? ccnt + c : ccnt; continue; }     // the usual case: a taxon seen before
+                        if (!counter_insert(ckey, ccnt, dmask, keys, cnt, cap, D, t, c)) { overflow = true; break; }
+                    }
                 }
             }
         }
@@ -1297,48 +1349,24 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
     rec_valid = true;
 }
 
-#ifndef BNS_WAVES_PER_SIMD
-#define BNS_WAVES_PER_SIMD 8
-#endif
 #ifdef BNS_WAVE_TIMES
 __device__ unsigned long long g_wave_times[2 * 8192];
 #endif
-// Spaced seeds have no minimizer locality (every lookup its own bucket), so their rounds are bound by the random-gather rate
-// of the memory system (41 G fetches/s reached, 44 G/s is the part's ceiling); a 32-bucket stage at 6 waves/SIMD measured
-// 6 % faster than 16 buckets at 8 (two passes per round instead of four), a 64-bucket stage at 3-4 waves 9 % slower.
-#ifndef BNS_SPACED_NB
-#define BNS_SPACED_NB 32         // buckets staged per probe pass for spaced seeds (16 / 32 / 64)
-#endif
-#ifndef BNS_SPACED_WAVES
-#define BNS_SPACED_WAVES 6       // waves per SIMD the spaced instantiations are compiled for
-#endif
-template <bool SPACED> struct ClassifyCfg { static constexpr int NB = 16, WAVES = BNS_WAVES_PER_SIMD; };
-template <> struct ClassifyCfg<true> { static constexpr int NB = BNS_SPACED_NB, WAVES = BNS_SPACED_WAVES; };
 template <bool SPACED, int LAYOUT, int KT, int NM, int SPAN = 8, bool OVC = false, bool WIDE = false, bool PACKED = false>
-// (the 64-byte bucket layout stages four 16-byte slots per lane -- sixteen registers: 7 waves per SIMD, no scratch)
-__global__ __launch_bounds__(256, (LAYOUT == 1 && !SPACED) ? 7 : ClassifyCfg<SPACED>::WAVES) void classify_kernel(ClassifyParams p)
+__global__ __launch_bounds__(256, (ClassifyTraits<SPACED, LAYOUT, KT, NM, SPAN, OVC, WIDE, PACKED>::WAVES)) void classify_kernel(ClassifyParams p)
 {
-    constexpr int NB = LAYOUT == 2 ? ClassifyCfg<SPACED>::NB : 16;
-    // the forms that probe two rounds at a time (classify_unit: PAIRS) keep the counter's arrays in the row of the stage, right behind
-    // its 16 buckets: list 64, stage 16 x 32, keys 128, counts 128 u32 = minb_aux_u32(24), the same bytes as the separate arrays
-    constexpr bool PAIRS = !SPACED && LAYOUT == 2 && KT != 0 && !OVC && !WIDE;
-    constexpr int AUX_U32 = PAIRS ? minb_aux_u32(MINB_NB_WIDE) : minb_aux_u32(NB);
-    // (the two-mate ASCII forms sit at 63 VGPRs and take the third load only with 12 bytes of scratch: they keep the 16-bucket stage)
-    constexpr bool STAGE3 = PAIRS && !(NM == 2 && !PACKED);
-    static_assert(!PAIRS || (NB == 16 && minb_aux_u32(MINB_NB_WIDE) == minb_aux_u32(16) + 2 * (int)LDS_CAP), "the counter is the stage's third KiB");
+    using T = ClassifyTraits<SPACED, LAYOUT, KT, NM, SPAN, OVC, WIDE, PACKED>;
     // per wave: counter keys/counts (1 KB), minimizer ring + bucket list + bucket stage (3.1 KB; the stage doubles as the
     // tin/tout scratch of resolve_wave -- its first KiB -- which runs when no probe is in flight), packed chunk image (1 KB): 18.6 KB / block (19 008 B;
     // 19 776 B with the double round's ring, 20 032 B with the wide identity's: eight blocks per CU -- 20 480 B each -- in every case)
     // (ring, list + stage and chunk image are separate arrays: the stage is written by the fetch itself (LDS DMA), and the compiler
     // puts a vmcnt wait in front of any LDS access it cannot tell apart from it)
-    // (ring_u32: 64 + window - 1 <= 79 32-bit hashes round by round, 128 + 16 for a double round, 64-bit identities for the wide identity)
-    __shared__ __attribute__((aligned(8))) u32 s_ring[4][ring_u32(WIDE, PAIRS && adjacent_kmers(KT, SPAN))];
-    __shared__ __attribute__((aligned(16))) u32 s_mh[4][AUX_U32];
+    __shared__ __attribute__((aligned(8))) u32 s_ring[4][T::RING_U32];
+    __shared__ __attribute__((aligned(16))) u32 s_mh[4][T::AUX_U32];
     __shared__ u64 s_pk[4][IMG_U64];
-    static_assert(AUX_U32 - MINB_LIST_U32 >= 2 * (int)LDS_CAP, "stage must hold tin/tout");
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // wave-uniform: keeps the unit loop scalar
     u32 *ctr_keys, *ctr_cnt;
-    if constexpr (PAIRS) {
+    if constexpr (T::PAIRS) {                     // (the counter's arrays in the row of the stage, right behind its 16 buckets)
         ctr_keys = s_mh[wv] + minb_aux_u32(16); ctr_cnt = ctr_keys + LDS_CAP;
     } else {
         __shared__ u32 s_keys[4][LDS_CAP], s_cnt[4][LDS_CAP];
@@ -1417,7 +1445,7 @@ __global__ __launch_bounds__(256, (LAYOUT == 1 && !SPACED) ? 7 : ClassifyCfg<SPA
                 // first wait after a store waits for its acknowledgement too.
                 if (pend_valid && lane == 0) cold_params()->records[pend_u] = pend;
             };
-            classify_unit<SPACED, LAYOUT, KT, NM, NB, SPAN, OVC, WIDE, PACKED, STAGE3>(p, base + j, offs, j * nm, true, pre, ctr_keys, ctr_cnt, s_mh[wv] + MINB_LIST_U32,
+            classify_unit<SPACED, LAYOUT, KT, NM, SPAN, OVC, WIDE, PACKED>(p, base + j, offs, j * nm, true, pre, ctr_keys, ctr_cnt, s_mh[wv] + MINB_LIST_U32,
                                           s_mh[wv] + MINB_LIST_U32 + LDS_CAP, LDS_CAP, true, s_ring[wv], s_mh[wv], s_pk[wv], pend, pend_valid, issue_next);
             pend_u = base + j;
             pre = npre;
@@ -1433,8 +1461,9 @@ __global__ __launch_bounds__(256, (LAYOUT == 1 && !SPACED) ? 7 : ClassifyCfg<SPA
 template <bool SPACED, int LAYOUT, bool WIDE = false, bool PACKED = false>
 __global__ __launch_bounds__(64) void classify_overflow_kernel(ClassifyParams p, u32 *scratch, u64 total_bases)
 {
-    __shared__ __attribute__((aligned(8))) u32 s_ring[WIDE ? 160 : 96];
-    __shared__ __attribute__((aligned(16))) u32 s_mh[MINB_AUX_U32];
+    using T = ClassifyTraits<SPACED, LAYOUT, 0, 0, 8, false, WIDE, PACKED, true>;
+    __shared__ __attribute__((aligned(8))) u32 s_ring[T::RING_U32];
+    __shared__ __attribute__((aligned(16))) u32 s_mh[T::AUX_U32];
     __shared__ u64 s_pk[IMG_U64];
     const u32 n = *p.ovf_count;
     for (u32 i = blockIdx.x; i < n; i += gridDim.x) {
@@ -1445,7 +1474,7 @@ __global__ __launch_bounds__(64) void classify_overflow_kernel(ClassifyParams p,
         uint4 rec;
         bool ok;
         const u64 offv = (threadIdx.x & 63u) == 0 ? b0 : ((threadIdx.x & 63u) == 1 ? bm : b1);
-        classify_unit<SPACED, LAYOUT, 0, 0, 16, 8, false, WIDE, PACKED>(p, u, offv, 0u, false, Prefetch{0u, 0u, 0u}, scratch + b0, scratch + total_bases + b0,
+        classify_unit<SPACED, LAYOUT, 0, 0, 8, false, WIDE, PACKED, true>(p, u, offv, 0u, false, Prefetch{0u, 0u, 0u}, scratch + b0, scratch + total_bases + b0,
                                       scratch + 2 * total_bases + b0, scratch + 3 * total_bases + b0, (u32)(b1 - b0), false, s_ring, s_mh, s_pk, rec, ok, [] {});
         if (ok && threadIdx.x == 0) p.records[u] = rec;
     }

@@ -173,3 +173,64 @@ def test_round_pairs_many_taxa(gpu_ctx, oracle):
     assert (got["n_hits"] > 0).all()
     d = [len(set(h.tolist())) for h in got["hits"]]
     assert max(d) > 64
+
+
+def test_round_by_round_tie_order(gpu_ctx, oracle):
+    """A form that votes round by round -- k = 29 on the clustered table: the generic kernel -- on units with two sibling taxa
+    of exactly equal counts, the taxon seen first in round 0 and the other in round 1 (reads of 65 and 129 k-mers; in a read
+    of 64 k-mers, one round, the first is at the lower lanes).  The vote's insertion order is the hit stream's and feeds the
+    tie fold; taxon, missing, ambig, n_hits and the hit stream are the oracle's."""
+    from classify_forms import expected_form
+    k = 29
+    ta, tb = 100, 101
+    tax = oracle.Taxonomy(pairs=[(1, 1), (2, 1), (ta, 2), (tb, 2)])
+    rng = np.random.default_rng(29)
+    table = oracle.Table()
+    seg_a, seg_b = synth.rand_seq(rng, 60), synth.rand_seq(rng, 60)
+    oracle.lca_map_add(table, tax, k, seg_a.tobytes(), ta)
+    oracle.lca_map_add(table, tax, k, seg_b.tobytes(), tb)
+    w = synth.World()
+    w.k, w.gaps, w.canon, w.tax, w.table, w.parent = k, None, True, tax, table, tax.parent
+    w.flags, w.keys, w.vals = table.arrays()
+    w.n_buckets = table.n_buckets
+    geo = load(gpu_ctx, w)
+    assert expected_form(k, True, None, 2, geo["m"], geo["identity_bits"], False, False, False)[2] == 0     # no fixed-k form
+
+    def unit(nk, c, pa, pb):
+        """nk k-mers: c of taxon a from k-mer pa on, c of taxon b from k-mer pb on, random sequence around them (the base on
+        either side of a piece is not the one its segment goes on with: the piece's c k-mers are all the read has of it)"""
+        n = c + k - 1
+        r = synth.rand_seq(rng, nk + k - 1)
+        oa, ob = int(rng.integers(0, 60 - n + 1)), int(rng.integers(0, 60 - n + 1))
+        r[pa:pa + n] = seg_a[oa:oa + n]
+        r[pb:pb + n] = seg_b[ob:ob + n]
+        avoid = {}
+        for pos, seg, o in ((pa, seg_a, oa), (pb, seg_b, ob)):
+            if pos > 0 and o > 0:
+                avoid.setdefault(pos - 1, set()).add(int(seg[o - 1]))
+            if pos + n < r.size and o + n < seg.size:
+                avoid.setdefault(pos + n, set()).add(int(seg[o + n]))
+        for f, bad in avoid.items():
+            r[f] = next(x for x in b"ACGT" if x not in bad)
+        return r
+
+    reads, where = [], []
+    for rep in range(8):
+        c = 1 + rep % 3                                         # 64 k-mers, one round: a at the lower lanes
+        pa = int(rng.integers(0, 64 - 2 * c - k + 1))
+        pb = int(rng.integers(pa + c + k, 64 - c + 1))
+        reads.append(unit(64, c, pa, pb)); where.append((c, pa, pb))
+        pa = int(rng.integers(0, 64 - k))                       # 65 k-mers: round 1 is k-mer 64 alone
+        reads.append(unit(65, 1, pa, 64)); where.append((1, pa, 64))
+        c = 1 + rep                                             # 129 k-mers: b in round 1, from k-mer 64 + rep on
+        pa = int(rng.integers(0, 64 - c - k + 1))
+        reads.append(unit(129, c, pa, 64 + rep)); where.append((c, pa, 64 + rep))
+    for r, (c, pa, pb) in zip(reads, where):
+        nk = r.size - k + 1
+        b = kmer_buckets(r, k, geo["m"], geo["buckets"])
+        assert len(b) == nk and all(x is not None for x in b)
+        assert pa + c <= 64 and pa + c + k <= pb and pb + c <= nk and (nk == 64 or pb >= 64)     # a in round 0, b behind it
+        _, _, _, hits = oracle.classify_seq(table, tax, k, r.tobytes(), None, canon=True)
+        assert list(hits) == [ta] * c + [tb] * c                # the tie, and its order
+    got = check(gpu_ctx, oracle, w, reads)
+    assert (got["taxon"] == 2).all() and (got["n_hits"] == [2 * c for c, _, _ in where]).all()
