@@ -90,6 +90,7 @@ def load():
         "bns_load_taxonomy": (C.c_int, [vp, u32p, C.c_uint32]),
         "bns_tally_enable": (C.c_int, [vp, C.c_int]),
         "bns_tally_read": (C.c_int, [vp, u64p, u64p, C.c_uint32, C.c_int]),
+        "bns_table_tally": (C.c_int, [vp, u64p, u64p, C.c_uint32]),
         "bns_set_confidence": (C.c_int, [vp, C.c_uint64, C.c_uint64]),
         "bns_sketch_enable": (C.c_int, [vp, C.c_uint32]),
         "bns_sketch_read": (C.c_int, [vp, u32p, vp, C.c_uint32, u32p, u32p, C.c_int]),

@@ -223,6 +223,15 @@ class Context:
         self._chk(self.L.bns_tally_read(self.h, _p(direct, u64p), _p(clade, u64p), n + 1, int(bool(reset))), "bns_tally_read")
         return direct, clade
 
+    def table_tally(self):
+        """bns_table_tally -> (direct, clade): the keys of the loaded table per taxon bin (tally_enable's bins, by the key's value) and
+        per clade, uint64 arrays of n + 1 entries.  Every context of a multi-GPU load returns the whole answer: do not add them up."""
+        n = getattr(self, "_n_tax", 0)
+        direct = np.zeros(n + 1, dtype=np.uint64)
+        clade = np.zeros(n + 1, dtype=np.uint64)
+        self._chk(self.L.bns_table_tally(self.h, _p(direct, u64p), _p(clade, u64p), n + 1), "bns_table_tally")
+        return direct, clade
+
     def set_confidence(self, threshold):
         """bns_set_confidence: every classify call walks its taxa up to the first ancestor whose clade holds ceil(threshold * Q) of a
         unit's Q probed k-mers (0 when none does); threshold 0 turns it off.  Needs a loaded taxonomy (unless 0)."""

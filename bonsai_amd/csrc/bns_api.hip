@@ -3,6 +3,7 @@
 #include "../../include/bonsai_amd.h"
 #include "bns_kernels.hip"
 #include "bns_tally.hpp"
+#include "bns_inspect.hpp"
 #include "bns_confidence.hpp"
 #include "bns_sketch.hpp"
 
@@ -59,6 +60,8 @@ constexpr int BNS_DBG_OVC_ON = 0x8000;              // classify: always the coop
 constexpr int BNS_DBG_PLAIN_FILL = 0x10;            // bns_load_table: keys in arrival order even into a crowded table (A/B of the group-aware fill)
 constexpr int BNS_DBG_GROUP_FILL = 0x20;            // bns_load_table: the group-aware fill even for a table with room (tests reach it on small tables)
 constexpr int BNS_DBG_BATCH_TINY = 0x40;            // bns_classify_text: a classify launch per >= 64 records (many batches on small texts)
+constexpr int BNS_DBG_INSPECT_TINY = 0x8;           // bns_table_tally: grids of at most 4 workgroups that flush their LDS counters every 3 rounds (tests: many rounds, a full LDS hash and the mid-walk flush on small tables; same counts)
+constexpr int BNS_DBG_INSPECT_WHOLE = 0x80;         // bns_table_tally: fetch whole 128-byte buckets instead of their upper halves (A/B; same counts)
 constexpr int BNS_DBG_SLICE_8K = 0x4000;            // bns_classify_batch uploads in 8 KiB slices (the slicing logic on small batches)
 constexpr int BNS_DBG_STREAM_CHUNK_SHIFT = 16, BNS_DBG_STREAM_CHUNK_MASK = 0x1F << 16;   // log2 of the streamed chunk (0 = 27)
 constexpr int BNS_DBG_SPACED_M_SHIFT = 24, BNS_DBG_SPACED_M_MASK = 0x1F << 24;           // spaced seeds: force the run minimizer's m
@@ -676,7 +679,15 @@ static int load_table_impl(bns_ctx *ctx, uint64_t n_buckets, const uint32_t *d_f
         if (streamed) return fail(ctx, BNS_ERR_ARG, "BNS_LAYOUT_KHASH probes the arrays themselves: they must be resident");
         ctx->kflags = d_flags; ctx->kkeys = d_keys; ctx->kvals = d_vals; ctx->kh_nb = n_buckets;
         ctx->layout = BNS_LAYOUT_KHASH;
-        ctx->n_keys = 0;                              // unknown without a scan; bns_table_info reports 0
+        // present keys (what kh_size would say): one pass over the flag words, so that bns_table_info says what the other layouts'
+        // loads say and bns_table_tally's sum(direct) can be held against it
+        unsigned long long *d_n = ((SmallLayout *)ctx->small.p)->load_cnt, n_present = 0;
+        HIPCHK(ctx, hipMemsetAsync(d_n, 0, 8, st));
+        hipLaunchKernelGGL(count_present_kernel, dim3(grid_for(ctx, std::max<u64>(1, n_buckets >> 4), 256)), dim3(256), 0, st, d_flags, (u64)n_buckets, d_n);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(&n_present, d_n, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        ctx->n_keys = n_present;
         return BNS_OK;
     }
     SmallLayout *sm = (SmallLayout *)ctx->small.p;
@@ -1371,6 +1382,64 @@ int bns_tally_read(bns_ctx *ctx, uint64_t *direct, uint64_t *clade, uint32_t len
     if (reset) HIPCHK(ctx, hipMemsetAsync(ctx->tally_direct.p, 0, bytes, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     return BNS_OK;
+}
+
+int bns_table_tally(bns_ctx *ctx, uint64_t *direct, uint64_t *clade, uint32_t len)
+{
+    if (!ctx) return BNS_ERR_ARG;
+    if (ctx->layout < 0) return fail(ctx, BNS_ERR_STATE, "no table loaded (bns_load_table)");
+    if (!ctx->nodes) return fail(ctx, BNS_ERR_STATE, "no taxonomy loaded (bns_load_taxonomy)");
+    if (len != ctx->n_nodes + 1u) return fail(ctx, BNS_ERR_ARG, "len must be n + 1 (n as given to bns_load_taxonomy)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const u32 n = ctx->n_nodes;
+    const TaxNode *nodes = (const TaxNode *)ctx->nodes;
+    const size_t bins = (size_t)n + 1;
+    const u32 n_pos = ctx->tax_clock + 1u;
+    // scratch of this call only: direct | clade | S
+    unsigned long long *d = nullptr;
+    HIPCHK(ctx, hipMalloc((void **)&d, (2 * bins + (clade ? (size_t)n_pos : 0)) * 8));
+    unsigned long long *c = d + bins, *S = c + bins;
+    int rc = [&]() -> int {
+        HIPCHK(ctx, hipMemsetAsync(d, 0, bins * 8, st));
+        const bool whole = (ctx->dbg & BNS_DBG_INSPECT_WHOLE) != 0, tiny = (ctx->dbg & BNS_DBG_INSPECT_TINY) != 0;
+        const u32 flush = tiny ? 3u : INSPECT_FLUSH_ROUNDS;
+        auto grid_of = [&](u64 items, unsigned per_block) { const unsigned g = grid_for(ctx, items, per_block); return tiny ? std::min(g, 4u) : g; };
+        if (ctx->layout == BNS_LAYOUT_KHASH)
+            hipLaunchKernelGGL(inspect_khash_kernel, dim3(grid_of(ctx->kh_nb, TALLY_BLOCK)), dim3(TALLY_BLOCK), 0, st, ctx->kflags, ctx->kvals,
+                               (u64)ctx->kh_nb, nodes, n, d, flush);
+        else if (ctx->layout == BNS_LAYOUT_BUCKET)
+            hipLaunchKernelGGL(inspect_slots_kernel, dim3(grid_of(ctx->n_slots, TALLY_BLOCK)), dim3(TALLY_BLOCK), 0, st, (const Slot *)ctx->slots,
+                               (u64)ctx->n_slots, nodes, n, d, flush);
+        else {
+            const u64 n_bucket = ctx->n_slots / 8;                               // home buckets and the spill-only ones behind them
+            const unsigned grid = grid_of(n_bucket, TALLY_BLOCK / 4 * INSPECT_MINB_UNROLL);
+            if (whole) hipLaunchKernelGGL(inspect_minb_kernel<true>, dim3(grid), dim3(TALLY_BLOCK), 0, st, (const MinBucket *)ctx->slots, n_bucket, nodes, n, d, flush);
+            else       hipLaunchKernelGGL(inspect_minb_kernel<false>, dim3(grid), dim3(TALLY_BLOCK), 0, st, (const MinBucket *)ctx->slots, n_bucket, nodes, n, d, flush);
+            HIPCHK(ctx, hipGetLastError());
+            if (ctx->n_ovf_slots)
+                hipLaunchKernelGGL(inspect_slots_kernel, dim3(grid_of(ctx->n_ovf_slots, TALLY_BLOCK)), dim3(TALLY_BLOCK), 0, st,
+                                   (const Slot *)ctx->ovf_slots, (u64)ctx->n_ovf_slots, nodes, n, d, flush);
+        }
+        HIPCHK(ctx, hipGetLastError());
+        if (clade) {
+            HIPCHK(ctx, hipMemsetAsync(S, 0, (size_t)n_pos * 8, st));
+            hipLaunchKernelGGL(clade_scatter_kernel, dim3(grid_for(ctx, n, 256)), dim3(256), 0, st, nodes, n, (const unsigned long long *)d, S, n_pos);
+            HIPCHK(ctx, hipGetLastError());
+            hipLaunchKernelGGL(clade_scan_kernel, dim3(1), dim3(CLADE_SCAN_BLOCK), 0, st, S, (u64)n_pos);
+            HIPCHK(ctx, hipGetLastError());
+            hipLaunchKernelGGL(clade_kernel, dim3(grid_for(ctx, (u64)n + 1, 256)), dim3(256), 0, st, nodes, n, (const unsigned long long *)d,
+                               (const unsigned long long *)S, n_pos, c);
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipMemcpyAsync(clade, c, bins * 8, hipMemcpyDeviceToHost, st));
+        }
+        if (direct) HIPCHK(ctx, hipMemcpyAsync(direct, d, bins * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        return BNS_OK;
+    }();
+    if (rc != BNS_OK) (void)hipStreamSynchronize(st);                            // nothing of the call may still use the scratch
+    (void)hipFree(d);
+    return rc;
 }
 
 int bns_set_confidence(bns_ctx *ctx, uint64_t num, uint64_t den)

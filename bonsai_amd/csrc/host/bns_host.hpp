@@ -104,8 +104,12 @@ u64 hll_estimate(const u8 *reg);
 // sketch = the register-wise maximum over the sketched bins in its subtree (sketch_bins ascending and distinct, sketch_regs HLL_M bytes
 // each, already merged over the contexts; 0 when the subtree has none).  0 on the "unclassified" line, bin n's own estimate on
 // "(not in taxonomy)".  The same lines in the same order as the seven-column report.
+// db_keys (`-d`; nullptr: none of this): n + 1 key counts of the db per clade (bns_table_tally's clade[]) add two columns behind the distinct
+// one, "\t%llu\t%.6f": db_keys[v] and (double)distinct / (double)db_keys[v] -- not clamped, the numerator is an estimate and may exceed the
+// denominator --, 0.000000 where db_keys[v] is 0; "0\t0.000000" on the "unclassified" line.
 std::string format_report(const u64 *direct, const u64 *clade, u32 n, const u32 *parent, const std::vector<std::string> &ranks,
-                          const std::unordered_map<u32, std::string> &names, const u32 *sketch_bins, const u8 *sketch_regs, u32 n_sketched);
+                          const std::unordered_map<u32, std::string> &names, const u32 *sketch_bins, const u8 *sketch_regs, u32 n_sketched,
+                          const u64 *db_keys = nullptr);
 
 // ---- reads --------------------------------------------------------------------------------------------
 struct bseq1_t {                // kseq_declare.h:40-44; the fields are VIEWS into memory owned by a ReadChunk (below)
@@ -322,6 +326,7 @@ struct ClassifierGeneric {
     std::FILE *taxon_out_ = nullptr;         // `bonsai classify -b`: the taxon of every unit, in input order, as raw little-endian u32
     std::FILE *report_out_ = nullptr;        // `bonsai classify -R`: the taxon report, written by write_report after the last unit
     bool sketch_on_ = false;                 // `-u` (enable_sketch): the report carries the distinct k-mer column
+    bool coverage_on_ = false;               // `-d`: write_report adds the clades' db key counts (bns_table_tally on context 0) and the coverage
     unsigned min_qual_ = 0;                  // `bonsai classify -Q`: set_min_base_quality (0: off)
     bool nseq_printed_ = false;              // process_dataset's "nseq:" line on stderr has been printed (by the device text path or the host one)
     u64 n_classified() const { return classified_[0]; }
@@ -342,6 +347,9 @@ void enable_tally(ClassifierGeneric &c);
 void enable_sketch(ClassifierGeneric &c, u32 max_taxa);
 // ... and, after the last, the tallies summed over the contexts and the report written to c.report_out_ (names_dmp may be nullptr)
 void write_report(ClassifierGeneric &c, const std::vector<u32> &parent, const char *nodes_dmp, const char *names_dmp);
+// `bonsai inspect`: "# " comment lines (k, present keys, layout, bns_table_geometry's buckets / window / overflow keys), then format_report
+// of the loaded table's keys per taxon (bns_table_tally on context 0: percentages of the db's keys)
+void write_inspect(ClassifierGeneric &c, const Database &db, const std::vector<u32> &parent, const char *nodes_dmp, const char *names_dmp, std::FILE *out);
 
 // classifier.h:112-129 / 72-108 / 45-61: byte-for-byte formatters.  The hit stream comes either as the reference's `taxa`
 // vector or already run-length encoded (bns_classify_batch_runs): same text.

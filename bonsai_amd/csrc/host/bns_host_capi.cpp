@@ -296,4 +296,24 @@ int bnsh_format_report_distinct(const uint64_t *direct, const uint64_t *clade, u
     });
 }
 
+// bnsh_format_report_distinct + the `-d` columns: db_keys = n + 1 key counts of the db per clade (NULL: the `-u` text as it is)
+int bnsh_format_report_coverage(const uint64_t *direct, const uint64_t *clade, uint32_t n, const uint32_t *parent, const char *ranks_blob,
+                                uint32_t n_ranks, const uint32_t *name_ids, const char *names_blob, uint64_t n_names,
+                                const uint32_t *sketch_bins, const uint8_t *sketch_regs, uint32_t n_sketched, const uint64_t *db_keys,
+                                char **out, uint64_t *out_bytes)
+{
+    return guard([&] {
+        const std::vector<std::string> ranks = ranks_blob ? split_nul(ranks_blob, n_ranks) : std::vector<std::string>{};
+        std::unordered_map<u32, std::string> names;
+        if (names_blob) {
+            const std::vector<std::string> nm = split_nul(names_blob, n_names);
+            for (uint64_t i = 0; i < n_names; ++i) names.emplace(name_ids[i], nm[i]);
+        }
+        const std::string s = format_report(direct, clade, n, parent, ranks, names, sketch_bins, sketch_regs, n_sketched, db_keys);
+        *out = static_cast<char *>(std::malloc(s.size() + 1));
+        std::memcpy(*out, s.c_str(), s.size() + 1);
+        *out_bytes = s.size();
+    });
+}
+
 }  // extern "C"

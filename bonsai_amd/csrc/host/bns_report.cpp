@@ -46,13 +46,18 @@ const char *rank_letter(const std::string &r)
     return "";
 }
 
-// distinct: the extra column of the `-u` report (nullptr: the seven-column line)
-void report_line(std::string &out, u64 clade, u64 direct, const u64 *distinct, u64 total, const std::string &code, u32 taxid, unsigned depth,
-                 const std::string &name)
+// distinct: the extra column of the `-u` report (nullptr: the seven-column line); db_keys: the two columns `-d` puts behind it, the
+// clade's key count in the db and distinct / db_keys (not clamped: the numerator is an estimate), 0.000000 where the db holds none
+void report_line(std::string &out, u64 clade, u64 direct, const u64 *distinct, const u64 *db_keys, u64 total, const std::string &code, u32 taxid,
+                 unsigned depth, const std::string &name)
 {
-    char head[160];
+    char head[224];
     const double pct = total ? 100.0 * (double)clade / (double)total : 0.0;
-    if (distinct)
+    if (distinct && db_keys)
+        std::snprintf(head, sizeof(head), "%6.2f\t%llu\t%llu\t%llu\t%llu\t%.6f\t%s\t%u\t", pct, (unsigned long long)clade, (unsigned long long)direct,
+                      (unsigned long long)*distinct, (unsigned long long)*db_keys, *db_keys ? (double)*distinct / (double)*db_keys : 0.0,
+                      code.c_str(), taxid);
+    else if (distinct)
         std::snprintf(head, sizeof(head), "%6.2f\t%llu\t%llu\t%llu\t%s\t%u\t", pct, (unsigned long long)clade, (unsigned long long)direct,
                       (unsigned long long)*distinct, code.c_str(), taxid);
     else
@@ -155,13 +160,14 @@ std::unordered_map<u32, std::string> read_scientific_names(const char *names_dmp
 
 namespace {
 std::string format_report_impl(const u64 *direct, const u64 *clade, u32 n, const u32 *parent, const std::vector<std::string> &ranks,
-                               const std::unordered_map<u32, std::string> &names, const u64 *distinct)
+                               const std::unordered_map<u32, std::string> &names, const u64 *distinct, const u64 *db_keys)
 {
+    if (!distinct) db_keys = nullptr;                      // (the coverage columns follow the distinct k-mer column)
     const u64 zero = 0;
     u64 total = 0;
     for (u32 v = 0; v <= n; ++v) total += direct[v];
     std::string out;
-    if (direct[0]) report_line(out, direct[0], direct[0], distinct ? &zero : nullptr, total, "U", 0u, 0u, "unclassified");
+    if (direct[0]) report_line(out, direct[0], direct[0], distinct ? &zero : nullptr, db_keys ? &zero : nullptr, total, "U", 0u, 0u, "unclassified");
     // children lists of the nodes with a count, in print order: clade descending, ties by taxid ascending
     std::vector<u32> child_cnt(n + 1, 0);
     std::vector<u32> roots;
@@ -198,11 +204,11 @@ std::string format_report_impl(const u64 *direct, const u64 *clade, u32 n, const
             if (!own.empty()) { f.base = own; f.steps = 0; }
             else if (!f.base.empty()) ++f.steps;
             const std::string code = f.base.empty() ? std::string("-") : f.steps ? f.base + std::to_string(f.steps) : f.base;
-            report_line(out, clade[f.v], direct[f.v], distinct ? distinct + f.v : nullptr, total, code, f.v, f.depth, name_of(f.v));
+            report_line(out, clade[f.v], direct[f.v], distinct ? distinct + f.v : nullptr, db_keys ? db_keys + f.v : nullptr, total, code, f.v, f.depth, name_of(f.v));
             for (u32 i = off[f.v + 1]; i-- > off[f.v];) st.push_back({kids[i], f.depth + 1, f.steps, f.base});   // (first child on top)
         }
     }
-    if (direct[n]) report_line(out, direct[n], direct[n], distinct ? distinct + n : nullptr, total, "-", 0xFFFFFFFFu, 0u, "(not in taxonomy)");
+    if (direct[n]) report_line(out, direct[n], direct[n], distinct ? distinct + n : nullptr, db_keys ? db_keys + n : nullptr, total, "-", 0xFFFFFFFFu, 0u, "(not in taxonomy)");
     return out;
 }
 }  // namespace
@@ -210,14 +216,15 @@ std::string format_report_impl(const u64 *direct, const u64 *clade, u32 n, const
 std::string format_report(const u64 *direct, const u64 *clade, u32 n, const u32 *parent, const std::vector<std::string> &ranks,
                           const std::unordered_map<u32, std::string> &names)
 {
-    return format_report_impl(direct, clade, n, parent, ranks, names, nullptr);
+    return format_report_impl(direct, clade, n, parent, ranks, names, nullptr, nullptr);
 }
 
 std::string format_report(const u64 *direct, const u64 *clade, u32 n, const u32 *parent, const std::vector<std::string> &ranks,
-                          const std::unordered_map<u32, std::string> &names, const u32 *sketch_bins, const u8 *sketch_regs, u32 n_sketched)
+                          const std::unordered_map<u32, std::string> &names, const u32 *sketch_bins, const u8 *sketch_regs, u32 n_sketched,
+                          const u64 *db_keys)
 {
     const std::vector<u64> distinct = clade_distinct(sketch_bins, sketch_regs, n_sketched, n, parent);
-    return format_report_impl(direct, clade, n, parent, ranks, names, distinct.data());
+    return format_report_impl(direct, clade, n, parent, ranks, names, distinct.data(), db_keys);
 }
 
 void enable_tally(ClassifierGeneric &c)
@@ -229,6 +236,26 @@ void enable_sketch(ClassifierGeneric &c, u32 max_taxa)
 {
     for (bns_ctx *cx : c.ctxs_) chk(cx, bns_sketch_enable(cx, max_taxa), "bns_sketch_enable");
     c.sketch_on_ = true;
+}
+
+void write_inspect(ClassifierGeneric &c, const Database &db, const std::vector<u32> &parent, const char *nodes_dmp, const char *names_dmp, std::FILE *out)
+{
+    const u32 n = (u32)parent.size();
+    bns_ctx *cx = c.ctxs_[0];
+    std::vector<u64> direct((size_t)n + 1, 0), clade((size_t)n + 1, 0);
+    chk(cx, bns_table_tally(cx, direct.data(), clade.data(), n + 1), "bns_table_tally");
+    uint64_t n_keys = 0, bytes = 0, geo[8] = {0};
+    int layout = -1;
+    chk(cx, bns_table_info(cx, &n_keys, &bytes, &layout), "bns_table_info");
+    chk(cx, bns_table_geometry(cx, geo), "bns_table_geometry");
+    const char *lname = layout == BNS_LAYOUT_KHASH ? "khash" : layout == BNS_LAYOUT_BUCKET ? "bucket" : "minbucket";
+    const std::vector<std::string> ranks = read_node_ranks(nodes_dmp);
+    const std::unordered_map<u32, std::string> names = names_dmp ? read_scientific_names(names_dmp) : std::unordered_map<u32, std::string>{};
+    const std::string text = format_report(direct.data(), clade.data(), n, parent.data(), ranks, names);
+    if (std::fprintf(out, "# k\t%u\n# keys\t%llu\n# layout\t%s\n# buckets\t%llu\n# window\t%llu\n# overflow keys\t%llu\n", db.k_, (unsigned long long)n_keys,
+                     lname, (unsigned long long)geo[0], (unsigned long long)geo[4], (unsigned long long)geo[5]) < 0 ||
+        std::fwrite(text.data(), 1, text.size(), out) != text.size())
+        die("Could not write the inspect report");
 }
 
 void write_report(ClassifierGeneric &c, const std::vector<u32> &parent, const char *nodes_dmp, const char *names_dmp)
@@ -267,7 +294,14 @@ void write_report(ClassifierGeneric &c, const std::vector<u32> &parent, const ch
         std::vector<u8> regs;
         bins.reserve(merged.size()); regs.reserve(merged.size() * HLL_M);
         for (const auto &kv : merged) { bins.push_back(kv.first); regs.insert(regs.end(), kv.second.begin(), kv.second.end()); }
-        text = format_report(direct.data(), clade.data(), n, parent.data(), ranks, names, bins.data(), regs.data(), (u32)bins.size());
+        // -d: the clades' key counts in the db.  Every context holds the same table: context 0's walk is the whole answer
+        std::vector<u64> db_keys;
+        if (c.coverage_on_) {
+            db_keys.resize((size_t)n + 1);
+            chk(c.ctxs_[0], bns_table_tally(c.ctxs_[0], nullptr, db_keys.data(), n + 1), "bns_table_tally");
+        }
+        text = format_report(direct.data(), clade.data(), n, parent.data(), ranks, names, bins.data(), regs.data(), (u32)bins.size(),
+                             c.coverage_on_ ? db_keys.data() : nullptr);
     } else text = format_report(direct.data(), clade.data(), n, parent.data(), ranks, names);
     if (!c.report_out_ || std::fwrite(text.data(), 1, text.size(), c.report_out_) != text.size()) die("Could not write the report");
 }

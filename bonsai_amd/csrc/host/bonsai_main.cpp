@@ -45,6 +45,9 @@ void usage(const char *exe)
                  "-n:\tnames.dmp for the report's names (scientific names; without it a taxon is named by its id).\n"
                  "-u:\tWith -R: one more column after the direct count, the number of distinct k-mers of the db that the reads covered in the\n"
                  "\ttaxon's clade (HyperLogLog estimate, 4096 registers: 1.6 %% standard error), by the k-mers' own taxa.\n"
+                 "-d:\tWith -R and -u: two more columns after the distinct k-mers, the number of keys the db holds for the taxon's clade (counted on\n"
+                 "\tthe GPU from the loaded table) and the coverage, distinct k-mers / db keys.  Not clamped: the numerator is an estimate\n"
+                 "\t(1.6 %% standard error) and may exceed 1.\n"
                  "-U:\tTaxa that can have a sketch per GPU context, 4 KiB each [65536]; beyond that a taxon's k-mers are not counted (a warning says so).\n"
                  "-t:\tConfidence threshold in [0, 1] (digits, at most 9 after the point) [0]: a read (pair) is called at the first of its\n"
                  "\ttaxon and the taxon's ancestors whose clade holds at least that fraction of its k-mers, else unclassified.\n"
@@ -93,10 +96,10 @@ int classify_main(int argc, char *argv[])
     const char *names_path = nullptr;
     unsigned long long conf_num = 0, conf_den = 1;
     unsigned min_qual = 0;
-    bool distinct = false;
+    bool distinct = false, coverage = false;
     long sketch_taxa = 65536;
     if (argc < 4) usage(argv[0]);
-    while ((co = getopt(argc, argv, "Cc:p:o:S:afFkKg:L:NP:b:R:n:t:Q:uU:h?")) >= 0) {
+    while ((co = getopt(argc, argv, "Cc:p:o:S:afFkKg:L:NP:b:R:n:t:Q:udU:h?")) >= 0) {
         switch (co) {
             case 'h': case '?': usage(argv[0]); break;
             case 'C': canonicalize = false; break;
@@ -112,6 +115,7 @@ int classify_main(int argc, char *argv[])
             case 'R': report_fp = std::fopen(optarg, "w"); if (!report_fp) { std::fprintf(stderr, "Could not open report file\n"); return EXIT_FAILURE; } break;
             case 'n': names_path = optarg; break;
             case 'u': distinct = true; break;
+            case 'd': coverage = true; break;
             case 'U': {
                 char *end = nullptr;
                 sketch_taxa = std::strtol(optarg, &end, 10);
@@ -152,6 +156,10 @@ int classify_main(int argc, char *argv[])
     }
     if (!ofp) { std::fprintf(stderr, "Could not open output file\n"); return EXIT_FAILURE; }
     if (distinct && !report_fp) { std::fprintf(stderr, "[E] -u adds a column to the taxon report: it needs -R <path>\n"); return EXIT_FAILURE; }
+    if (coverage && !(distinct && report_fp)) {
+        std::fprintf(stderr, "[E] -d adds the db key count and the coverage behind the distinct k-mer column: it needs -R <path> and -u\n");
+        usage(argv[0]);
+    }
     const int npos = argc - optind;
     if (npos != 3 && npos != 4) usage(argv[0]);
     const auto t_start = std::chrono::steady_clock::now();
@@ -208,6 +216,7 @@ int classify_main(int argc, char *argv[])
         if (min_qual) bns::set_min_base_quality(c, min_qual);
         if (report_fp) bns::enable_tally(c);
         if (distinct) bns::enable_sketch(c, (bns::u32)sketch_taxa);
+        c.coverage_on_ = coverage;
         if (devs.size() > 1) {                                   // which collective library replicated the db over how many devices
             // (one line per device: a multi-GPU record says what it ran on)
             for (size_t i = 0; i < devs.size(); ++i) {
@@ -306,6 +315,47 @@ int pack_main(int argc, char *argv[])
         std::fprintf(stderr, "[E] %s\n", e.what());
         return EXIT_FAILURE;
     }
+    return EXIT_SUCCESS;
+}
+
+// `bonsai inspect`: what the db holds per taxon (Kraken 2's kraken2-inspect), counted on the GPU from the table as classify loads it
+int inspect_main(int argc, char *argv[])
+{
+    auto inspect_usage = [&]() {
+        std::fprintf(stderr, "Usage: %s inspect [-g device] [-L minbucket|bucket|khash] [-n names.dmp] [-o file] <dbpath> <tax_path>\n"
+                             "Prints '# ' lines (k, keys, layout, buckets, window, overflow keys), then the db's keys per taxon in the layout of\n"
+                             "classify -R: percent of the db's keys, keys in the clade, keys of the taxon itself, rank code, taxid, name.\n", argv[0]);
+        return EXIT_FAILURE;
+    };
+    int co, device = 0, layout = BNS_LAYOUT_MINBUCKET;
+    const char *names_path = nullptr, *out_path = nullptr;
+    while ((co = getopt(argc, argv, "g:L:n:o:h?")) >= 0) {
+        switch (co) {
+            case 'g': device = std::atoi(optarg); break;
+            case 'n': names_path = optarg; break;
+            case 'o': out_path = optarg; break;
+            case 'L':
+                if (std::strcmp(optarg, "khash") == 0) layout = BNS_LAYOUT_KHASH;
+                else if (std::strcmp(optarg, "bucket") == 0) layout = BNS_LAYOUT_BUCKET;
+                else if (std::strcmp(optarg, "minbucket") == 0) layout = BNS_LAYOUT_MINBUCKET;
+                else return inspect_usage();
+                break;
+            default: return inspect_usage();
+        }
+    }
+    if (argc - optind != 2) return inspect_usage();
+    std::FILE *ofp = out_path ? std::fopen(out_path, "w") : stdout;
+    if (!ofp) { std::fprintf(stderr, "Could not open output file\n"); return EXIT_FAILURE; }
+    try {
+        bns::Database &db = *new bns::Database(argv[optind]);                // (never destroyed, as in classify)
+        const std::vector<bns::u32> taxmap = bns::build_parent_map(argv[optind + 1]);
+        bns::ClassifierGeneric &c = *new bns::ClassifierGeneric(db, taxmap, std::vector<int>{device}, 1, 0, 0, 1, true, layout);
+        bns::write_inspect(c, db, taxmap, argv[optind + 1], names_path, ofp);
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "[E] %s\n", e.what());
+        return EXIT_FAILURE;
+    }
+    if (ofp != stdout && std::fclose(ofp) != 0) { std::fprintf(stderr, "[E] Could not write the inspect report\n"); return EXIT_FAILURE; }
     return EXIT_SUCCESS;
 }
 
@@ -410,10 +460,12 @@ int main(int argc, char *argv[])
     if (argc > 1 && (std::strcmp(argv[1], "build") == 0 || std::strcmp(argv[1], "phase2") == 0 || std::strcmp(argv[1], "p2") == 0))
         return leave(build_main(argc - 1, argv + 1));                // bin/bonsai.cpp:527-529 aliases
     if (argc > 1 && std::strcmp(argv[1], "pack") == 0) return leave(pack_main(argc - 1, argv + 1));
-    std::fprintf(stderr, "Usage: %s <classify|build|pack> ...\n"
+    if (argc > 1 && std::strcmp(argv[1], "inspect") == 0) return leave(inspect_main(argc - 1, argv + 1));
+    std::fprintf(stderr, "Usage: %s <classify|build|pack|inspect> ...\n"
                          "  classify <opts> <dbpath> <tax_path> <inr1.fq> [<inr2.fq>]\n"
                          "  build    <opts> <out.path> <ignored> <genome paths>\n"
                          "  pack     -o <out.bnsp> <in1.fq> [<in2.fq>]      (reads -> 2-bit container for classify)\n"
+                         "  inspect  <opts> <dbpath> <tax_path>             (the db's keys per taxon, in the layout of classify -R)\n"
                          "Other reference subcommands (prebuild, hist, metatree) are out of scope (DESIGN.md).\n", argv[0]);
     return EXIT_FAILURE;
 }

@@ -59,6 +59,10 @@ def lib():
         L.bnsh_format_report_distinct.restype = C.c_int
         L.bnsh_format_report_distinct.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_char_p,
                                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.bnsh_format_report_coverage.restype = C.c_int
+        L.bnsh_format_report_coverage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_char_p,
+                                                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p),
+                                                  C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -99,10 +103,11 @@ def hll_estimate(registers):
     return int(lib().bnsh_hll_estimate(registers.ctypes.data))
 
 
-def format_report(direct, clade, parent, ranks=None, names=None, sketch_bins=None, sketch_registers=None):
+def format_report(direct, clade, parent, ranks=None, names=None, sketch_bins=None, sketch_registers=None, db_keys=None):
     """the `bonsai classify -R` report text (bns::format_report) from the tallies (n + 1 entries each), parent[] (n), ranks (list by
     taxid) and names ({taxid: name}); with sketch_bins (ascending) and sketch_registers ([s, 4096], merged over the contexts) the `-u`
-    report with the distinct k-mer column"""
+    report with the distinct k-mer column; with db_keys as well (n + 1 key counts of the db per clade, Context.table_tally()'s clade) the
+    `-d` report: two more columns, the key count and distinct / db_keys"""
     direct = np.ascontiguousarray(direct, dtype=np.uint64); clade = np.ascontiguousarray(clade, dtype=np.uint64)
     parent = np.ascontiguousarray(parent, dtype=np.uint32)
     n = parent.size
@@ -114,11 +119,23 @@ def format_report(direct, clade, parent, ranks=None, names=None, sketch_bins=Non
     ids = np.array([i for i, _ in items], dtype=np.uint32)
     nb = b"".join(x.encode() + b"\0" for _, x in items)
     out, ob = C.c_void_p(), C.c_uint64()
+    if db_keys is not None and sketch_bins is None:
+        raise ValueError("db_keys adds columns behind the distinct k-mer column: it needs sketch_bins and sketch_registers")
     if sketch_bins is not None:
         sb = np.ascontiguousarray(sketch_bins, dtype=np.uint32)
         sr = np.ascontiguousarray(sketch_registers, dtype=np.uint8)
         if sr.size != sb.size * 4096:
             raise ValueError("sketch_registers needs 4096 bytes per bin")
+        if db_keys is not None:
+            dk = np.ascontiguousarray(db_keys, dtype=np.uint64)
+            if dk.size != n + 1:
+                raise ValueError("db_keys needs n + 1 entries")
+            if lib().bnsh_format_report_coverage(direct.ctypes.data, clade.ctypes.data, n, parent.ctypes.data, rb if ranks else None, len(ranks),
+                                                 ids.ctypes.data if items else None, nb if items else None, len(items),
+                                                 sb.ctypes.data if sb.size else None, sr.ctypes.data if sb.size else None, sb.size,
+                                                 dk.ctypes.data, C.byref(out), C.byref(ob)) != 0:
+                raise HostIOError(lib().bnsh_last_error().decode())
+            return _take_blob(out, ob.value).decode()
         if lib().bnsh_format_report_distinct(direct.ctypes.data, clade.ctypes.data, n, parent.ctypes.data, rb if ranks else None, len(ranks),
                                              ids.ctypes.data if items else None, nb if items else None, len(items),
                                              sb.ctypes.data if sb.size else None, sr.ctypes.data if sb.size else None, sb.size,

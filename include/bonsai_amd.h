@@ -125,7 +125,8 @@ int bns_load_table_multi(bns_ctx **ctxs, int n_ctx, uint64_t n_buckets, const ui
  * opened) and the number of ranks of its communicator (0: no broadcast yet -- one context, or a db streamed per device).  A host prints
  * it so that a multi-GPU record says which collective library replicated the table over how many devices. */
 int bns_rccl_info(int *version, int *n_ranks);
-/* number of present keys / device bytes of the active table */
+/* number of present keys / device bytes of the active table.  n_keys is counted when the table is loaded, in every layout (a
+ * BNS_LAYOUT_KHASH load passes over the flag words once for it); bns_table_tally's sum(direct) equals it. */
 int bns_table_info(const bns_ctx *ctx, uint64_t *n_keys, uint64_t *device_bytes, int *layout);
 /* stats4 = {present keys, keys in the MINBUCKET overflow table, main table bytes, overflow table bytes} */
 int bns_table_stats(const bns_ctx *ctx, uint64_t *stats4);
@@ -178,6 +179,21 @@ int bns_load_taxonomy(bns_ctx *ctx, const uint32_t *parent, uint32_t n);
  * _device calls made on another stream must be complete.  Counts of several contexts add up (clade sums too). */
 int bns_tally_enable(bns_ctx *ctx, int on);
 int bns_tally_read(bns_ctx *ctx, uint64_t *direct, uint64_t *clade, uint32_t len, int reset);
+
+/* ---- per-taxon key counts of the loaded table (what `bonsai inspect` and `bonsai classify -R -u -d` report) ------------------------
+ * No reference counterpart (Kraken 2's kraken2-inspect, the denominator of KrakenUniq's cov column); defined in DESIGN.md.
+ * Every key present in the context's active table is counted exactly once, whatever the layout and wherever the loader put it (khash
+ * slots that are empty or deleted do not count; home, spill-only and overflow buckets of the clustered layout all do).  A key's value
+ * t goes to bns_tally_enable's bins: bin 0 for t = 0; bin t for a taxon t < n whose chain reaches a root; bin n for anything else.
+ * The same attribution as bns_sketch_enable's, so a clade's distinct-k-mer estimate over its key count is the share of its keys a
+ * sample covered.  direct[v] (may be NULL) = keys in bin v; clade[v] (may be NULL) = the sum over v's subtree (clade_kernel), bins 0 and n
+ * as they are.  sum(direct) == bns_table_info's n_keys, always.
+ * len must be n + 1, else BNS_ERR_ARG.  No table or no taxonomy: BNS_ERR_STATE.  One streaming walk of the table (inspect_*_kernel) on
+ * the context's stream; the scratch is allocated for the call and freed; no state is kept, the tally of bns_tally_enable and the
+ * sketches are not touched; nothing is launched or allocated unless this is called.
+ * Every context of a multi-GPU load holds the same table: each context's result is the whole answer.  Do NOT add the results of several
+ * contexts up (unlike bns_tally_read's). */
+int bns_table_tally(bns_ctx *ctx, uint64_t *direct, uint64_t *clade, uint32_t len);
 
 /* ---- confidence threshold (what `bonsai classify -t` sets) -------------------------------------------------------------------------
  * No reference counterpart: Kraken 2's --confidence, as defined in DESIGN.md.  theta = num / den, exact.  For each unit, Q = its hits +
