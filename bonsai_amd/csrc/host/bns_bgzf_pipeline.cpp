@@ -3,15 +3,6 @@
 #include "bns_text_pipeline.hpp"
 
 namespace bns {
-bool bgzf_gpu_wanted(const ClassifierGeneric &c, const char *fq1, const char *fq2)
-{
-    if (fq2 || c.get_emit_fastq()) return false;
-    if (const char *e = std::getenv("BNS_TEXT_GPU")) if (e[0] == '0') return false;
-    struct stat st;
-    if (::stat(fq1, &st) != 0 || !S_ISREG(st.st_mode)) return false;
-    return is_bgzf_file(fq1) && !std::getenv("BNS_NO_BGZF");
-}
-
 // A BGZF file as text in DEVICE memory, batch by batch in file order: compressed members up (pread into page-locked memory,
 // bns_inflate_members_device: one member per wavefront, thousands per batch, two batches side by side on inflater handles of their
 // own), their text left in HBM behind HEAD bytes of room (for what the caller could not finish of the batch in front: the record that
@@ -35,7 +26,6 @@ public:
         fd_ = ::open(path, O_RDONLY);
         if (fd_ < 0) die(std::string("Could not open ") + path + " for reading.");
         fsize_ = (u64)::lseek(fd_, 0, SEEK_END);
-        auto env_num = [](const char *name, u64 dflt) { const char *e = std::getenv(name); return e && std::atol(e) > 0 ? (u64)std::atol(e) : dflt; };
         MEMB_ = std::min<u64>(env_num("BNS_BGZF_BATCH_MEMBERS", 16384), 1u << 20);   // members per batch
         HEAD = std::min<u64>(env_num("BNS_BGZF_HEAD_MB", 64) << 20, 256ull << 20);   // room in front of a batch's text for what the batch before left
         if (const char *e = std::getenv("BNS_BGZF_HEAD_BYTES")) HEAD = (u64)std::max(4096L, std::min(256L << 20, std::atol(e)));       // (tests: windows of a few records)
@@ -56,9 +46,10 @@ public:
         // is touched (walking the headers over a mapping was a page fault per member: 1.8-2.5 s per 460 k members, the longest stage).
         // A batch = the members that START in a range (the one that straddles its end included: hence the slack).
         // CB: 96 MiB = ~3 k members a batch.  The member-per-wavefront inflate kernel is at its rate from ~4 k members in flight (two
-        // handles work side by side), and a slot is page-locked before its first use, 0.45 ms per MiB with the other threads' HIP calls
-        // waiting behind it: with 384 MiB ranges (what the member-per-lane kernel wanted) the GPU stood idle for the first 0.3 s of a
-        // file (profiles/r05_bgzf_trace.txt: 64 M reads 1.35 s with 384 MiB, 0.92 with 128, 0.88 with 96 and with 64, 1.04 with 48).
+        // handles work side by side), and a slot is page-locked before its first use (registered memory of our own, PinnedBuf::reserve:
+        // hipHostMalloc was 0.45 ms per MiB with every other thread's HIP calls waiting behind it -- the GPU idled through most of a file's
+        // first 0.15 s while five slots were made; BNS_PIN_MALLOC=1: as before): with 384 MiB ranges (what the member-per-lane kernel wanted)
+        // the GPU stood idle for the first 0.3 s of a file (profiles/r05_bgzf_trace.txt: 64 M reads 1.35 s with 384 MiB, 0.92 with 128, 0.88 with 96 and with 64, 1.04 with 48).
         const u64 CB = std::max<u64>(1u << 20, (u64)((double)(env_num("BNS_BGZF_RANGE_MB", 96) << 20) * range_scale));
         // (the FIRST range is short: a slot is page-locked before it is read -- 0.45 ms per MiB -- and nothing is inflated until the first one
         // is; one short range only: every size step re-allocates the inflaters' device buffers and the result arrays, a drained device each)
@@ -81,8 +72,14 @@ public:
             }
         } catch (...) { free_all(); throw; }
         t_begin_ = tnow();
+        // ---- readers: ranges of the file into page-locked slots (portable: whichever device inflates them), piece by piece
+        reader_ = std::make_unique<SlotReader<Slot>>(mu_, cv_, R, n_ranges_, NS_, READ_PIECE, "BGZF members", [this](Slot &sl, SlotReader<Slot>::Plan &p) {
+            sl.file_off = range_off_[sl.seq];
+            sl.bytes = (size_t)std::min<u64>(fsize_ - sl.file_off, range_off_[sl.seq + 1] - sl.file_off + SLACK);
+            p.ctx = dev_[sl.seq % G].ctx;
+            p.span[0] = {fd_, &sl.comp, sl.file_off, sl.bytes, sl.bytes + 256};
+        });
         splitter_ = std::thread([this] { split_loop(); });
-        for (unsigned r = 0; r < R; ++r) readers_.emplace_back([this] { read_loop(); });
         for (unsigned g = 0; g < G; ++g) for (unsigned i = 0; i < dev_[g].ni; ++i) inflaters_.emplace_back([this, g, i] { inflate_loop(g, dev_[g].handles[i]); });
     }
     // everybody home (the figures above are final after this)
@@ -90,14 +87,15 @@ public:
     {
         cancel();
         if (splitter_.joinable()) splitter_.join();
-        for (auto &t : readers_) if (t.joinable()) t.join();
+        reader_->join();
         for (auto &t : inflaters_) if (t.joinable()) t.join();
+        t_read = reader_->t_read; t_pin = reader_->t_pin;
     }
     ~BgzfDeviceSource() override
     {
         stop();
-        loaded_.clear(); inflated_.clear(); reading_.clear(); read_done_.clear();     // (their slots go back to spare_ while it still exists)
-        for (Slot *p : all_slots_) delete p;
+        loaded_.clear(); inflated_.clear();                    // (their slots go back to the reader while it still exists)
+        reader_.reset();
         free_all();
     }
     BgzfDeviceSource(const BgzfDeviceSource &) = delete;
@@ -110,10 +108,10 @@ public:
         Dev &d = dev_[g];
         std::unique_lock<std::mutex> lk(mu_);
         const double tw = tnow();
-        cv_.wait(lk, [&] { return cancel_ || inflated_.count(d.next_out) || d.next_out >= n_batches_; });
+        cv_.wait(lk, [&] { return reader_->cancelled() || inflated_.count(d.next_out) || d.next_out >= n_batches_; });
         t_wait_next += tnow() - tw;
         if (d.next_out == 0) t_first_inflated = tnow() - t_begin_;
-        if (cancel_ || !inflated_.count(d.next_out)) return false;
+        if (reader_->cancelled() || !inflated_.count(d.next_out)) return false;
         std::unique_ptr<Batch> b = std::move(inflated_[d.next_out]); inflated_.erase(d.next_out);
         it.seq = d.next_out; it.tbuf = b->tbuf; it.text_bytes = b->text_bytes; it.last = b->last;
         d.next_out += G;
@@ -126,8 +124,8 @@ public:
     {
         Dev &d = dev_[g];
         std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [&] { return cancel_ || !d.free_t.empty(); });
-        if (cancel_) return -1;
+        cv_.wait(lk, [&] { return reader_->cancelled() || !d.free_t.empty(); });
+        if (reader_->cancelled()) return -1;
         const int t = d.free_t.back(); d.free_t.pop_back();
         return t;
     }
@@ -135,8 +133,8 @@ public:
     bns_ctx *ctx(unsigned g) const override { return dev_[g].ctx; }
     unsigned devices() const override { return G; }
     void release(unsigned g, int t) override { std::lock_guard<std::mutex> lk(mu_); dev_[g].free_t.push_back(t); cv_.notify_all(); }
-    void cancel() override { std::lock_guard<std::mutex> lk(mu_); cancel_ = true; cv_.notify_all(); }
-    std::string error() override { std::lock_guard<std::mutex> lk(mu_); return error_; }
+    void cancel() override { std::lock_guard<std::mutex> lk(mu_); reader_->cancel(); }
+    std::string error() override { std::lock_guard<std::mutex> lk(mu_); return reader_->error(); }
 
     std::string timing_line() override
     {
@@ -166,7 +164,6 @@ private:
         std::vector<u32> in_len, out_len, want_crc, crc, status;
         int tbuf = -1;                                          // device text buffer it was inflated into
     };
-    struct Piece { Slot *s; size_t off, len; };
     static constexpr u64 SLACK = 65536 + 64;
 
     void free_all()
@@ -179,58 +176,7 @@ private:
         }
         if (fd_ >= 0) { ::close(fd_); fd_ = -1; }
     }
-    void fail_with(const std::string &w) { if (error_.empty()) error_ = w; cancel_ = true; cv_.notify_all(); }     // (mu_ held)
 
-    // ---- readers: ranges of the file into page-locked slots, piece by piece
-    void read_loop()
-    {
-        try {
-            for (;;) {
-                Piece pc{nullptr, 0, 0};
-                {
-                    std::unique_lock<std::mutex> lk(mu_);
-                    for (;;) {
-                        if (cancel_) return;
-                        if (!pieces_.empty()) { pc = pieces_.front(); pieces_.pop_front(); break; }
-                        if (next_range_ < n_ranges_ && (!spare_.empty() || all_slots_.size() < NS_)) {
-                            Slot *sl;
-                            if (!spare_.empty()) { sl = spare_.back(); spare_.pop_back(); }
-                            else { sl = new Slot(); all_slots_.push_back(sl); }
-                            sl->seq = next_range_++;
-                            sl->file_off = range_off_[sl->seq];
-                            sl->bytes = (size_t)std::min<u64>(fsize_ - sl->file_off, range_off_[sl->seq + 1] - sl->file_off + SLACK);
-                            reading_[sl->seq] = std::shared_ptr<Slot>(sl, [this](Slot *q) { std::lock_guard<std::mutex> g(mu_); spare_.push_back(q); cv_.notify_all(); });
-                            lk.unlock();
-                            const double tp0 = tnow();
-                            // (page-locked, portable: whichever device inflates it.  Registered memory of our own: hipHostMalloc was 0.45 ms per
-                            // MiB with every other thread's HIP calls waiting behind it -- the GPU idled through most of a file's first 0.15 s while
-                            // five slots were made; BNS_PIN_MALLOC=1: as before -- PinnedBuf::reserve)
-                            sl->comp.reserve(dev_[sl->seq % G].ctx, sl->bytes + 256);
-                            const double tp1 = tnow();
-                            lk.lock();
-                            t_pin += tp1 - tp0;
-                            const size_t PIECE = 8u << 20;
-                            unsigned np = 0;
-                            for (size_t o = 0; o < sl->bytes; o += PIECE) { pieces_.push_back(Piece{sl, o, std::min(PIECE, sl->bytes - o)}); ++np; }
-                            sl->pieces_left = np;
-                            if (!np) { read_done_[sl->seq] = std::move(reading_[sl->seq]); reading_.erase(sl->seq); }
-                            cv_.notify_all();
-                            continue;
-                        }
-                        if (next_range_ >= n_ranges_ && reading_.empty()) return;
-                        cv_.wait(lk);
-                    }
-                }
-                const double t0 = tnow();
-                pread_all(fd_, pc.s->comp.p + pc.off, pc.len, pc.s->file_off + pc.off, "BGZF members");
-                const double t1 = tnow();
-                std::lock_guard<std::mutex> lk(mu_);
-                t_read += t1 - t0;
-                if (--pc.s->pieces_left == 0) { const u64 q = pc.s->seq; read_done_[q] = std::move(reading_[q]); reading_.erase(q); }
-                cv_.notify_all();
-            }
-        } catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu_); fail_with(e.what()); }
-    }
     // ---- walker: the members of every range, in file order -> batches
     void split_loop()
     {
@@ -241,10 +187,11 @@ private:
                 {
                     std::unique_lock<std::mutex> lk(mu_);
                     const double tw = tnow();
-                    cv_.wait(lk, [&] { return cancel_ || read_done_.count(r); });
+                    cv_.wait(lk, [&] { return reader_->cancelled() || reader_->loaded(r); });
                     t_wait_walk += tnow() - tw;
-                    if (cancel_) return;
-                    sl = std::move(read_done_[r]); read_done_.erase(r);
+                    if (reader_->cancelled()) return;
+                    // (the slot goes back to the readers when the last batch that points into it lets go)
+                    sl = std::shared_ptr<Slot>(reader_->take(r).release(), [this](Slot *q) { std::lock_guard<std::mutex> g(mu_); reader_->give_back(std::unique_ptr<Slot>(q)); });
                 }
                 const double t0 = tnow();
                 const u64 range_end = range_off_[r + 1];
@@ -269,8 +216,7 @@ private:
                     if (at + msz > fsize_ || rel + msz > sl->bytes) die("truncated BGZF member");
                     if (msz < pay + 8) die("damaged BGZF member");
                     const unsigned char *t = buf + rel + msz - 8;
-                    const u32 crc = t[0] | ((u32)t[1] << 8) | ((u32)t[2] << 16) | ((u32)t[3] << 24);
-                    const u32 isize = t[4] | ((u32)t[5] << 8) | ((u32)t[6] << 16) | ((u32)t[7] << 24);
+                    const u32 crc = le32(t), isize = le32(t + 4);
                     if (isize > 65536u) die("damaged BGZF member (recorded text size above 64 KiB)");
                     if (isize) {
                         if (cur && (cur->in_off.size() >= MEMB_ || cur->text_bytes + isize > TEXT_MAX)) emit(false);      // (a range that inflates to more than a buffer holds: several batches)
@@ -286,7 +232,7 @@ private:
                 if (cur || file_done) emit(file_done);
                 if (file_done) break;
             }
-        } catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu_); fail_with(e.what()); }
+        } catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu_); reader_->fail(e.what()); }
     }
     // ---- inflaters: a handle each; device g's batches in file order, each into a free text buffer of that device (behind HEAD bytes of room)
     void inflate_loop(unsigned g, bns_inflater *h)
@@ -299,9 +245,9 @@ private:
                 {
                     std::unique_lock<std::mutex> lk(mu_);
                     const double tw = tnow();
-                    cv_.wait(lk, [&] { return cancel_ || (loaded_.count(d.next_inflate) && !d.free_t.empty()) || d.next_inflate >= n_batches_; });
+                    cv_.wait(lk, [&] { return reader_->cancelled() || (loaded_.count(d.next_inflate) && !d.free_t.empty()) || d.next_inflate >= n_batches_; });
                     t_wait_inf += tnow() - tw;
-                    if (cancel_ || !loaded_.count(d.next_inflate)) break;
+                    if (reader_->cancelled() || !loaded_.count(d.next_inflate)) break;
                     b = std::move(loaded_[d.next_inflate]); loaded_.erase(d.next_inflate); d.next_inflate += G;
                     tb = d.free_t.back(); d.free_t.pop_back();
                 }
@@ -326,7 +272,7 @@ private:
                 inflated_[seq] = std::move(b);
                 cv_.notify_all();
             }
-        } catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu_); fail_with(e.what()); }
+        } catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu_); reader_->fail(e.what()); }
     }
 
     std::vector<Dev> dev_;
@@ -336,16 +282,12 @@ private:
     std::vector<u64> range_off_;
     std::mutex mu_;
     std::condition_variable cv_;
-    std::vector<Slot *> spare_, all_slots_;                    // (slots go back to spare_ when the last batch that points into them lets go)
-    std::deque<Piece> pieces_;
-    std::map<u64, std::shared_ptr<Slot>> reading_, read_done_;
+    std::unique_ptr<SlotReader<Slot>> reader_;                 // (the cancel flag and the first error of all this source's threads are its)
     std::map<u64, std::unique_ptr<Batch>> loaded_, inflated_;
-    u64 next_range_ = 0, n_batches_ = ~0ULL;
-    bool cancel_ = false;
-    std::string error_;
+    u64 n_batches_ = ~0ULL;
     double t_begin_ = 0;
     std::thread splitter_;
-    std::vector<std::thread> readers_, inflaters_;
+    std::vector<std::thread> inflaters_;
 };
 
 // A BGZF file whose text never leaves the devices (process_device_text over BgzfDeviceSource's batches: batch b inflated on device b % G).
@@ -355,17 +297,6 @@ bool process_bgzf_gpu(ClassifierGeneric &c, const char *fq1, std::FILE *out, u64
     return process_device_text(c, src, out, units_done, "BGZF text");
 }
 
-
-bool bgzf_pair_gpu_wanted(const ClassifierGeneric &c, const char *fq1, const char *fq2)
-{
-    if (!fq2 || c.get_emit_fastq() || std::getenv("BNS_NO_BGZF")) return false;
-    if (const char *e = std::getenv("BNS_TEXT_GPU")) if (e[0] == '0') return false;
-    for (const char *p : {fq1, fq2}) {
-        struct stat st;
-        if (::stat(p, &st) != 0 || !S_ISREG(st.st_mode) || !is_bgzf_file(p)) return false;
-    }
-    return true;
-}
 
 // A PAIR of BGZF files on SEVERAL devices: batch b of either file is inflated on device b % G, the second file's ranges scaled by the
 // files' sizes so that batch b of either holds about the same records (both files hold the same number; what process_text_gpu_pair does

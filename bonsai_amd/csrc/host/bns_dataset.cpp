@@ -209,6 +209,37 @@ void load_packed_chunk(ClassifierGeneric &c, bns_ctx *ctx, int fd, u64 off, cons
     RecVec::publish();
     r.t_pack = tnow() - t0;
 }
+
+// ---- which inputs go to the device as text
+enum class InputKind { OTHER, PLAIN, BGZF, GZIP };
+// one look at a path: plain FASTA / FASTQ text, a BGZF file (is_bgzf_file's test), one plain gzip stream, or none of these (a path that is no regular file, too)
+InputKind sniff_input(const char *path)
+{
+    struct stat st;
+    if (::stat(path, &st) != 0 || !S_ISREG(st.st_mode)) return InputKind::OTHER;
+    const int f = ::open(path, O_RDONLY);
+    if (f < 0) return InputKind::OTHER;
+    unsigned char m[64];
+    const ssize_t n = ::pread(f, m, sizeof(m), 0);
+    ::close(f);
+    size_t pay = 0;
+    if (n >= 18 && bgzf_member(m, (size_t)n, pay) != 0) return InputKind::BGZF;
+    if (n >= 3 && m[0] == 0x1f && m[1] == 0x8b) return m[2] == 8 && st.st_size >= 18 ? InputKind::GZIP : InputKind::OTHER;
+    if (n >= 2 && (m[0] == '>' || m[0] == '@' || m[0] == '\n')) return InputKind::PLAIN;
+    return InputKind::OTHER;
+}
+// the device-text route of an input (OTHER: none, the host reader's); a pair takes a route only when both files are of that kind
+InputKind device_text_route(const ClassifierGeneric &c, const char *fq1, const char *fq2)
+{
+    if (c.get_emit_fastq()) return InputKind::OTHER;           // (FASTQ-style output prints bases and qualities: the host parser has them)
+    if (const char *e = std::getenv("BNS_TEXT_GPU")) if (e[0] == '0') return InputKind::OTHER;
+    if (is_pack_container(fq1)) return InputKind::OTHER;
+    const InputKind k = sniff_input(fq1);
+    if (fq2 && sniff_input(fq2) != k) return InputKind::OTHER;
+    if (k == InputKind::BGZF && std::getenv("BNS_NO_BGZF")) return InputKind::OTHER;     // (not the gzip route either: a BGZF file is many small members)
+    if (k == InputKind::GZIP) if (const char *e = std::getenv("BNS_GZ_GPU")) if (e[0] == '0') return InputKind::OTHER;
+    return k;
+}
 }  // namespace
 
 
@@ -217,36 +248,26 @@ void process_dataset(ClassifierGeneric &c, const char *fq1, const char *fq2, std
 {
     int is_paired = fq2 != nullptr;
     const int fd = fileno(out);
-    // one plain FASTA / FASTQ file: parsed, packed and classified on the device from its bytes (process_text_gpu); whatever the kernels
-    // hand back (text that is not in their regular form) is parsed here, from the record boundary they stopped at
-    u64 text_begin = 0;
-    if (!is_pack_container(fq1) && text_gpu_wanted(c, fq1, fq2)) {
+    // Text parsed, packed and classified on the device from the input's bytes.  Where such a route stops short (text that is not in the
+    // kernels' regular form, a stream the device decoder does not take), ONE plain file says where: the host parser goes on from
+    // text_begin, the record boundary the kernels stopped at.  Every other route says how many units it printed: the host reader takes
+    // the whole input and leaves out the first skip_units.
+    u64 text_begin = 0, skip_units = 0;
+    switch (device_text_route(c, fq1, fq2)) {
+    case InputKind::PLAIN: {    // the file(s) as text on the device; a pair: mates by record index
+        if (fq2) { if (process_text_gpu_pair(c, fq1, fq2, out, skip_units)) return; break; }
         struct stat st;
         text_begin = process_text_gpu(c, fq1, out);
         if (::stat(fq1, &st) == 0 && text_begin >= (u64)st.st_size) return;
+        break;
     }
-    // a BGZF file: members inflated on the device, their text parsed and classified where it lies (process_bgzf_gpu).  Text the kernels
-    // hand back: the whole file goes through the host parser, which leaves out the units that were printed already
-    u64 skip_units = 0;
-    if (!is_pack_container(fq1) && bgzf_gpu_wanted(c, fq1, fq2)) {
-        if (process_bgzf_gpu(c, fq1, out, skip_units)) return;
-    }
-    // one plain gzip file: the stream entered at block headers found on the device, inflated, parsed and classified there (process_gz_gpu);
-    // same rule for what it hands back -- and for a stream the device decoder does not take
-    else if (!is_pack_container(fq1) && gz_gpu_wanted(c, fq1, fq2)) {
-        if (process_gz_gpu(c, fq1, out, skip_units)) return;
-    }
-    // a pair of plain gzip files: both streams inflated on the device, mates paired there (process_gz_gpu_pair); same rule
-    else if (!is_pack_container(fq1) && gz_pair_gpu_wanted(c, fq1, fq2)) {
-        if (process_gz_gpu_pair(c, fq1, fq2, out, skip_units)) return;
-    }
-    // a pair of BGZF files: both inflated on the device and paired there (process_bgzf_gpu_pair); same rule for what it hands back
-    if (!is_pack_container(fq1) && bgzf_pair_gpu_wanted(c, fq1, fq2)) {
-        if (process_bgzf_gpu_pair(c, fq1, fq2, out, skip_units)) return;
-    }
-    // a pair of plain files: both as text on the device, mates by record index (process_text_gpu_pair); same rule for what it hands back
-    else if (!is_pack_container(fq1) && pair_gpu_wanted(c, fq1, fq2)) {
-        if (process_text_gpu_pair(c, fq1, fq2, out, skip_units)) return;
+    case InputKind::BGZF:       // members inflated on the device, their text parsed and classified where it lies; a pair: paired there
+        if (fq2 ? process_bgzf_gpu_pair(c, fq1, fq2, out, skip_units) : process_bgzf_gpu(c, fq1, out, skip_units)) return;
+        break;
+    case InputKind::GZIP:       // the stream(s) entered at block headers found on the device, inflated, parsed and classified there
+        if (fq2 ? process_gz_gpu_pair(c, fq1, fq2, out, skip_units) : process_gz_gpu(c, fq1, out, skip_units)) return;
+        break;
+    case InputKind::OTHER: break;
     }
     // a pre-packed read container (`bonsai pack`): no parser and no packer -- every chunk goes from the file into the page-locked
     // buffers of the GPU call (load_packed_chunk, several loader threads per device: one pread stream is ~6 GB/s)

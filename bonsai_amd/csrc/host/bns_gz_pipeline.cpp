@@ -6,27 +6,6 @@
 
 namespace bns {
 
-bool gz_gpu_wanted(const ClassifierGeneric &c, const char *fq1, const char *fq2)
-{
-    if (fq2 || c.get_emit_fastq()) return false;
-    if (const char *e = std::getenv("BNS_TEXT_GPU")) if (e[0] == '0') return false;
-    if (const char *e = std::getenv("BNS_GZ_GPU")) if (e[0] == '0') return false;
-    struct stat st;
-    if (::stat(fq1, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 18) return false;
-    unsigned char m[3] = {0, 0, 0};
-    const int f = ::open(fq1, O_RDONLY);
-    if (f < 0) return false;
-    const bool gz = ::pread(f, m, 3, 0) == 3 && m[0] == 0x1f && m[1] == 0x8b && m[2] == 8;
-    ::close(f);
-    return gz && !is_bgzf_file(fq1);
-}
-
-// a pair of such files (R1.fastq.gz + R2.fastq.gz: what the reference's process_dataset is usually given, classifier.h:296-337)
-bool gz_pair_gpu_wanted(const ClassifierGeneric &c, const char *fq1, const char *fq2)
-{
-    return fq2 && gz_gpu_wanted(c, fq1, nullptr) && gz_gpu_wanted(c, fq2, nullptr);
-}
-
 namespace {
 // The file as text in DEVICE memory, batch by batch.  Readers pread the file into page-locked SLOTS (slot r = file bytes
 // [r * P, (r + 1) * P + OVER): a call takes whole DEFLATE blocks only, so what it leaves of its slot's tail is in the next slot's head);
@@ -46,7 +25,6 @@ public:
         fd_ = ::open(path, O_RDONLY);
         if (fd_ < 0) die(std::string("Could not open ") + path + " for reading.");
         fsize_ = (u64)::lseek(fd_, 0, SEEK_END);
-        auto env_num = [](const char *name, u64 dflt) { const char *e = std::getenv(name); return e && std::atol(e) > 0 ? (u64)std::atol(e) : dflt; };
         // P: 256 MiB of compressed bytes a call = ~4600 chunks of 64 KiB, what fills the device's 3584 decoder wavefronts (128 MiB: 1.10 s of
         // kernels per 20 GB of text, 256: 0.90, 64: 1.90 -- profiles/r06_gz.txt)
         P_ = std::min<u64>(std::max<u64>(env_num("BNS_GZ_PIECE_MB", 256) << 20, 1u << 20), 1024ull << 20);
@@ -75,16 +53,21 @@ public:
         if (tnow() - t_alloc0 > 0.1 && std::getenv("BNS_CLI_TIMING"))
             std::fprintf(stderr, "[timing] gzip source: device buffers (3 x %.2f GB of text, the decoder's for %.0f MiB calls) took %.3f s to allocate\n",
                          (double)(HEAD + TEXT_MAX) / 1e9, (double)std::min<u64>(fsize_, P_ + OVER_) / 1048576.0, tnow() - t_alloc0);
-        for (unsigned r = 0; r < R_; ++r) readers_.emplace_back([this] { read_loop(); });
+        // ---- readers: slots of the file into page-locked memory, piece by piece, at most three slots ahead of the caller
+        reader_ = std::make_unique<SlotReader<Slot>>(mu_, cv_, R_, n_slots_, 3, READ_PIECE, "gzip stream", [this](Slot &sl, SlotReader<Slot>::Plan &p) {
+            sl.file_off = sl.seq * P_;
+            sl.bytes = (size_t)std::min<u64>(fsize_ - sl.file_off, P_ + OVER_);
+            p.ctx = ctx_;
+            p.span[0] = {fd_, &sl.comp, sl.file_off, sl.bytes, sl.bytes + 256};
+        });
         caller_ = std::thread([this] { call_loop(); });
     }
     ~GzDeviceSource() override
     {
         const double t0 = tnow();
         stop();
-        ready_.clear(); reading_.clear();
         const double t1 = tnow();
-        for (Slot *p : all_slots_) delete p;
+        reader_.reset();
         const double t2 = tnow();
         free_all();
         if (tnow() - t0 > 0.1 && std::getenv("BNS_CLI_TIMING"))
@@ -97,9 +80,9 @@ public:
     {
         std::unique_lock<std::mutex> lk(mu_);
         const double tw = tnow();
-        cv_.wait(lk, [&] { return cancel_ || !out_.empty() || done_; });
+        cv_.wait(lk, [&] { return reader_->cancelled() || !out_.empty() || done_; });
         t_wait_next += tnow() - tw;
-        if (cancel_ || out_.empty()) return false;
+        if (reader_->cancelled() || out_.empty()) return false;
         it = out_.front(); out_.pop_front();
         ++next_out_;
         return true;
@@ -109,14 +92,15 @@ public:
     bns_ctx *ctx(unsigned) const override { return ctx_; }
     unsigned devices() const override { return 1; }
     void release(unsigned, int t) override { std::lock_guard<std::mutex> lk(mu_); free_t_.push_back(t); cv_.notify_all(); }
-    void cancel() override { std::lock_guard<std::mutex> lk(mu_); cancel_ = true; cv_.notify_all(); }
-    std::string error() override { std::lock_guard<std::mutex> lk(mu_); return error_; }
+    void cancel() override { std::lock_guard<std::mutex> lk(mu_); reader_->cancel(); }
+    std::string error() override { std::lock_guard<std::mutex> lk(mu_); return reader_->error(); }
     bool gave_up() override { std::lock_guard<std::mutex> lk(mu_); return gave_up_; }
     void stop() override
     {
         cancel();
-        for (auto &t : readers_) if (t.joinable()) t.join();
+        reader_->join();
         if (caller_.joinable()) caller_.join();
+        t_read = reader_->t_read; t_pin = reader_->t_pin;
     }
     std::string timing_line() override
     {
@@ -129,8 +113,7 @@ public:
     }
 
 private:
-    struct Slot { PinnedBuf comp; u64 r = 0, file_off = 0; size_t bytes = 0; unsigned pieces_left = 0; };
-    struct Piece { Slot *s; size_t off, len; };
+    struct Slot { PinnedBuf comp; u64 seq = 0, file_off = 0; size_t bytes = 0; unsigned pieces_left = 0; };
 
     void free_all()
     {
@@ -140,81 +123,32 @@ private:
         if (d_window_) { bns_dev_free(ctx_, d_window_); d_window_ = nullptr; }
         if (fd_ >= 0) { ::close(fd_); fd_ = -1; }
     }
-    void fail_with(const std::string &w) { if (error_.empty()) error_ = w; cancel_ = true; cv_.notify_all(); }     // (mu_ held)
-
-    // ---- readers: slots of the file into page-locked memory, piece by piece, at most three slots ahead of the caller
-    void read_loop()
-    {
-        try {
-            for (;;) {
-                Piece pc{nullptr, 0, 0};
-                {
-                    std::unique_lock<std::mutex> lk(mu_);
-                    for (;;) {
-                        if (cancel_ || done_) return;
-                        if (!pieces_.empty()) { pc = pieces_.front(); pieces_.pop_front(); break; }
-                        if (next_slot_ < n_slots_ && (!spare_.empty() || all_slots_.size() < 3)) {
-                            Slot *sl;
-                            if (!spare_.empty()) { sl = spare_.back(); spare_.pop_back(); }
-                            else { sl = new Slot(); all_slots_.push_back(sl); }
-                            sl->r = next_slot_++;
-                            sl->file_off = sl->r * P_;
-                            sl->bytes = (size_t)std::min<u64>(fsize_ - sl->file_off, P_ + OVER_);
-                            reading_[sl->r] = sl;
-                            lk.unlock();
-                            const double tp0 = tnow();
-                            sl->comp.reserve(ctx_, sl->bytes + 256);
-                            const double tp1 = tnow();
-                            lk.lock();
-                            t_pin += tp1 - tp0;
-                            const size_t PIECE = 8u << 20;
-                            unsigned np = 0;
-                            for (size_t o = 0; o < sl->bytes; o += PIECE) { pieces_.push_back(Piece{sl, o, std::min(PIECE, sl->bytes - o)}); ++np; }
-                            sl->pieces_left = np;
-                            if (!np) { ready_[sl->r] = sl; reading_.erase(sl->r); }
-                            cv_.notify_all();
-                            continue;
-                        }
-                        if (next_slot_ >= n_slots_ && reading_.empty()) return;
-                        cv_.wait(lk);
-                    }
-                }
-                const double t0 = tnow();
-                pread_all(fd_, pc.s->comp.p + pc.off, pc.len, pc.s->file_off + pc.off, "gzip stream");
-                const double t1 = tnow();
-                std::lock_guard<std::mutex> lk(mu_);
-                t_read += t1 - t0;
-                if (--pc.s->pieces_left == 0) { ready_[pc.s->r] = pc.s; reading_.erase(pc.s->r); }
-                cv_.notify_all();
-            }
-        } catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu_); fail_with(e.what()); }
-    }
 
     // slot r, read (nullptr: cancelled); the slots in front of it go back to the readers
     Slot *slot(u64 r)
     {
         std::unique_lock<std::mutex> lk(mu_);
-        for (auto it = ready_.begin(); it != ready_.end() && it->first < r;) { spare_.push_back(it->second); it = ready_.erase(it); cv_.notify_all(); }
+        while (reader_->first_loaded() < r) reader_->give_back(reader_->take(reader_->first_loaded()));
         const double tw = tnow();
-        cv_.wait(lk, [&] { return cancel_ || ready_.count(r); });
+        cv_.wait(lk, [&] { return reader_->cancelled() || reader_->loaded(r); });
         t_wait_slot += tnow() - tw;
-        return cancel_ ? nullptr : ready_[r];
+        return reader_->cancelled() ? nullptr : reader_->peek(r);
     }
     // slot r if it has been read already (no waiting)
-    Slot *peek(u64 r) { std::lock_guard<std::mutex> lk(mu_); auto it = ready_.find(r); return it == ready_.end() ? nullptr : it->second; }
+    Slot *peek(u64 r) { std::lock_guard<std::mutex> lk(mu_); return reader_->peek(r); }
     // a slot's bytes to the device ahead of the calls on it (bns_inflate_stream_prefetch: on a stream of its own, under the kernels of the
     // calls on the slot in front); once per slot
     void bring_up(Slot *sl)
     {
-        if (!prefetch_ || sl->r < next_up_) return;
+        if (!prefetch_ || sl->seq < next_up_) return;
         if (bns_inflate_stream_prefetch(h_, reinterpret_cast<const uint8_t *>(sl->comp.p), sl->bytes) != BNS_OK) die(std::string("bns_inflate_stream_prefetch: ") + bns_inflater_error(h_));
-        next_up_ = sl->r + 1;
+        next_up_ = sl->seq + 1;
     }
     void give_up(const std::string &why)
     {
         std::lock_guard<std::mutex> lk(mu_);
         gave_up_ = true; done_ = true; why_ = "; gave up: " + why;
-        cv_.notify_all();
+        reader_->stop_opening();
     }
     void emit(int tbuf, u64 text_bytes, bool last)
     {
@@ -222,7 +156,7 @@ private:
         Item it; it.seq = n_emitted_++; it.tbuf = tbuf; it.text_bytes = text_bytes; it.last = last;
         out_.push_back(it);
         text_total += text_bytes;
-        if (last) { n_batches_ = n_emitted_; done_ = true; }
+        if (last) { n_batches_ = n_emitted_; done_ = true; reader_->stop_opening(); }
         cv_.notify_all();
     }
 
@@ -258,9 +192,9 @@ private:
                 {
                     std::unique_lock<std::mutex> lk(mu_);
                     const double tw = tnow();
-                    cv_.wait(lk, [&] { return cancel_ || !free_t_.empty(); });
+                    cv_.wait(lk, [&] { return reader_->cancelled() || !free_t_.empty(); });
                     t_wait_buf += tnow() - tw;
-                    if (cancel_) return;
+                    if (reader_->cancelled()) return;
                     tb = free_t_.back(); free_t_.pop_back();
                 }
                 bns_gz_result res{};
@@ -320,9 +254,7 @@ private:
                     Slot *ts = sl;
                     if (tr + 8 + 4096 > sl->file_off + sl->bytes && !final_slot) { ts = slot(r + 1); if (!ts) { release(0, tb); return; } }
                     const unsigned char *t = reinterpret_cast<const unsigned char *>(ts->comp.p) + (tr - ts->file_off);
-                    const u32 want_crc = t[0] | ((u32)t[1] << 8) | ((u32)t[2] << 16) | ((u32)t[3] << 24);
-                    const u32 want_isize = t[4] | ((u32)t[5] << 8) | ((u32)t[6] << 16) | ((u32)t[7] << 24);
-                    if (crc != want_crc || (u32)isize != want_isize) die("gzip member does not inflate to its recorded checksum and size");
+                    if (crc != le32(t) || (u32)isize != le32(t + 4)) die("gzip member does not inflate to its recorded checksum and size");
                     { std::lock_guard<std::mutex> lk(mu_); ++n_members; }
                     tr += 8;
                     // (a file of MANY SMALL members -- gzip members of a few hundred KB that are not BGZF -- is a call and a drained stream per
@@ -341,7 +273,7 @@ private:
                 else release(0, tb);
                 if (last) return;
             }
-        } catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu_); fail_with(e.what()); }
+        } catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu_); reader_->fail(e.what()); }
     }
 
     bns_ctx *ctx_;
@@ -355,18 +287,15 @@ private:
     std::vector<int> free_t_;
     std::mutex mu_;
     std::condition_variable cv_;
-    std::vector<Slot *> spare_, all_slots_;
-    std::deque<Piece> pieces_;
-    std::map<u64, Slot *> reading_, ready_;
+    std::unique_ptr<SlotReader<Slot>> reader_;                 // (the cancel flag and the first error of all this source's threads are its)
     std::deque<Item> out_;
-    u64 next_slot_ = 0, n_emitted_ = 0, next_out_ = 0, n_batches_ = ~0ULL;
-    bool cancel_ = false, done_ = false, gave_up_ = false;
+    u64 n_emitted_ = 0, next_out_ = 0, n_batches_ = ~0ULL;
+    bool done_ = false, gave_up_ = false;
     bool prefetch_ = true, room_retry_ = true;
     unsigned room_default_ = 16;
     u64 n_room_ = 0;                                           // calls asked again with more room
     u64 next_up_ = 0;                                          // slots below this one have been brought up
-    std::string error_, why_;
-    std::vector<std::thread> readers_;
+    std::string why_;
     std::thread caller_;
 };
 }  // namespace

@@ -65,6 +65,9 @@ inline void pread_all(int fd, void *dst, size_t n, u64 at, const char *what)
         got += (size_t)r;
     }
 }
+// a number from the environment (unset, or not above zero: dflt)
+inline u64 env_num(const char *name, u64 dflt) { const char *e = std::getenv(name); return e && std::atol(e) > 0 ? (u64)std::atol(e) : dflt; }
+inline u32 le32(const unsigned char *p) { return p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); }
 
 // ---- text blocks of the host reader (bns_reader.cpp) and of ChunkSource (bns_chunks.cpp)
 constexpr size_t TEXT_BLOCK_HEAD = 64u << 10;                    // room in front of a raw block's text for the unparsed tail of the block before it
@@ -177,20 +180,14 @@ inline char *kraken_line_raw(char *w, const HitRuns &runs, tax_t taxon, u32 ambi
 void pack_chunk(ClassifierGeneric &c, bns_ctx *ctx, const bseq1_t *bs, unsigned n, int is_paired, ChunkResult &r, unsigned copy_threads);
 void call_chunk(bns_ctx *ctx, ChunkResult &r);
 
-// ---- text parsed on the device (bns_text_pipeline.cpp): which inputs take that path, and the pipelines.  -> how far they got: the file
-// offset the host parser goes on from (one plain file), or false + the units that were printed (the host parser reads the input again
-// and leaves those out)
-bool text_gpu_wanted(const ClassifierGeneric &c, const char *fq1, const char *fq2);
-bool pair_gpu_wanted(const ClassifierGeneric &c, const char *fq1, const char *fq2);
-bool bgzf_gpu_wanted(const ClassifierGeneric &c, const char *fq1, const char *fq2);
-bool bgzf_pair_gpu_wanted(const ClassifierGeneric &c, const char *fq1, const char *fq2);
+// ---- text parsed on the device (bns_text_pipeline.cpp, bns_bgzf_pipeline.cpp, bns_gz_pipeline.cpp): the pipelines; process_dataset picks
+// the route.  -> how far they got: the file offset the host parser goes on from (one plain file), or false + the units that were printed
+// (the host parser reads the input again and leaves those out)
 u64 process_text_gpu(ClassifierGeneric &c, const char *fq1, std::FILE *out);
 bool process_text_gpu_pair(ClassifierGeneric &c, const char *fq1, const char *fq2, std::FILE *out, u64 &units_done);
 bool process_bgzf_gpu(ClassifierGeneric &c, const char *fq1, std::FILE *out, u64 &units_done);
 bool process_bgzf_gpu_pair(ClassifierGeneric &c, const char *fq1, const char *fq2, std::FILE *out, u64 &units_done);
-bool gz_gpu_wanted(const ClassifierGeneric &c, const char *fq1, const char *fq2);
 bool process_gz_gpu(ClassifierGeneric &c, const char *fq1, std::FILE *out, u64 &units_done);
-bool gz_pair_gpu_wanted(const ClassifierGeneric &c, const char *fq1, const char *fq2);
 bool process_gz_gpu_pair(ClassifierGeneric &c, const char *fq1, const char *fq2, std::FILE *out, u64 &units_done);
 
 }  // namespace bns

@@ -51,20 +51,6 @@ unsigned format_text_job(ClassifierGeneric &c, const TextJob &j, std::vector<Cla
     return nt;
 }
 
-bool text_gpu_wanted(const ClassifierGeneric &c, const char *fq1, const char *fq2)
-{
-    if (fq2 || c.get_emit_fastq()) return false;               // (FASTQ-style output prints bases and qualities: the host parser has them)
-    if (const char *e = std::getenv("BNS_TEXT_GPU")) if (e[0] == '0') return false;
-    struct stat st;
-    if (::stat(fq1, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 2) return false;
-    unsigned char m[2] = {0, 0};
-    const int f = ::open(fq1, O_RDONLY);
-    if (f < 0) return false;
-    const bool plain = ::pread(f, m, 2, 0) == 2 && !(m[0] == 0x1f && m[1] == 0x8b) && (m[0] == '>' || m[0] == '@' || m[0] == '\n');
-    ::close(f);
-    return plain;
-}
-
 // -> the file offset the host parser has to go on from (== the file's size: nothing left)
 u64 process_text_gpu(ClassifierGeneric &c, const char *fq1, std::FILE *out)
 {
@@ -78,99 +64,45 @@ u64 process_text_gpu(ClassifierGeneric &c, const char *fq1, std::FILE *out)
     (void)!::pread(fd, &first_byte, 1, 0);
     const bool fastq = first_byte == '@';
     const unsigned G = (unsigned)c.ctxs_.size();
-    auto env_mb = [](const char *name, u64 dflt) { const char *e = std::getenv(name); return e && std::atol(e) > 0 ? (u64)std::atol(e) << 20 : dflt; };
     // (64 MiB: one upload piece.  Against 128 MiB on one box, interleaved, 256 M reads: -K 1.78-1.95 s against 1.91-1.99, Kraken lines
     // 2.20-2.34 against 2.22-2.86 -- half the page-locked memory to set up at the start, the formatters fed in smaller portions;
     // tools/r05_block_ab.sh, profiles/r05_cli_blocks.txt)
-    u64 B = std::min<u64>(env_mb("BNS_TEXT_BLOCK_MB", 64ull << 20), 1ull << 30);
-    u64 SLACK = std::min<u64>(env_mb("BNS_TEXT_SLACK_MB", 4ull << 20), B);
+    u64 B = std::min<u64>(env_num("BNS_TEXT_BLOCK_MB", 64) << 20, 1ull << 30);
+    u64 SLACK = std::min<u64>(env_num("BNS_TEXT_SLACK_MB", 4) << 20, B);
     if (const char *e = std::getenv("BNS_TEXT_BLOCK_BYTES")) { B = (u64)std::max(64L, std::atol(e)); SLACK = std::min<u64>(SLACK, std::max<u64>(B / 2, 2048)); }   // (tests: many blocks on small files)
     const u64 n_blocks = std::max<u64>(1, (fsize + B - 1) / B);
     unsigned R = (unsigned)std::max(2, std::min(8, usable_cpus() / 2));
     if (const char *e = std::getenv("BNS_TEXT_READERS")) R = (unsigned)std::max(1, std::min(32, std::atoi(e)));
-    const size_t PIECE = 8u << 20;
     const bool want_runs = c.get_emit_kraken() != 0;
     const bool taxon_only = !want_runs;                        // (-K: the tally and the -b file read the taxon alone)
     const bool timing = std::getenv("BNS_CLI_TIMING") != nullptr;
 
     std::mutex mu;
     std::condition_variable cv;
-    std::vector<std::unique_ptr<TextJob>> spare;               // recycled jobs (their page-locked buffers with them)
-    unsigned jobs_made = 0;
     const bool dev_lines = lines_on_device(c);
     unsigned max_jobs = 2 * G + 4 + (dev_lines ? 2 : 0);        // blocks in flight: in a call, uploaded ahead of it (prefetch), read ahead of that, being formatted (device lines: until written)
     if (const char *e = std::getenv("BNS_TEXT_JOBS")) max_jobs = (unsigned)std::max(2, std::min(64, std::atoi(e)));
-    struct Piece { TextJob *job; size_t off, len; };
-    std::deque<Piece> pieces;                                  // reads to do
-    std::map<u64, std::unique_ptr<TextJob>> loading, loaded, done;
-    u64 next_load = 0, next_verify = 0;
+    // ---- readers: block b = B + SLACK bytes at b * B, into a job from the pool (the jobs come back from the sink: their page-locked
+    // buffers with them); the reader's cancel flag and first error are this function's, for all its threads
+    SlotReader<TextJob> rd(mu, cv, R, n_blocks, max_jobs, READ_PIECE, "text block", [&](TextJob &j, SlotReader<TextJob>::Plan &p) {
+        j.file_off = j.seq * B;
+        j.bytes = (size_t)std::min<u64>(fsize - j.file_off, B + SLACK);
+        j.last = j.file_off + j.bytes >= fsize;
+        j.guessed = j.ok = j.prefetched = false; j.n_records = 0; j.status = 0; j.why = 0;
+        p.ctx = c.ctxs_[j.seq % G];
+        p.span[0] = {fd, &j.text, j.file_off, j.bytes, (size_t)(B + SLACK) + 256};     // (page-locks on first use: 0.2 ms per MiB, once per job)
+    });
+    std::map<u64, std::unique_ptr<TextJob>> done;
+    u64 next_verify = 0;
     u64 verified_end = 0;                                      // where the first record of block next_verify starts
     std::map<u64, u64> end_of;                                 // block -> where it stopped (as far as known)
     std::deque<std::unique_ptr<TextJob>> redo;                 // blocks whose guessed start was wrong
-    bool cancel = false, stop_loading = false;
     u64 resume_at = fsize;                                     // the host parser's share starts here (fsize: nothing)
-    std::string error;
-    double t_read = 0, t_call = 0, t_alloc = 0;
+    double t_call = 0;
     u64 n_guess = 0, n_redo = 0, n_ahead = 0;
     double t_idle = 0;                                         // callers waiting for a block to be read
-    auto fail_with = [&](const std::string &w) { if (error.empty()) error = w; cancel = true; cv.notify_all(); };
     // ---- formatters and the writer (file order): verified blocks go to the sink under their block number
-    TextSink sink(c, ofd, [&](std::unique_ptr<TextJob> j) { std::lock_guard<std::mutex> lk(mu); spare.push_back(std::move(j)); cv.notify_all(); });
-
-    // ---- readers: a loader hands out blocks (a job each, from the pool) cut into pieces; R threads pread the pieces
-    auto reader = [&] {
-        try {
-            for (;;) {
-                Piece pc{nullptr, 0, 0};
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    for (;;) {
-                        if (cancel) return;
-                        if (!pieces.empty()) { pc = pieces.front(); pieces.pop_front(); break; }
-                        // nothing to read: open the next block if a job is to be had
-                        if (!stop_loading && next_load < n_blocks && (!spare.empty() || jobs_made < max_jobs)) {
-                            std::unique_ptr<TextJob> j;
-                            if (!spare.empty()) { j = std::move(spare.back()); spare.pop_back(); }
-                            else { j = std::make_unique<TextJob>(); ++jobs_made; }
-                            j->seq = next_load++;
-                            j->file_off = j->seq * B;
-                            j->bytes = (size_t)std::min<u64>(fsize - j->file_off, B + SLACK);
-                            j->last = j->file_off + j->bytes >= fsize;
-                            j->guessed = j->ok = j->prefetched = false; j->n_records = 0; j->status = 0; j->why = 0;
-                            TextJob *jp = j.get();
-                            const u64 seq = j->seq;
-                            loading[seq] = std::move(j);
-                            lk.unlock();
-                            const double ta = tnow();
-                            jp->text.reserve(c.ctxs_[seq % G], (size_t)(B + SLACK) + 256);      // (page-locks on first use: 0.2 ms per MiB, once per job)
-                            const double tb = tnow();
-                            lk.lock();
-                            t_alloc += tb - ta;
-                            unsigned np = 0;
-                            for (size_t o = 0; o < jp->bytes; o += PIECE) { pieces.push_back(Piece{jp, o, std::min(PIECE, jp->bytes - o)}); ++np; }
-                            jp->pieces_left = np;
-                            if (!np) { loaded[seq] = std::move(loading[seq]); loading.erase(seq); }
-                            cv.notify_all();
-                            continue;
-                        }
-                        if (next_load >= n_blocks || stop_loading) { if (pieces.empty() && loading.empty()) return; }
-                        cv.wait(lk);
-                    }
-                }
-                const double t0 = tnow();
-                pread_all(fd, pc.job->text.p + pc.off, pc.len, pc.job->file_off + pc.off, "text block");
-                const double t1 = tnow();
-                std::lock_guard<std::mutex> lk(mu);
-                t_read += t1 - t0;
-                if (--pc.job->pieces_left == 0) {
-                    const u64 seq = pc.job->seq;
-                    loaded[seq] = std::move(loading[seq]);
-                    loading.erase(seq);
-                }
-                cv.notify_all();
-            }
-        } catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu); fail_with(e.what()); }
-    };
+    TextSink sink(c, ofd, [&](std::unique_ptr<TextJob> j) { std::lock_guard<std::mutex> lk(mu); rd.give_back(std::move(j)); });
 
     // ---- one library call on a block from a known (or guessed) start
     auto call_block = [&](bns_ctx *ctx, TextJob &j) {
@@ -178,22 +110,8 @@ u64 process_text_gpu(ClassifierGeneric &c, const char *fq1, std::FILE *out)
         u64 lines_cap = dev_lines ? ((j.bytes - rel) / 160 + 4096) * LINES_ROOM_PER_RECORD : 0;
         u64 cap = (j.bytes - rel) / 160 + 4096, names_cap = cap * 24, runs_cap = cap * 4;   // (316 bytes, ~10 of name and 1-3 hit runs per 150-bp FASTQ record; BNS_TEXT_CAP doubles them)
         for (;;) {
-            j.taxon.resize(ctx, cap);
             bns_text_out o{};
-            o.taxon = j.taxon.data();
-            j.dev_lines = dev_lines; j.lines_bytes = 0;
-            if (dev_lines) {
-                j.lines.resize(ctx, lines_cap);
-                o.lines = j.lines.data(); o.lines_cap = lines_cap; o.lines_flags = c.get_emit_all() ? BNS_LINES_ALL : 0u;
-            } else if (!taxon_only) {
-                j.missing.resize(ctx, cap); j.ambig.resize(ctx, cap); j.n_hits.resize(ctx, cap); j.seq_len.resize(ctx, cap); j.name_off.resize(ctx, cap + 1);
-                j.run_start.resize(ctx, cap); j.n_runs.resize(ctx, cap); j.names.resize(ctx, names_cap);
-                o.missing = j.missing.data(); o.ambig = j.ambig.data(); o.n_hits = j.n_hits.data(); o.seq_len = j.seq_len.data();
-                o.name_off = j.name_off.data(); o.names = j.names.data(); o.names_cap = names_cap;
-                o.run_start = j.run_start.data(); o.n_runs = j.n_runs.data();
-                j.run_tax.resize(ctx, runs_cap); j.run_len.resize(ctx, runs_cap);
-                o.run_tax = j.run_tax.data(); o.run_len = j.run_len.data(); o.runs_cap = runs_cap;
-            }
+            size_text_job(ctx, j, o, taxon_only, cap, names_cap, runs_cap, lines_cap, c.get_emit_all() != 0);
             bns_text_info info{};
             const char *tp = j.text.p + rel;
             const u64 tb = j.bytes - rel;
@@ -223,7 +141,7 @@ u64 process_text_gpu(ClassifierGeneric &c, const char *fq1, std::FILE *out)
                 return;
             }
             // the kernels do not take (all of) this text: what they took is printed, the host parser goes on from where they stopped
-            if (!j.ok) { resume_at = j.end; stop_loading = true; }
+            if (!j.ok) { resume_at = j.end; rd.stop_opening(); }
             verified_end = j.end;
             end_of[next_verify] = j.end;                       // (a fact now, whatever the block's caller guessed)
             sink.submit(std::move(it->second));                // (its seq is its block number: the sink prints in that order)
@@ -244,26 +162,26 @@ u64 process_text_gpu(ClassifierGeneric &c, const char *fq1, std::FILE *out)
                     std::unique_lock<std::mutex> lk(mu);
                     for (;;) {
                         const double tw0 = tnow();
-                        cv.wait(lk, [&] { return cancel || resume_at != fsize || !redo.empty() || loaded.count(mine) || (mine >= n_blocks && next_verify >= n_blocks); });
+                        cv.wait(lk, [&] { return rd.cancelled() || resume_at != fsize || !redo.empty() || rd.loaded(mine) || (mine >= n_blocks && next_verify >= n_blocks); });
                         if (mine < n_blocks) t_idle += tnow() - tw0;
-                        if (cancel || resume_at != fsize) return;
+                        if (rd.cancelled() || resume_at != fsize) return;
                         if (!redo.empty()) { j = std::move(redo.front()); redo.pop_front(); break; }
-                        if (!loaded.count(mine)) return;       // (every block is verified)
+                        if (!rd.loaded(mine)) return;       // (every block is verified)
                         const u64 b = mine;
-                        TextJob &nj = *loaded[b];
+                        TextJob &nj = *rd.peek(b);
                         if (b == 0) nj.start = 0;
                         else if (end_of.count(b - 1)) nj.start = end_of[b - 1];
                         else {                                 // the block in front is still on another device: guess from the text
                             const long at = find_record_start(nj.text.p, std::min<size_t>(nj.bytes, (size_t)SLACK), fastq);
-                            if (at < 0) { cv.wait(lk, [&] { return cancel || resume_at != fsize || end_of.count(b - 1) || !redo.empty(); }); continue; }
+                            if (at < 0) { cv.wait(lk, [&] { return rd.cancelled() || resume_at != fsize || end_of.count(b - 1) || !redo.empty(); }); continue; }
                             nj.start = nj.file_off + (u64)at; nj.guessed = true; ++n_guess;
                         }
-                        j = std::move(loaded[b]); loaded.erase(b);
+                        j = rd.take(b);
                         mine += G;
                         break;
                     }
-                    auto it = loaded.find(mine);
-                    if (it != loaded.end() && !it->second->prefetched) { ahead = it->second.get(); ahead->prefetched = true; ++n_ahead; }
+                    TextJob *nx = rd.peek(mine);
+                    if (nx && !nx->prefetched) { ahead = nx; ahead->prefetched = true; ++n_ahead; }
                 }
                 const double t0 = tnow();
                 if (j->start > j->file_off + j->bytes) die("text block: its first record starts behind its buffer");
@@ -281,29 +199,29 @@ u64 process_text_gpu(ClassifierGeneric &c, const char *fq1, std::FILE *out)
                 sequence();
                 cv.notify_all();
             }
-        } catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu); fail_with(e.what()); }
+        } catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu); rd.fail(e.what()); }
     };
 
-    std::vector<std::thread> readers, callers;
-    for (unsigned r = 0; r < R; ++r) readers.emplace_back(reader);
+    std::vector<std::thread> callers;
     for (unsigned g = 0; g < G; ++g) callers.emplace_back(caller, g);
     for (auto &t : callers) t.join();
     u64 n_final;
+    bool failed;
     {
         std::lock_guard<std::mutex> lk(mu);
         n_final = next_verify;                                 // every block up to here is verified (or the path has handed over there)
-        stop_loading = true;
-        cv.notify_all();
+        failed = !rd.error().empty();
+        rd.stop_opening();
     }
-    if (error.empty()) sink.finish(n_final); else sink.finish(0, true);
-    { std::lock_guard<std::mutex> lk(mu); cancel = true; cv.notify_all(); }
-    for (auto &t : readers) t.join();
+    if (!failed) sink.finish(n_final); else sink.finish(0, true);
+    { std::lock_guard<std::mutex> lk(mu); rd.cancel(); }
+    rd.join();
     for (bns_ctx *cx : c.ctxs_) (void)bns_text_prefetch(cx, nullptr, nullptr, 0);      // (blocks uploaded ahead of a call that never came: handed over, or failed)
-    if (!error.empty()) die(error);
+    if (!rd.error().empty()) die(rd.error());
     if (timing)
         std::fprintf(stderr, "[timing] text on the device: %llu blocks of %llu MiB on %u device(s), %u readers: page-lock %.3f s, pread %.3f (summed), calls %.3f (summed), format %.3f, write %.3f; "
                              "callers waited %.3f s for blocks, %llu uploads started ahead of their call; %llu guessed starts, %llu classified again%s%s\n",
-                     (unsigned long long)next_verify, (unsigned long long)(B >> 20), G, R, t_alloc, t_read, t_call, sink.t_format, sink.t_write, t_idle, (unsigned long long)n_ahead,
+                     (unsigned long long)next_verify, (unsigned long long)(B >> 20), G, R, rd.t_pin, rd.t_read, t_call, sink.t_format, sink.t_write, t_idle, (unsigned long long)n_ahead,
                      (unsigned long long)n_guess, (unsigned long long)n_redo, resume_at != fsize ? "; the host parser takes the rest" : "", sink.note().c_str());
     return resume_at;
 }
@@ -502,23 +420,6 @@ bool process_device_text_pair(ClassifierGeneric &c, DeviceTextSource &src0, Devi
     return !handed_back;
 }
 
-bool pair_gpu_wanted(const ClassifierGeneric &c, const char *fq1, const char *fq2)
-{
-    if (!fq2 || c.get_emit_fastq()) return false;
-    if (const char *e = std::getenv("BNS_TEXT_GPU")) if (e[0] == '0') return false;
-    for (const char *p : {fq1, fq2}) {
-        struct stat st;
-        if (::stat(p, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 2) return false;
-        unsigned char m[2] = {0, 0};
-        const int f = ::open(p, O_RDONLY);
-        if (f < 0) return false;
-        const bool plain = ::pread(f, m, 2, 0) == 2 && !(m[0] == 0x1f && m[1] == 0x8b) && (m[0] == '>' || m[0] == '@' || m[0] == '\n');
-        ::close(f);
-        if (!plain) return false;
-    }
-    return true;
-}
-
 // A PAIR of plain files as text on the device (bns_classify_text with two streams: record i of the one file and record i of the
 // other are mates, kseq_declare.h:116-131).  Two files cannot be cut at the same RECORD by byte offsets, so: file 1 is cut into
 // blocks at nominal offsets like a single file (block b = the records that start in it: `limit`); file 2 gets blocks of its own
@@ -544,9 +445,8 @@ bool process_text_gpu_pair(ClassifierGeneric &c, const char *fq1, const char *fq
     const int ofd = fileno(out);
     const unsigned G = (unsigned)c.ctxs_.size();
     const bool timing = std::getenv("BNS_CLI_TIMING") != nullptr;
-    auto env_mb = [](const char *name, u64 dflt) { const char *e = std::getenv(name); return e && std::atol(e) > 0 ? (u64)std::atol(e) << 20 : dflt; };
-    u64 B = std::min<u64>(env_mb("BNS_TEXT_BLOCK_MB", 96ull << 20), 1ull << 29);
-    u64 ROOM = env_mb("BNS_TEXT_ROOM_MB", 16ull << 20);        // file 2's buffer reaches this far in front of and behind its nominal block
+    u64 B = std::min<u64>(env_num("BNS_TEXT_BLOCK_MB", 96) << 20, 1ull << 29);
+    u64 ROOM = env_num("BNS_TEXT_ROOM_MB", 16) << 20;          // file 2's buffer reaches this far in front of and behind its nominal block
     u64 SLACK = 4ull << 20;
     if (const char *e = std::getenv("BNS_TEXT_BLOCK_BYTES")) { B = (u64)std::max(64L, std::atol(e)); ROOM = std::max<u64>(B, 4096); SLACK = std::max<u64>(B / 2, 2048); }   // (tests)
     const u64 n_blocks = std::max<u64>(1, (fsize[0] + B - 1) / B);
@@ -556,7 +456,6 @@ bool process_text_gpu_pair(ClassifierGeneric &c, const char *fq1, const char *fq
     auto off2 = [&](u64 b) { return (u64)((long double)b * (long double)B * (long double)fsize[1] / (long double)std::max<u64>(1, fsize[0])); };
     unsigned R = (unsigned)std::max(2, std::min(8, usable_cpus() / 2));
     if (const char *e = std::getenv("BNS_TEXT_READERS")) R = (unsigned)std::max(1, std::min(32, std::atoi(e)));
-    const size_t PIECE = 8u << 20;
 
     struct PairJob {
         u64 seq = 0;
@@ -568,74 +467,27 @@ bool process_text_gpu_pair(ClassifierGeneric &c, const char *fq1, const char *fq
     };
     std::mutex mu;
     std::condition_variable cv;
-    std::vector<std::unique_ptr<PairJob>> spare;
-    unsigned jobs_made = 0;
     const unsigned max_jobs = 3 * G + 2;                        // per device: in its call, uploaded ahead of it, being read
-    struct Piece { PairJob *j; int s; size_t off, len; };
-    std::deque<Piece> pieces;
-    std::map<u64, std::unique_ptr<PairJob>> loading, loaded;
-    u64 next_load = 0;
-    bool cancel = false;
-    std::string error;
-    double t_read = 0, t_call = 0, t_idle = 0;
+    // ---- readers: block b of file 1 like a single file's, file 2's nominal block with ROOM on both sides; the reader's cancel flag and
+    // first error are this function's, for all its threads
+    SlotReader<PairJob> rd(mu, cv, R, n_blocks, max_jobs, READ_PIECE, "text block", [&](PairJob &j, SlotReader<PairJob>::Plan &p) {
+        const u64 b = j.seq;
+        j.prefetched = false;
+        j.off[0] = b * B;
+        j.bytes[0] = (size_t)std::min<u64>(fsize[0] - j.off[0], B + SLACK);
+        j.last = j.off[0] + j.bytes[0] >= fsize[0];
+        const u64 lo2 = off2(b) > ROOM ? off2(b) - ROOM : 0;
+        const u64 hi2 = (j.last || b + 1 == n_blocks) ? fsize[1] : std::min<u64>(fsize[1], off2(b + 1) + ROOM);
+        j.off[1] = std::min(lo2, fsize[1]);
+        j.bytes[1] = (size_t)(hi2 > j.off[1] ? hi2 - j.off[1] : 0);
+        p.ctx = c.ctxs_[b % G];
+        p.span[0] = {fds[0], &j.text[0], j.off[0], j.bytes[0], (size_t)std::max<u64>(B + SLACK, j.bytes[0]) + 256};
+        p.span[1] = {fds[1], &j.text[1], j.off[1], j.bytes[1], (size_t)std::max<u64>(B2 + 2 * ROOM, j.bytes[1]) + 256};
+    });
+    double t_call = 0, t_idle = 0;
     u64 n_ahead = 0;
-    auto fail_with = [&](const std::string &w) { if (error.empty()) error = w; cancel = true; cv.notify_all(); };
     JobPool pool;
     TextSink sink(c, ofd, [&](std::unique_ptr<TextJob> j) { pool.put(std::move(j)); });
-
-    auto reader = [&] {
-        try {
-            for (;;) {
-                Piece pc{nullptr, 0, 0, 0};
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    for (;;) {
-                        if (cancel) return;
-                        if (!pieces.empty()) { pc = pieces.front(); pieces.pop_front(); break; }
-                        if (next_load < n_blocks && (!spare.empty() || jobs_made < max_jobs)) {
-                            std::unique_ptr<PairJob> j;
-                            if (!spare.empty()) { j = std::move(spare.back()); spare.pop_back(); }
-                            else { j = std::make_unique<PairJob>(); ++jobs_made; }
-                            const u64 b = j->seq = next_load++;
-                            j->prefetched = false;
-                            j->off[0] = b * B;
-                            j->bytes[0] = (size_t)std::min<u64>(fsize[0] - j->off[0], B + SLACK);
-                            j->last = j->off[0] + j->bytes[0] >= fsize[0];
-                            const u64 lo2 = off2(b) > ROOM ? off2(b) - ROOM : 0;
-                            const u64 hi2 = (j->last || b + 1 == n_blocks) ? fsize[1] : std::min<u64>(fsize[1], off2(b + 1) + ROOM);
-                            j->off[1] = std::min(lo2, fsize[1]);
-                            j->bytes[1] = (size_t)(hi2 > j->off[1] ? hi2 - j->off[1] : 0);
-                            PairJob *jp = j.get();
-                            loading[b] = std::move(j);
-                            lk.unlock();
-                            bns_ctx *cx = c.ctxs_[b % G];
-                            jp->text[0].reserve(cx, (size_t)std::max<u64>(B + SLACK, jp->bytes[0]) + 256);
-                            jp->text[1].reserve(cx, (size_t)std::max<u64>(B2 + 2 * ROOM, jp->bytes[1]) + 256);
-                            lk.lock();
-                            unsigned np = 0;
-                            for (int s = 0; s < 2; ++s)
-                                for (size_t o = 0; o < jp->bytes[s]; o += PIECE) { pieces.push_back(Piece{jp, s, o, std::min(PIECE, jp->bytes[s] - o)}); ++np; }
-                            jp->pieces_left = np;
-                            if (!np) { loaded[b] = std::move(loading[b]); loading.erase(b); }
-                            cv.notify_all();
-                            continue;
-                        }
-                        if (next_load >= n_blocks && loading.empty()) return;
-                        cv.wait(lk);
-                    }
-                }
-                const double t0 = tnow();
-                pread_all(fds[pc.s], pc.j->text[pc.s].p + pc.off, pc.len, pc.j->off[pc.s] + pc.off, "text block");
-                const double t1 = tnow();
-                std::lock_guard<std::mutex> lk(mu);
-                t_read += t1 - t0;
-                if (--pc.j->pieces_left == 0) { const u64 b = pc.j->seq; loaded[b] = std::move(loading[b]); loading.erase(b); }
-                cv.notify_all();
-            }
-        } catch (const std::exception &e) { std::lock_guard<std::mutex> lk(mu); fail_with(e.what()); }
-    };
-    std::vector<std::thread> readers;
-    for (unsigned r = 0; r < R; ++r) readers.emplace_back(reader);
 
     Turns turns;
     // what the turn carries from block to block
@@ -653,12 +505,12 @@ bool process_text_gpu_pair(ClassifierGeneric &c, const char *fq1, const char *fq
                 {
                     std::unique_lock<std::mutex> lk(mu);
                     const double tw = tnow();
-                    cv.wait(lk, [&] { return cancel || loaded.count(b); });
+                    cv.wait(lk, [&] { return rd.cancelled() || rd.loaded(b); });
                     t_idle += tnow() - tw;
-                    if (cancel) { turns.halt(); break; }
-                    j = std::move(loaded[b]); loaded.erase(b);
-                    auto nx = loaded.find(b + G);                    // this device's next block: its upload may start now
-                    if (nx != loaded.end() && !nx->second->prefetched) { ahead = nx->second.get(); ahead->prefetched = true; ++n_ahead; }
+                    if (rd.cancelled()) { turns.halt(); break; }
+                    j = rd.take(b);
+                    PairJob *nx = rd.peek(b + G);                    // this device's next block: its upload may start now
+                    if (nx && !nx->prefetched) { ahead = nx; ahead->prefetched = true; ++n_ahead; }
                 }
                 if (ahead) {
                     const char *tp[2] = {ahead->text[0].p, ahead->text[1].p};
@@ -694,26 +546,25 @@ bool process_text_gpu_pair(ClassifierGeneric &c, const char *fq1, const char *fq
                 std::lock_guard<std::mutex> lk(mu);
                 t_call += tnow() - t0;
                 units += calls.units;
-                spare.push_back(std::move(j));
-                cv.notify_all();
+                rd.give_back(std::move(j));
                 if (!ok) break;
             }
-        } catch (const std::exception &e) { { std::lock_guard<std::mutex> lk(mu); fail_with(e.what()); } turns.halt(); }
+        } catch (const std::exception &e) { { std::lock_guard<std::mutex> lk(mu); rd.fail(e.what()); } turns.halt(); }
     };
     std::vector<std::thread> th;
     for (unsigned g = 1; g < G; ++g) th.emplace_back(worker, g);
     worker(0);
     for (auto &t : th) t.join();
-    { std::lock_guard<std::mutex> lk(mu); cancel = true; cv.notify_all(); }
-    for (auto &t : readers) t.join();
+    { std::lock_guard<std::mutex> lk(mu); rd.cancel(); }
+    rd.join();
     for (bns_ctx *cx : c.ctxs_) (void)bns_text_prefetch(cx, nullptr, nullptr, 0);          // (blocks uploaded ahead of a call that never came)
-    if (!error.empty()) { sink.finish(0, true); die(error); }
+    if (!rd.error().empty()) { sink.finish(0, true); die(rd.error()); }
     sink.finish(n_jobs);
     units_done = units;
     if (timing)
         std::fprintf(stderr, "[timing] pair of files, text on the device: %llu jobs, blocks of %llu + %llu MiB on %u device(s), %u readers: pread %.3f s (summed), calls %.3f (summed), format %.3f, write %.3f; "
                              "waited %.3f s for blocks, %llu uploads started ahead of their call%s%s\n",
-                     (unsigned long long)n_jobs, (unsigned long long)(B >> 20), (unsigned long long)(B2 >> 20), G, R, t_read, t_call, sink.t_format, sink.t_write, t_idle,
+                     (unsigned long long)n_jobs, (unsigned long long)(B >> 20), (unsigned long long)(B2 >> 20), G, R, rd.t_read, t_call, sink.t_format, sink.t_write, t_idle,
                      (unsigned long long)n_ahead, handed_back ? "; the host parser takes the rest" : "", sink.note().c_str());
     return !handed_back;
 }

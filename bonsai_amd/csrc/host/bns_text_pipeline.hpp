@@ -1,8 +1,9 @@
 // bns_text_pipeline.hpp -- what the device-text pipelines share (bns_text_pipeline.cpp: plain files; bns_bgzf_pipeline.cpp: BGZF files;
 // bns_gz_pipeline.cpp: one plain gzip stream): the result buffers of a bns_classify_text call and their ordered writer, the turn chain
 // that cuts an input's blocks in order, the library calls on one block, and the interface of a source of text that lies in device memory.
+// How the inputs' bytes get into page-locked memory is the one loop of bns_slot_reader.hpp (SlotReader), under each pipeline's own monitor.
 #pragma once
-#include "bns_host_internal.hpp"
+#include "bns_slot_reader.hpp"
 
 namespace bns {
 struct TextJob {
