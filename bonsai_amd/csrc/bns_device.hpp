@@ -650,6 +650,8 @@ __device__ __forceinline__ void probe_minbucket2(const MinBucket *__restrict__ b
     const u32 xfA = mph_fold(keyA), xfB = mph_fold(keyB);
     constexpr u32 GO = 1u << MINB_HOME_SHIFT;
     // one half's lookup in the stage and its verdict (probe_minbucket's, TAGS = false); returns "walks on"
+    // The FIRST pass knows val to be zero and takes the slot's value as read, hit or not: a value is read only under its found mask
+    // (the votes, the hit stream).
     auto look = [&](auto first_tag, u32 &bkt, u32 rank, u32 xf, u64 key, u32 &found, u32 &val, u32 home, u32 &hx) -> bool {
         constexpr bool FIRST = decltype(first_tag)::value;
         const bool mine = bkt != MINB_NONE && rank < nb;
@@ -660,7 +662,7 @@ __device__ __forceinline__ void probe_minbucket2(const MinBucket *__restrict__ b
         const bool hit = mine & eq & (!KEY_MAY_BE_ONES || ((hdr.x >> (8u + slot)) & 1u));
         const u32 v = *reinterpret_cast<const u32 *>(B + 80 + 4u * slot);
         found = hit ? 1u : found;
-        val = hit ? v : val;
+        val = FIRST ? v : (hit ? v : val);
         bool cont;
         if (FIRST) cont = mine & !hit & ((hdr.x & (GO | 0xFFu)) >= (GO | MINB_CAP));
         else       cont = mine & !hit & ((hdr.x & 0xFFu) >= MINB_CAP) & ((((home ? home : hdr.x) & GO)) != 0u);
@@ -754,16 +756,21 @@ __device__ __forceinline__ void probe_minbucket2(const MinBucket *__restrict__ b
         __builtin_amdgcn_wave_barrier();
         return true;
     };
-    if (pass(std::true_type{}))
+    // found == 2 is set by a lane that walks down its chain, and a pass with such a lane sets `more`: a call that ends with its first
+    // pass -- 19 of 20 -- has nobody to look up in the overflow table and does not ask (two compares and two ballots).
+    if (pass(std::true_type{}) && more) {
         while (more && pass(std::false_type{})) {}
 #ifdef BNS_COUNT_FETCHES
-    { const u64 gA = ballot64(foundA == 2u), gB = ballot64(foundB == 2u);
-      if ((gA | gB) && lane == 0) { atomicAdd(&g_fetch_count[2], (unsigned long long)(__popcll(gA) + __popcll(gB))); atomicAdd(&g_fetch_count[3], 1ULL); } }
+        { const u64 gA = ballot64(foundA == 2u), gB = ballot64(foundB == 2u);
+          if ((gA | gB) && lane == 0) { atomicAdd(&g_fetch_count[2], (unsigned long long)(__popcll(gA) + __popcll(gB))); atomicAdd(&g_fetch_count[3], 1ULL); } }
 #endif
-    minb_ovf_walk(keyA, foundA, valA, ovf_slots, ovf_mask);
-    minb_ovf_walk(keyB, foundB, valB, ovf_slots, ovf_mask);
-    ra = ProbeResult{valA, (foundA & 1u) != 0u};
-    rb = ProbeResult{valB, (foundB & 1u) != 0u};
+        minb_ovf_walk(keyA, foundA, valA, ovf_slots, ovf_mask);
+        minb_ovf_walk(keyB, foundB, valB, ovf_slots, ovf_mask);
+    }
+    // found is 0, 1 or 2, never 3 -- a lane that hit has left (bkt == MINB_NONE) and is never sent on -- so ONE compare says "hit", and
+    // the caller's ballot and its lane predicate are that compare
+    ra = ProbeResult{valA, foundA == 1u};
+    rb = ProbeResult{valB, foundB == 1u};
 }
 
 // ---- taxonomy ----------------------------------------------------------------------------------------
