@@ -161,6 +161,7 @@ def load():
     L._bns_signatures = sig
     # test aids the library exports next to the ABI of include/bonsai_amd.h (not declared there)
     for name, (res, args) in {"bns_debug_set": (C.c_int, [vp, C.c_int]),
+                              "bns_debug_set_claim_waves": (C.c_int, [vp, C.c_uint]),
                               "bns_debug_last_classify_form": (C.c_int, [vp, u32p, C.c_int])}.items():
         fn = getattr(L, name)
         fn.restype = res

@@ -161,6 +161,11 @@ class Context:
         """test / profiling switches (BNS_DBG_* in bns_api.hip); not part of the public header"""
         self._chk(self.L.bns_debug_set(self.h, bits), "bns_debug_set")
 
+    def debug_claim_waves(self, waves):
+        """bns_debug_set_claim_waves (a test aid, not part of the public header): classify_kernel's claims are sized for `waves`
+        resident wavefronts (a multiple of 4) and its grid capped at waves / 4 workgroups; 0 = the device's own"""
+        self._chk(self.L.bns_debug_set_claim_waves(self.h, int(waves)), "bns_debug_set_claim_waves")
+
     def last_classify_form(self):
         """bns_debug_last_classify_form (a test aid, not part of the public header): what the last classify call of this context
         launched.  "kernel": (SPACED, LAYOUT, KT, NM, SPAN, OVC, WIDE, PACKED) of the classify_kernel instantiation (None before the

@@ -38,7 +38,7 @@ struct DevBuf {
 // ctx->small: the few device words the entry points share with their kernels.  Every entry point zeroes ITS words on its own
 // stream before use; nothing here persists across calls.
 struct SmallLayout {
-    u32 work_counter; u32 pad0[31];            // [0,128)   classify_kernel's chunk counter, on a line of its own (80 M atomics/s)
+    u32 work_counter; u32 pad0[31];            // [0,128)   classify_kernel's claim counter, on a line of its own (80 M atomics/s)
     u32 ovf_count, max_len; u32 pad1[30];      // [128,256) classify: units handed to the overflow kernel; longest read of the batch
     unsigned long long load_cnt[8];            // [256,320) table load / device build counters
     unsigned long long runs_cursor;            // [320,328) hit_runs_kernel's output cursor
@@ -128,6 +128,7 @@ struct bns_ctx {
     u32 table_span = 0;             // the window candidate (MIN_CANDS span: 15 / 11 / 8) the loaded table was built with; 0: none (spaced seed)
     std::string warn;               // what the last table load has to say about the table it built (bns_table_warning)
     int dbg = 0;
+    unsigned claim_waves = 0;   // bns_debug_set_claim_waves
     ClassifyForm last_form;     // bns_debug_last_classify_form
     u32 table_k = 0;            // k the minimizer-clustered layout was built for
     // taxonomy
@@ -301,9 +302,18 @@ int ready(bns_ctx *ctx, bool need_table, bool need_tax)
 namespace {
 // Every classify_kernel / classify_overflow_kernel launch goes through these two: the instantiation launched and the one
 // recorded in the form are the same template arguments.
+// max_blocks: the workgroups that are resident at once (or fewer: bns_debug_set_claim_waves).  Units per claim: the full chunk when
+// that leaves every one of their wavefronts at least one, else an even share (>= 4: a claim is an offsets load); the grid and
+// the start of the dynamic claims follow from it (bns_claims.hpp).
 template <bool SP, int LY, int KT, int NM, int SPAN, bool OVC, bool WIDE, bool PACKED>
-void launch_classify(ClassifyForm &f, const ClassifyParams &p, unsigned grid, hipStream_t st)
+void launch_classify(ClassifyForm &f, const ClassifyParams &p0, unsigned max_blocks, hipStream_t st)
 {
+    ClassifyParams p = p0;
+    u32 grid;
+    const u32 full = classify_chunk((u32)p.nmates);
+    claim_geometry(p.n_units, max_blocks, full, p.chunk, grid);
+    p.claim_base = claim_dynamic_start(p.n_units, grid * 4u, p.chunk, full);
+    if (p.chunk < full) p.work_counter = nullptr;          // dealt out by the static claims alone: the kernel asks no counter
     f = ClassifyForm{};
     f.w[ClassifyForm::VALID] = 1; f.w[ClassifyForm::SPACED] = SP; f.w[ClassifyForm::LAYOUT] = LY; f.w[ClassifyForm::KT] = KT;
     f.w[ClassifyForm::NM] = NM; f.w[ClassifyForm::SPAN] = SPAN; f.w[ClassifyForm::OVC] = OVC; f.w[ClassifyForm::WIDE] = WIDE;
@@ -380,6 +390,10 @@ int bns_device_count(void)
  * 4: no minimizer window; BNS_ABLATION builds only) make results WRONG; the others select code paths that a small test could
  * not reach otherwise (streamed load, sliced upload, one-rank RCCL broadcast). */
 int bns_debug_set(bns_ctx *ctx, int bits) { if (!ctx) return BNS_ERR_ARG; ctx->dbg = bits; return BNS_OK; }
+/* test aid like bns_debug_set, not part of the public header: classify_kernel's claims are sized for `waves` resident
+ * wavefronts and its grid capped at waves / 4 workgroups (0: the device's own).  With 4 or 8, a batch of a few hundred short reads runs
+ * staggered static claims and full dynamic ones, on wavefronts that go on claiming. */
+int bns_debug_set_claim_waves(bns_ctx *ctx, unsigned waves) { if (!ctx || (waves & 3u)) return BNS_ERR_ARG; ctx->claim_waves = waves; return BNS_OK; }
 /* test aid like bns_debug_set, not part of the public header: which kernels the last classify dispatch of this context launched.
  * Copies min(n, 18) words to out and returns how many; the words, in order: valid (0 until something was classified) | SPACED,
  * LAYOUT, KT, NM, SPAN, OVC, WIDE, PACKED of the classify_kernel instantiation | classify_overflow_kernel: launched (0 / 1), its
@@ -392,12 +406,12 @@ int bns_debug_last_classify_form(const bns_ctx *ctx, uint32_t *out, int n)
     return c;
 }
 #ifdef BNS_WAVE_TIMES
-// measurement builds only: (start, end) wall-clock stamps of the 8192 wavefronts of the last classify_kernel launch
-extern "C" int bns_debug_wave_times(bns_ctx *ctx, unsigned long long *out16384)
+// measurement builds only: the WAVE_STAMPS (5) wall-clock stamps of each of the 8192 wavefronts of the last classify_kernel launch
+extern "C" int bns_debug_wave_times(bns_ctx *ctx, unsigned long long *out40960)
 {
-    if (!ctx || !out16384) return BNS_ERR_ARG;
+    if (!ctx || !out40960) return BNS_ERR_ARG;
     if (hipDeviceSynchronize() != hipSuccess) return BNS_ERR_HIP;
-    if (hipMemcpyFromSymbol(out16384, HIP_SYMBOL(bns::g_wave_times), 16384 * sizeof(unsigned long long)) != hipSuccess) return BNS_ERR_HIP;
+    if (hipMemcpyFromSymbol(out40960, HIP_SYMBOL(bns::g_wave_times), sizeof(bns::g_wave_times)) != hipSuccess) return BNS_ERR_HIP;
     return BNS_OK;
 }
 #endif
@@ -1642,7 +1656,7 @@ static int classify_device_impl(bns_ctx *ctx, const char *d_bases, const uint64_
     const int nm = paired ? 2 : 1;
     const u64 n_units = n_reads / (u64)nm;
     if (n_units == 0) return BNS_OK;
-    if (n_units >= (1ULL << 32) - (1ULL << 22)) return fail(ctx, BNS_ERR_ARG, "more than 2^32 - 2^22 units in one batch: split it");   // (headroom: every wavefront claims one chunk past the end)
+    if (n_units >= (1ULL << 32) - (1ULL << 22)) return fail(ctx, BNS_ERR_ARG, "more than 2^32 - 2^22 units in one batch: split it");   // (headroom: every wavefront draws one claim past the end)
 
     SmallLayout *sm = (SmallLayout *)ctx->small.p;
     u32 *d_ovf = &sm->ovf_count;
@@ -1675,12 +1689,9 @@ static int classify_device_impl(bns_ctx *ctx, const char *d_bases, const uint64_
     // reference behaviour for a spaced seed through the string for_each: nothing is emitted
     p.emit_none = (ctx->spaced && !ctx->spaced_intended) ? 1 : 0;
 
-    // units per claim: the full chunk when that leaves every resident wave (8 blocks of 4 per CU) at least one, else an even share
-    // (>= 4: a claim is an atomic plus an offsets load)
-    const u64 resident_waves = (u64)ctx->n_cu * 8 * 4;
-    const u32 chunk = (u32)std::min<u64>(classify_chunk((u32)nm), std::max<u64>(4, (n_units + resident_waves - 1) / resident_waves));
-    p.chunk = chunk;
-    unsigned grid = grid_for(ctx, (n_units + chunk - 1) / chunk, 4);
+    // persistent grid: at most the workgroups that are resident at once, 8 of 4 wavefronts per CU (launch_classify sizes the claims by it)
+    unsigned grid = (unsigned)ctx->n_cu * 8u;
+    if (ctx->claim_waves) grid = std::max(1u, std::min(grid, ctx->claim_waves / 4u));
     const int evi = ctx->ev_head;
     if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev0[evi], st));
     // Contiguous seeds on the clustered table with a common k: k, the mates per unit and the minimizer window are compile-time
@@ -1700,7 +1711,7 @@ static int classify_device_impl(bns_ctx *ctx, const char *d_bases, const uint64_
         dispatch_sp_layout(ctx->spaced, ctx->layout, [&](auto sp, auto ly) {
             constexpr bool SP = decltype(sp)::value;
             constexpr int LY = decltype(ly)::value;
-            // persistent grid = the blocks that are resident at once (a wide probe stage takes more LDS per block than 8 per CU allow)
+            // (a wide probe stage takes more LDS per block than 8 per CU allow)
             auto go = [&](auto pk) {
                 constexpr bool PK = decltype(pk)::value;
                 int per_cu = 8;

@@ -1350,7 +1350,9 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
 }
 
 #ifdef BNS_WAVE_TIMES
-__device__ unsigned long long g_wave_times[2 * 8192];
+// per wavefront: kernel entry, first claim in hand, first unit finished, last unit finished, exit (tools/wave_times.py)
+constexpr int WAVE_STAMPS = 5;
+__device__ unsigned long long g_wave_times[WAVE_STAMPS * 8192];
 #endif
 template <bool SPACED, int LAYOUT, int KT, int NM, int SPAN = 8, bool OVC = false, bool WIDE = false, bool PACKED = false>
 __global__ __launch_bounds__(256, (ClassifyTraits<SPACED, LAYOUT, KT, NM, SPAN, OVC, WIDE, PACKED>::WAVES)) void classify_kernel(ClassifyParams p)
@@ -1374,33 +1376,45 @@ __global__ __launch_bounds__(256, (ClassifyTraits<SPACED, LAYOUT, KT, NM, SPAN, 
     }
     const int lane = lane_id();
 #ifdef BNS_WAVE_TIMES                        // measurement builds only: when does each wavefront start and finish?
-    const unsigned long long t_start = wall_clock64();
-    struct TimeStamp { unsigned long long t0; u32 slot; __device__ ~TimeStamp() { if ((threadIdx.x & 63u) == 0) { g_wave_times[2 * slot] = t0; g_wave_times[2 * slot + 1] = wall_clock64(); } } } stamp{t_start, blockIdx.x * 4u + (u32)wv};
+    struct TimeStamp {
+        unsigned long long t[WAVE_STAMPS]; u32 slot;
+        __device__ ~TimeStamp() { if ((threadIdx.x & 63u) == 0 && slot < 8192u) { t[4] = wall_clock64(); for (int i = 0; i < WAVE_STAMPS; ++i) g_wave_times[WAVE_STAMPS * slot + i] = t[i]; } }
+    } stamp{{(unsigned long long)wall_clock64(), 0, 0, 0, 0}, blockIdx.x * 4u + (u32)wv};
 #endif
     // unit indices are 32-bit here (bns_classify_batch_device rejects batches of 2^32 units or more)
     const u32 n_units = (u32)p.n_units;
     const u32 nm = NM ? (u32)NM : (u32)p.nmates;
-    // Work distribution: wavefronts CLAIM chunks of consecutive units (classify_chunk(): 63 reads / 31 pairs) from a counter instead of owning a fixed
+    // Work distribution: wavefronts CLAIM chunks of consecutive units (classify_chunk(): 31 reads or pairs) instead of owning a fixed
     // stride of them.  With equal shares the wavefronts of one launch finished anywhere between 66 % and 100 % of its duration
     // (older waves win the issue arbitration and run ahead; measured with a -DBNS_WAVE_TIMES build, tools/wave_times.py), i.e. the
     // last third of the kernel ran on a thinning population of waves -- and this kernel needs all eight per SIMD to cover its
     // latencies.  Claiming keeps every wave busy until the batch is empty.
-    // Software pipeline, per wave: the NEXT chunk's claim (one atomic) is in flight from the start of a chunk, its offsets (one
-    // 64-lane load: 17 or 33 of them) from the chunk's third unit, the first 256 bases of the next unit while a unit is
-    // classified.  Offsets travel through VECTOR loads so that LDS waits (lgkmcnt) never stall on them.
-    u32 *const ctr = p.work_counter;
-    const u32 CH = p.chunk;                                  // classify_chunk(nm), less for a batch too small to give every wave one that size
-    auto claim = [&]() -> u32 { return lane == 0 ? atomicAdd(ctr, CH) : 0u; };                             // (lane 0 holds the result)
+    // Which units a claim stands for is bns_claims.hpp's business: a wavefront's FIRST chunk is a closed form of its index (no
+    // atomic while all of them start at once; staggered sizes, so that their later claims do not come in step either), every
+    // further one an index drawn from the work counter: the full chunk that far behind the static part.
+    // Software pipeline, per wave: the NEXT chunk's claim (one atomic) is issued with the prefetch loads of the unit three from
+    // the chunk's end and looked at one unit later, where its offsets (one 64-lane load: up to 32 or 63 of them) are asked for
+    // in turn: each rides under a bucket-fetch wait that the unit pays anyway, and the offsets are there for the last unit's
+    // prefetch.  The first 256 bases of the next unit travel while a unit is classified.  Offsets travel through VECTOR loads so
+    // that LDS waits (lgkmcnt) never stall on them.
+    const u32 FULL = classify_chunk(nm);
+    // claim index of the next chunk (lane 0 holds the result).  No counter: the batch is dealt out by the static claims alone, and claim 0
+    // lies past its end (claim_base = n_units).
+    auto claim = [&]() -> u32 { u32 *const c = cold_params()->work_counter; return c && lane == 0 ? atomicAdd(c, 1u) : 0u; };
     // (the offsets pointer is taken from the kernarg segment at the point of use and advanced in SGPRs: kept as a per-lane address
     // across the kernel it cost two VGPRs -- or, in the instantiations at the 64-register limit, 8 bytes of scratch)
-    auto load_offs = [&](u32 base) -> u64 {
-        const u32 left = n_units - base, cnt = left < CH ? left : CH;
+    auto load_offs = [&](u32 base, u32 cnt) -> u64 {
         const u64 *op = const_cast<const u64 *>(cold_params()->offsets) + (u64)base * nm;
         return (u32)lane <= cnt * nm ? op[lane] : 0ULL;
     };
-    u32 base = (u32)__builtin_amdgcn_readfirstlane((int)claim());
+    u32 base, cnt;
+    claim_static(blockIdx.x * 4u + (u32)wv, p.chunk, FULL, base, cnt);
+#ifdef BNS_WAVE_TIMES
+    stamp.t[1] = wall_clock64();
+#endif
     if (base >= n_units) return;
-    u64 offs = load_offs(base);
+    cnt = claim_cnt(base, cnt, n_units);
+    u64 offs = load_offs(base, cnt);
     Prefetch pre;
     {
         const u64 o0 = readlane64(offs, 0);
@@ -1411,15 +1425,15 @@ __global__ __launch_bounds__(256, (ClassifyTraits<SPACED, LAYOUT, KT, NM, SPAN, 
     u32 pend_u = 0;
     bool pend_valid = false;
     for (;;) {
-        const u32 left = n_units - base, cnt = left < CH ? left : CH;
-        u32 next_v = claim();                                    // next chunk, claimed now, looked at two units from now
+        u32 next_v = 0;
         u32 nbase = 0xFFFFFFFFu;
         u64 noffs = 0;
-        const u32 jload = cnt > 2u ? 2u : cnt - 1u;
+        const u32 jload = cnt > 2u ? cnt - 2u : 0u;              // the unit in front of which the next claim is looked at: the last but one
         for (u32 j = 0; j < cnt; ++j) {
             if (j == jload) {
-                nbase = (u32)__builtin_amdgcn_readfirstlane((int)next_v);
-                if (nbase < n_units) noffs = load_offs(nbase);
+                if (j == 0u) next_v = claim();                       // (a chunk of one or two units: asked for and looked at on the spot)
+                nbase = claim_dynamic_base(cold_params()->claim_base, (u32)__builtin_amdgcn_readfirstlane((int)next_v), FULL);
+                if (nbase < n_units) noffs = load_offs(nbase, claim_cnt(nbase, FULL, n_units));
             }
             Prefetch npre;
             // Issued by classify_unit behind the unit's first pack, so that the pack's wait for `pre` (here since the previous unit's
@@ -1441,6 +1455,7 @@ __global__ __launch_bounds__(256, (ClassifyTraits<SPACED, LAYOUT, KT, NM, SPAN, 
                     nr = (u64)nbase * nm;
                 }
                 prefetch_issue<PACKED>(p, nr, n0, nL, npre);
+                if (j + 1u == jload) next_v = claim();               // the next chunk: looked at in front of the unit after this one
                 // The previous unit's record is stored next to the prefetch loads: gfx9 has one counter for loads and stores, so the
                 // first wait after a store waits for its acknowledgement too.
                 if (pend_valid && lane == 0) cold_params()->records[pend_u] = pend;
@@ -1449,9 +1464,14 @@ __global__ __launch_bounds__(256, (ClassifyTraits<SPACED, LAYOUT, KT, NM, SPAN, 
                                           s_mh[wv] + MINB_LIST_U32 + LDS_CAP, LDS_CAP, true, s_ring[wv], s_mh[wv], s_pk[wv], pend, pend_valid, issue_next);
             pend_u = base + j;
             pre = npre;
+#ifdef BNS_WAVE_TIMES
+            stamp.t[3] = wall_clock64();
+            if (!stamp.t[2]) stamp.t[2] = stamp.t[3];
+#endif
         }
         if (nbase >= n_units) break;
         base = nbase; offs = noffs;
+        cnt = claim_cnt(base, FULL, n_units);     // (recomputed: nothing but the base is carried over)
     }
     if (pend_valid && lane == 0) cold_params()->records[pend_u] = pend;
 }

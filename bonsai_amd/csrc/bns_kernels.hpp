@@ -1,12 +1,14 @@
 // bns_kernels.hpp -- kernel parameter block shared by the kernels and the host-side launcher.
 #pragma once
 #include "bns_device.hpp"
+#include "bns_claims.hpp"
 
 namespace bns {
 
-// Units a wavefront claims at a time.  One 64-lane load brings a chunk's offsets (chunk * mates + 1 of them: at most 63 reads or
-// 31 pairs), and all claims go to ONE counter whose atomics saturate at about 80 M/s: at 1.2 G reads/s chunks of 8 or 16 units
-// are bound by that (15.0 / 8.3 ms per 10 M reads), chunks of 31 are not (7.0 ms); 47 and 63 balance a little worse (7.05 / 7.12).
+// Units of a full claim.  One 64-lane load brings a chunk's offsets (chunk * mates + 1 of them: at most 63 reads or 31 pairs), and
+// all claims go to ONE counter whose atomics saturate at about 80 M/s (measured at 1.2 G reads/s: chunks of 8 or 16 units were
+// bound by that -- 15.0 / 8.3 ms per 10 M reads -- chunks of 31 were not, 7.0 ms; 47 and 63 balanced a little worse, 7.05 / 7.12).
+// How the claims are laid over a batch -- a first one per wavefront without the counter -- is in bns_claims.hpp.
 #ifndef BNS_CLASSIFY_CHUNK1
 #define BNS_CLASSIFY_CHUNK1 31
 #endif
@@ -68,8 +70,9 @@ struct ClassifyParams {
     u32 *taxon, *missing, *ambig, *n_hits, *hits;
     uint4 *records;     // classify_kernel writes one {taxon, missing, ambig, n_hits} record per unit; unpack_kernel splits it
     u32 *ovf_count;
-    u32 *work_counter;  // classify_kernel: next unclaimed unit (wavefronts claim `chunk` units at a time)
-    u32 chunk;          // units per claim: classify_chunk(nmates), fewer when the batch is small (a CLI chunk of 112 k reads is 1775 claims of 63: 444 blocks on 256 CUs)
+    u32 *work_counter;  // classify_kernel: the next dynamic claim index (bns_claims.hpp), from 0
+    u32 chunk;          // units per claim: classify_chunk(nmates); fewer when the batch is small -- every wavefront then takes one such claim by its index and none from the counter
+    u32 claim_base;     // dynamic claim d stands for the units from claim_base + d * chunk (written by launch_classify: the units its grid's static claims take)
     u64 *ovf_list;
 };
 

@@ -1,37 +1,54 @@
 #!/usr/bin/env python
-"""When do the 8192 wavefronts of one classify_kernel launch finish?  (measurement build -DBNS_WAVE_TIMES; run with
-BONSAI_AMD_LIB=bonsai_amd/lib/libT.so)  Prints the spread of the finish times as fractions of the kernel's duration."""
-import ctypes, json, os, subprocess, sys
+"""Where does each of the 8192 wavefronts of one classify_kernel launch spend its time?  (measurement build -DBNS_WAVE_TIMES; run
+with BONSAI_AMD_LIB=<that build>)  Five stamps per wavefront: kernel entry, first claim in hand, first unit finished, last unit
+finished, exit.  Prints the percentiles of each as fractions of the kernel's duration, and the share of wave-time (wavefronts x
+duration) that lies before a wavefront's first unit has finished and after its last one has."""
+import ctypes, json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 import bench, bonsai_amd
 
+STAMPS = ("entry", "first_claim", "first_unit_done", "last_unit_done", "exit")
+PCTS = (0, 1, 5, 25, 50, 75, 95, 99, 100)
+
 sys.argv = [sys.argv[0], "--no-cpu", "--no-probe", "--steps", "3", "--warmup", "1"] + sys.argv[1:]
 # run the bench in-process, then read the stamps of its last launch
-import builtins
-ctxs = []
 orig = bonsai_amd.Context
 class Keep(orig):
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k); ctxs.append(self)
     def close(self):
-        t = np.zeros(16384, dtype=np.uint64)
+        t = np.zeros(len(STAMPS) * 8192, dtype=np.uint64)
         self.L.bns_debug_wave_times.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self.L.bns_debug_wave_times(self.h, t.ctypes.data)
-        t0, t1 = t[0::2].astype(np.int64), t[1::2].astype(np.int64)
-        ok = t1 > 0
-        base, end = t0[ok].min(), t1[ok].max()
-        fin = (t1[ok] - base) / float(end - base)
-        st = (t0[ok] - base) / float(end - base)
-        print(json.dumps({"waves": int(ok.sum()), "start_frac_max": float(st.max()), "finish_frac_percentiles": {str(p): float(np.percentile(fin, p)) for p in (0, 1, 5, 25, 50, 75, 95, 99, 100)},
-                          "mean_alive_frac": float(((t1[ok] - t0[ok]) / float(end - base)).mean())}))
-        # by XCD (block index mod 8 is the usual round-robin) and by CU-ish groups
-        blk = np.arange(8192)[ok] // 4
+        t = t.reshape(8192, len(STAMPS)).astype(np.int64)
+        t = t[t[:, 4] > 0]
+        base, end = t[:, 0].min(), t[:, 4].max()
+        dur = float(end - base)
+        f = (t - base) / dur
+        out = {"waves": int(t.shape[0]), "duration_ticks": int(end - base)}
+        for i, name in enumerate(STAMPS):
+            out[name + "_frac_percentiles"] = {str(p): round(float(np.percentile(f[:, i], p)), 5) for p in PCTS}
+        n = float(t.shape[0])
+        out["wave_time_share"] = {
+            "before_entry": round(float(f[:, 0].sum() / n), 5),
+            "entry_to_first_claim": round(float((f[:, 1] - f[:, 0]).sum() / n), 5),
+            "first_claim_to_first_unit_done": round(float((f[:, 2] - f[:, 1]).sum() / n), 5),
+            "before_first_unit_done": round(float(f[:, 2].sum() / n), 5),
+            "after_last_unit_done": round(float((1.0 - f[:, 3]).sum() / n), 5),
+            "after_exit": round(float((1.0 - f[:, 4]).sum() / n), 5),
+            "resident": round(float((f[:, 4] - f[:, 0]).sum() / n), 5),
+        }
+        # what a unit takes in the steady state, for scale: (last - first unit done) over the units in between is not known per
+        # wavefront, but the first unit's own time against the batch mean is
+        out["first_unit_ticks_median"] = float(np.median(t[:, 2] - t[:, 1]))
+        print(json.dumps(out))
+        # by XCD (block index mod 8 is the usual round-robin)
+        blk = np.arange(8192)[: t.shape[0]] // 4
         for x in range(8):
             sel = (blk % 8) == x
-            print("xcd-ish %d: median finish %.3f  p95 %.3f" % (x, float(np.median(fin[sel])), float(np.percentile(fin[sel], 95))))
+            if sel.any():
+                print("xcd-ish %d: median exit %.3f  p95 %.3f" % (x, float(np.median(f[sel, 4])), float(np.percentile(f[sel, 4], 95))))
         super().close()
 bonsai_amd.Context = Keep
 bench.main()
