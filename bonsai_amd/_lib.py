@@ -122,6 +122,13 @@ def load():
         "bns_probe_device": (C.c_int, [vp, vp, C.c_uint64, vp, vp, vp]),
         "bns_resolve_batch": (C.c_int, [vp, u32p, u16p, u64p, C.c_uint64, u32p]),
         "bns_build_table_device": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, vp, vp, u64p, vp]),
+        "bns_build_begin": (C.c_int, [vp, C.c_uint64]),
+        "bns_build_seed": (C.c_int, [vp, C.c_uint64, u32p, u64p, u32p]),
+        "bns_build_add": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp]),
+        "bns_build_finish": (C.c_int, [vp, u64p]),
+        "bns_build_export": (C.c_int, [vp, u32p, u64p, u32p]),
+        "bns_build_stats": (C.c_int, [vp, u64p]),
+        "bns_build_end": (C.c_int, [vp]),
         "bns_set_timing": (C.c_int, [vp, C.c_int]),
         "bns_last_kernel_ms": (C.c_float, [vp]),
         "bns_timing_summary": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),

@@ -523,6 +523,47 @@ class Context:
                                                 d_flags, d_keys, d_vals, _p(hdr, u64p), stream), "bns_build_table_device")
         return hdr
 
+    # ---- build session: a table that persists in the context, grows, and can start from an existing khash table
+    def build_begin(self, n_buckets=0):
+        """opens a session with max(4, n_buckets rounded up to a power of two) empty buckets"""
+        self._chk(self.L.bns_build_begin(self.h, int(n_buckets)), "bns_build_begin")
+
+    def build_seed(self, n_buckets, flags, keys, vals):
+        """the present slots of a khash table (host arrays as load_table takes them); once, before the first build_add"""
+        flags = np.ascontiguousarray(flags, dtype=np.uint32)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        vals = np.ascontiguousarray(vals, dtype=np.uint32)
+        if flags.size < max(1, (int(n_buckets) + 15) >> 4) or keys.size < n_buckets or vals.size < n_buckets:
+            raise ValueError("flags / keys / vals are shorter than n_buckets asks")
+        self._chk(self.L.bns_build_seed(self.h, int(n_buckets), _p(flags, u32p), _p(keys, u64p), _p(vals, u32p)), "bns_build_seed")
+
+    def build_add(self, d_bases, d_offsets, n_seqs, total_bases, d_taxid, stream=None):
+        """one batch of whole sequences (device arrays, as build_table_device takes them); the table grows as it must"""
+        self._chk(self.L.bns_build_add(self.h, d_bases, d_offsets, n_seqs, total_bases, d_taxid, stream), "bns_build_add")
+
+    def build_stats(self, timing=False):
+        """{batches, grows, seeded, keys} of the open session (+ add_s / grow_s with timing=True: wall seconds inside build_add, and
+        the part of them spent growing)"""
+        out = np.zeros(6, dtype=np.uint64)
+        self._chk(self.L.bns_build_stats(self.h, _p(out, u64p)), "bns_build_stats")
+        d = dict(zip(("batches", "grows", "seeded", "keys"), (int(x) for x in out[:4])))
+        if timing:
+            d["add_s"], d["grow_s"] = float(out[4]) * 1e-6, float(out[5]) * 1e-6
+        return d
+
+    def build_finish(self):
+        """compacts, writes the flags and returns hdr, flags, keys, vals (numpy; hdr = n_buckets, n_occupied, size, upper_bound).
+        The session stays open (build_stats still answers) until build_end."""
+        hdr = np.zeros(4, dtype=np.uint64)
+        self._chk(self.L.bns_build_finish(self.h, _p(hdr, u64p)), "bns_build_finish")
+        nb = int(hdr[0])
+        flags = np.zeros(max(1, nb >> 4), dtype=np.uint32); keys = np.zeros(nb, dtype=np.uint64); vals = np.zeros(nb, dtype=np.uint32)
+        self._chk(self.L.bns_build_export(self.h, _p(flags, u32p), _p(keys, u64p), _p(vals, u32p)), "bns_build_export")
+        return hdr, flags, keys, vals
+
+    def build_end(self):
+        self._chk(self.L.bns_build_end(self.h), "bns_build_end")
+
     def set_timing(self, on=True):
         self._chk(self.L.bns_set_timing(self.h, int(on)), "bns_set_timing")
 

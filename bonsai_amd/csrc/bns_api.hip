@@ -78,11 +78,13 @@ struct ClassifyForm {
 }  // namespace
 
 struct bns_text_work;                                     // bns_ingest.hip: workspace of bns_classify_text
+namespace bns { struct BuildSession; }                    // bns_build.hpp: the table a build session grows
 void text_work_free(struct bns_ctx *ctx);
 
 struct bns_ctx {
     int device = 0;
     bns_text_work *text_work = nullptr;
+    bns::BuildSession *build = nullptr;                  // bns_build_begin .. bns_build_end; while it is open the encoder, the window and the taxonomy stay
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;                   // host-buffer entry points: uploads of the next slice while one is classified
     hipStream_t back_stream = nullptr;                   // ... and the copy-back of a classified slice's results, behind neither of the two
@@ -299,6 +301,8 @@ int ready(bns_ctx *ctx, bool need_table, bool need_tax)
 
 }  // namespace
 
+#include "bns_build.hpp"
+
 namespace {
 // Every classify_kernel / classify_overflow_kernel launch goes through these two: the instantiation launched and the one
 // recorded in the form are the same template arguments.
@@ -371,7 +375,7 @@ bool launch_fixed_k(ClassifyForm &f, const ClassifyParams &p, unsigned grid, hip
 
 extern "C" {
 
-int bns_version(void) { return 108; }
+int bns_version(void) { return 109; }
 
 int bns_device_pci_bus_id(int device, char *out, int cap)
 {
@@ -503,6 +507,7 @@ void bns_destroy(bns_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     free_table(ctx);
+    build_free(ctx);
     text_work_free(ctx);
     if (ctx->nodes) (void)hipFree(ctx->nodes);
     DevBuf *bufs[] = {&ctx->words, &ctx->nmask, &ctx->ovf_list, &ctx->scratch, &ctx->small, &ctx->records, &ctx->st_bases, &ctx->st_offsets,
@@ -529,6 +534,7 @@ void bns_destroy(bns_ctx *ctx)
 int bns_set_encoder(bns_ctx *ctx, uint32_t k, const uint16_t *gaps, int canonicalize, int spaced_intended)
 {
     if (!ctx) return BNS_ERR_ARG;
+    if (ctx->build) return fail(ctx, BNS_ERR_STATE, "bns_set_encoder while a build session is open (bns_build_end)");
     if (k < 1 || k > 32) return fail(ctx, BNS_ERR_ARG, "k must be in [1,32] (u64 k-mers)");
     u32 c = 1;
     ctx->pos[0] = 0;
@@ -602,6 +608,7 @@ int bns_set_window(bns_ctx *ctx, uint32_t w, int score)
 {
     if (!ctx) return BNS_ERR_ARG;
     if (!ctx->enc_set) return fail(ctx, BNS_ERR_STATE, "configure the encoder first (bns_set_encoder)");
+    if (ctx->build) return fail(ctx, BNS_ERR_STATE, "bns_set_window while a build session is open (bns_build_end)");
     if (score != BNS_SCORE_LEX && score != BNS_SCORE_ENTROPY_PATH && score != BNS_SCORE_ENTROPY_STRING) return fail(ctx, BNS_ERR_ARG, "unknown score");
     if (score == BNS_SCORE_ENTROPY_STRING && ctx->spaced)
         return fail(ctx, BNS_ERR_ARG, "BNS_SCORE_ENTROPY_STRING is the contiguous-seed string overload (encoder.h:425,434); a spaced seed scores through the path rule");
@@ -1541,6 +1548,7 @@ int bns_sketch_read(bns_ctx *ctx, uint32_t *bins, uint8_t *registers, uint32_t c
 int bns_load_taxonomy(bns_ctx *ctx, const uint32_t *parent, uint32_t n)
 {
     if (!ctx || !parent || n < 2) return BNS_ERR_ARG;
+    if (ctx->build) return fail(ctx, BNS_ERR_STATE, "bns_load_taxonomy while a build session is open (bns_build_end)");
     if (n > (1u << 28)) return fail(ctx, BNS_ERR_TAX_RANGE, "taxid >= 2^28");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::vector<TaxNode> nodes(n);
@@ -2494,6 +2502,33 @@ int bns_build_table_device(bns_ctx *ctx, const char *d_bases, const uint64_t *d_
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(st));
     if (header4) { header4[0] = n_buckets; header4[1] = h_cnt; header4[2] = h_cnt; header4[3] = upper; }
+    return BNS_OK;
+}
+
+int bns_build_begin(bns_ctx *ctx, uint64_t n_buckets_hint) { return build_begin(ctx, n_buckets_hint); }
+int bns_build_seed(bns_ctx *ctx, uint64_t n_buckets, const uint32_t *flags, const uint64_t *keys, const uint32_t *vals)
+{
+    return build_seed(ctx, n_buckets, flags, keys, vals);
+}
+int bns_build_add(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bases,
+                  const uint32_t *d_taxid, void *stream)
+{
+    return build_add(ctx, d_bases, d_offsets, n_seqs, total_bases, d_taxid, stream);
+}
+int bns_build_finish(bns_ctx *ctx, uint64_t *header4) { return build_finish(ctx, header4); }
+int bns_build_export(bns_ctx *ctx, uint32_t *flags, uint64_t *keys, uint32_t *vals) { return build_export(ctx, flags, keys, vals); }
+int bns_build_stats(const bns_ctx *ctx, uint64_t *out6)
+{
+    if (!ctx || !out6) return BNS_ERR_ARG;
+    if (!ctx->build) return BNS_ERR_STATE;
+    out6[0] = ctx->build->n_batches; out6[1] = ctx->build->n_grows; out6[2] = ctx->build->n_seeded; out6[3] = ctx->build->n_keys;
+    out6[4] = (u64)(ctx->build->s_add * 1e6); out6[5] = (u64)(ctx->build->s_grow * 1e6);
+    return BNS_OK;
+}
+int bns_build_end(bns_ctx *ctx)
+{
+    if (!ctx) return BNS_ERR_ARG;
+    build_free(ctx);
     return BNS_OK;
 }
 

@@ -817,27 +817,93 @@ struct DevMem {
     ~DevMem() { if (p) bns_dev_free(ctx, p); }
     DevMem(const DevMem &) = delete; DevMem &operator=(const DevMem &) = delete;
 };
+// device memory that is re-used from one batch to the next and only re-allocated for a larger one
+struct GrowMem {
+    bns_ctx *ctx; void *p = nullptr; size_t cap = 0;
+    explicit GrowMem(bns_ctx *c) : ctx(c) {}
+    ~GrowMem() { release(); }
+    void release() { if (p) bns_dev_free(ctx, p); p = nullptr; cap = 0; }
+    void ensure(size_t n)
+    {
+        if (n <= cap) return;
+        release();
+        chk(ctx, bns_dev_alloc(ctx, n, &p), "bns_dev_alloc");
+        cap = n;
+    }
+    GrowMem(const GrowMem &) = delete; GrowMem &operator=(const GrowMem &) = delete;
+};
+
+// whole sequences of at most batch_bases bases (one sequence longer than that is a batch of its own)
+struct BuildBatch {
+    std::string bases;
+    std::vector<u64> offsets{0};
+    std::vector<u32> taxids;
+    void clear() { bases.clear(); offsets.assign(1, 0); taxids.clear(); }
+};
+
+// one batch waits while the device works on the one before it and the reader fills the next
+class BatchQueue {
+public:
+    void push(BuildBatch &&b)
+    {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return !full_ || abandoned_; });
+        if (abandoned_) return;
+        slot_ = std::move(b); full_ = true;
+        cv_.notify_all();
+    }
+    bool abandoned() { std::lock_guard<std::mutex> lk(mu_); return abandoned_; }
+    void finish(std::exception_ptr e) { std::lock_guard<std::mutex> lk(mu_); done_ = true; err_ = e; cv_.notify_all(); }
+    bool pop(BuildBatch &out)
+    {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return full_ || done_; });
+        if (!full_) return false;
+        out = std::move(slot_); full_ = false;
+        cv_.notify_all();
+        return true;
+    }
+    void abandon() { std::lock_guard<std::mutex> lk(mu_); abandoned_ = true; cv_.notify_all(); }   // the consumer left early
+    void rethrow() { std::lock_guard<std::mutex> lk(mu_); if (err_) std::rethrow_exception(err_); }
+private:
+    std::mutex mu_;
+    std::condition_variable cv_;
+    BuildBatch slot_;
+    bool full_ = false, done_ = false, abandoned_ = false;
+    std::exception_ptr err_;
+};
+
+// every FASTA record of every genome file is one sequence under the genome's taxid (feature_min.h:67-82)
+void read_build_batches(const std::vector<std::string> &paths, const std::vector<std::pair<std::string, tax_t>> &names, u64 batch_bases,
+                        BatchQueue &q)
+{
+    std::exception_ptr err;
+    try {
+        BuildBatch b;
+        for (const std::string &path : paths) {
+            if (q.abandoned()) break;
+            const tax_t tx = get_taxid(path.c_str(), names);
+            SeqReader rd(path.c_str());
+            bseq1_t rec;
+            while (rd.read(rec) >= 0) {
+                if (!b.taxids.empty() && b.bases.size() + rec.seq.size() > batch_bases) { q.push(std::move(b)); b = BuildBatch(); }
+                b.bases += rec.seq;
+                b.offsets.push_back(b.bases.size());
+                b.taxids.push_back(tx);
+            }
+        }
+        if (!b.taxids.empty()) q.push(std::move(b));
+    } catch (...) {
+        err = std::current_exception();
+    }
+    q.finish(err);
+}
 }  // namespace
 
 Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &parent, const char *seq2tax_path,
                  const BuildOptions &opt)
 {
     const auto names = build_name_hash(seq2tax_path);
-    // every FASTA record of every genome file is one sequence under the genome's taxid (feature_min.h:67-82)
-    std::string bases;
-    std::vector<u64> offsets{0};
-    std::vector<u32> taxids;
-    for (const std::string &path : paths) {
-        const tax_t tx = get_taxid(path.c_str(), names);
-        SeqReader rd(path.c_str());
-        bseq1_t rec;
-        while (rd.read(rec) >= 0) {
-            bases += rec.seq;
-            offsets.push_back(bases.size());
-            taxids.push_back(tx);
-        }
-    }
-    if (taxids.empty()) die("Need input files from command line or file. See usage.");
     const unsigned k = opt.k;
     spvec_t gaps = opt.spacing.empty() ? spvec_t(k - 1, 0) : opt.spacing;
     if (gaps.size() + 1 != k) die("Error: input vector must have size 1 less than k.");       // spacer.h:65-68
@@ -853,43 +919,77 @@ Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &
     chk(ctx, bns_set_window(ctx, w, opt.entropy ? BNS_SCORE_ENTROPY_PATH : BNS_SCORE_LEX), "bns_set_window");
     chk(ctx, bns_load_taxonomy(ctx, parent.data(), (u32)parent.size()), "bns_load_taxonomy");
 
-    u64 upper = 0;                                                                             // emitted values <= this
-    for (size_t i = 0; i + 1 < offsets.size(); ++i) {
-        const u64 L = offsets[i + 1] - offsets[i];
-        if (L >= span) upper += L - span + 1;
-        else if (L >= c) upper += 1;        // the emitted-stream modes (-C -w, real-entropy) flush one minimum for a sequence
-    }                                       // that never fills a window (encoder.h:304-305)
-    bases.resize(bases.size() + 8, 'N');                                                       // 4-byte readable tail
-    DevMem d_bases(ctx, bases.size()), d_off(ctx, offsets.size() * 8), d_tx(ctx, taxids.size() * 4);
-    chk(ctx, bns_dev_upload(ctx, d_bases.p, bases.data(), bases.size()), "upload");
-    chk(ctx, bns_dev_upload(ctx, d_off.p, offsets.data(), offsets.size() * 8), "upload");
-    chk(ctx, bns_dev_upload(ctx, d_tx.p, taxids.data(), taxids.size() * 4), "upload");
+    // The genome files go to the device's build session (bns_build_begin .. bns_build_end) in batches of whole sequences: this thread
+    // uploads and adds batch n while a second one reads batch n + 1.  Host memory and the HBM that holds bases are bounded by the
+    // batch; the table grows on the device as it must, and only the batch that did not fit is encoded again.
+    u64 batch_bases = opt.batch_bases ? opt.batch_bases : 1;
+    if (const char *e = std::getenv("BNS_BUILD_BATCH")) { const long long v = std::atoll(e); if (v > 0) batch_bases = (u64)v; }
+    BatchQueue q;
+    std::thread reader([&] { read_build_batches(paths, names, batch_bases, q); });
+    struct Join { BatchQueue &q; std::thread &t; ~Join() { q.abandon(); if (t.joinable()) t.join(); } } join{q, reader};
 
-    // khash grows when n_occupied has REACHED upper_bound and another key comes (khash64.h:330): upper_bound keys still fit
-    auto pow2_for = [](u64 keys) { u64 nb = 4; while ((u64)(nb * 0.77 + 0.5) < keys) nb <<= 1; return nb; };
-    // windowed dbs keep roughly 2/(ws+1) of the positions; start there and grow on BNS_ERR_TABLE
-    const u64 ws = w - c + 1;
-    u64 nb = pow2_for(ws > 1 ? std::max<u64>(1024, upper * 3 / (ws + 1)) : upper);
-    Database db;
-    for (int attempt = 0; attempt < 40; ++attempt) {
-        DevMem d_f(ctx, (nb < 16 ? 1 : nb >> 4) * 4), d_k(ctx, nb * 8), d_v(ctx, nb * 4);
-        u64 hdr[4] = {0, 0, 0, 0};
-        const int rc = bns_build_table_device(ctx, (const char *)d_bases.p, (const u64 *)d_off.p, taxids.size(),
-                                              offsets.back(), (const u32 *)d_tx.p, nb, (u32 *)d_f.p, (u64 *)d_k.p, (u32 *)d_v.p,
-                                              hdr, nullptr);
-        if (rc == BNS_ERR_TABLE) { nb <<= 1; continue; }                                       // load factor would exceed 0.77
-        chk(ctx, rc, "bns_build_table_device");
-        const u64 want = pow2_for(hdr[2]);
-        if (want < nb) { nb = want; continue; }                                                // compact to khash's own size
-        db.k_ = k; db.w_ = w; db.s_ = gaps;
-        db.db_.n_buckets = hdr[0]; db.db_.n_occupied = hdr[1]; db.db_.size = hdr[2]; db.db_.upper_bound = hdr[3];
-        db.db_.flags.resize(nb < 16 ? 1 : nb >> 4); db.db_.keys.resize(nb); db.db_.vals.resize(nb);
-        chk(ctx, bns_dev_download(ctx, db.db_.flags.data(), d_f.p, db.db_.flags.size() * 4), "download");
-        chk(ctx, bns_dev_download(ctx, db.db_.keys.data(), d_k.p, nb * 8), "download");
-        chk(ctx, bns_dev_download(ctx, db.db_.vals.data(), d_v.p, nb * 4), "download");
-        return db;
+    GrowMem d_bases(ctx), d_off(ctx), d_tx(ctx);
+    bool begun = false;
+    BuildBatch b;
+    double t_wait = 0, t_upload = 0, t_finish = 0;                                             // seconds of this thread (BNS_CLI_TIMING)
+    for (;;) {
+        const double tw0 = tnow();
+        const bool more = q.pop(b);
+        t_wait += tnow() - tw0;
+        if (!more) break;
+        if (!begun) {
+            u64 upper = 0;                                                                     // emitted values of the first batch <= this
+            for (size_t i = 0; i + 1 < b.offsets.size(); ++i) {
+                const u64 L = b.offsets[i + 1] - b.offsets[i];
+                if (L >= span) upper += L - span + 1;
+                else if (L >= c) upper += 1;    // the emitted-stream modes (-C -w, real-entropy) flush one minimum for a sequence
+            }                                   // that never fills a window (encoder.h:304-305)
+            // windowed dbs keep roughly 2/(ws+1) of the positions; the session starts there and grows from it
+            const u64 ws = w - c + 1;
+            u64 hint = 4;
+            const u64 est = ws > 1 ? std::max<u64>(1024, upper * 3 / (ws + 1)) : upper;
+            while ((u64)(hint * 0.77 + 0.5) < est) hint <<= 1;
+            chk(ctx, bns_build_begin(ctx, hint), "bns_build_begin");
+            if (opt.seed)
+                chk(ctx, bns_build_seed(ctx, opt.seed->db_.n_buckets, opt.seed->db_.flags.data(), opt.seed->db_.keys.data(),
+                                        opt.seed->db_.vals.data()), "bns_build_seed");
+            begun = true;
+        }
+        const u64 total = b.offsets.back();
+        b.bases.resize(b.bases.size() + 8, 'N');                                               // 4-byte readable tail
+        const double tu0 = tnow();
+        d_bases.ensure(b.bases.size()); d_off.ensure(b.offsets.size() * 8); d_tx.ensure(b.taxids.size() * 4);
+        chk(ctx, bns_dev_upload(ctx, d_bases.p, b.bases.data(), b.bases.size()), "upload");
+        chk(ctx, bns_dev_upload(ctx, d_off.p, b.offsets.data(), b.offsets.size() * 8), "upload");
+        chk(ctx, bns_dev_upload(ctx, d_tx.p, b.taxids.data(), b.taxids.size() * 4), "upload");
+        std::string().swap(b.bases);                                                           // (the device has them)
+        t_upload += tnow() - tu0;
+        chk(ctx, bns_build_add(ctx, (const char *)d_bases.p, (const u64 *)d_off.p, b.taxids.size(), total, (const u32 *)d_tx.p, nullptr),
+            "bns_build_add");
     }
-    die("could not size the hash table");
+    q.rethrow();
+    if (!begun) die("Need input files from command line or file. See usage.");
+    d_bases.release(); d_off.release(); d_tx.release();
+
+    Database db;
+    u64 hdr[4] = {0, 0, 0, 0}, stats[6] = {0, 0, 0, 0, 0, 0};
+    const double tf0 = tnow();
+    chk(ctx, bns_build_finish(ctx, hdr), "bns_build_finish");
+    chk(ctx, bns_build_stats(ctx, stats), "bns_build_stats");
+    const u64 nb = hdr[0];
+    db.k_ = k; db.w_ = w; db.s_ = gaps;
+    db.db_.n_buckets = hdr[0]; db.db_.n_occupied = hdr[1]; db.db_.size = hdr[2]; db.db_.upper_bound = hdr[3];
+    db.db_.flags.resize(nb < 16 ? 1 : nb >> 4); db.db_.keys.resize(nb); db.db_.vals.resize(nb);
+    chk(ctx, bns_build_export(ctx, db.db_.flags.data(), db.db_.keys.data(), db.db_.vals.data()), "bns_build_export");
+    chk(ctx, bns_build_end(ctx), "bns_build_end");
+    t_finish = tnow() - tf0;
+    if (std::getenv("BNS_CLI_TIMING")) {
+        std::fprintf(stderr, "[timing] build: waiting for the reader %.3f s, upload %.3f s, add %.3f s (of which growing %.3f s), finish + export %.3f s\n",
+                     t_wait, t_upload, (double)stats[4] * 1e-6, (double)stats[5] * 1e-6, t_finish);
+        std::fprintf(stderr, "build: %llu batches, %llu grows, %llu seeded keys, %llu keys in %llu buckets\n", (unsigned long long)stats[0],
+                     (unsigned long long)stats[1], (unsigned long long)stats[2], (unsigned long long)hdr[2], (unsigned long long)nb);
+    }
+    return db;
 }
 
 // ---------------------------------------------------------------------------------------------- Encoder

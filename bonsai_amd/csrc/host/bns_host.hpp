@@ -437,10 +437,16 @@ struct BuildOptions {
     bool canon = true;
     bool entropy = false;        // -e: score::Entropy (path-overload rule) instead of score::Lex
     int device = 0;
+    u64 batch_bases = 1ULL << 30;   // -B: the genome files reach the device in batches of whole sequences of at most this many bases
+                                    // (a longer sequence is a batch of its own); the environment's BNS_BUILD_BATCH overrides it
+    const Database *seed = nullptr; // -A: the db starts from this one's present slots.  k, wsz, spacing above must be the file's own (a
+                                    // bns.db records neither canon nor entropy: the caller repeats them)
 };
 // lca_map (feature_min.h:178-183 -> make_map :93-171 -> update_lca_map :205-228) on the GPU: every k-mer (or windowed
 // minimizer) of every sequence of genome g maps to get_taxid(g); shared ones to the lca.  Returns a Database whose
 // khash arrays are valid for kh_get and sized like khash would size them (smallest power of two with load <= 0.77).
+// The files are streamed through a build session of the device library (bns_build_begin ..): host memory holds a batch or two and
+// the finished table, never the whole input; with opt.seed the result is the map of a build over the seed db's genomes and these.
 Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &parent, const char *seq2tax_path,
                  const BuildOptions &opt);
 

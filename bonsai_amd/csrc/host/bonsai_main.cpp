@@ -370,6 +370,10 @@ void build_usage(const char *exe)
                  "-S: Set spacing.\n-T: Set tax_path (nodes.dmp).\n-M: Set seq2taxpath (name<TAB>taxid).\n"
                  "-F: Load genome paths from file.\n-C: Do not canonicalize.\n-z: Write gzip-compressed.\n"
                  "-p: Threads (accepted; the build runs on the GPU).\n-g: GPU index [0].\n"
+                 "-B: Bases per batch: the genome files reach the GPU in batches of whole sequences of at most this many bases. [1073741824]\n"
+                 "-A: Add to this db (old.bns[.gz]): the new db holds its keys and those of <paths>, as a build over all genomes would.\n"
+                 "    k, w and the spacing are taken from the file; a -k, -w or -S that disagrees is an error.  A db records neither -C\n"
+                 "    nor -e: repeat them as they were given when the db was built.  <out.path> may be the -A path itself.\n"
                  "-t / -f (tax-depth / feature-count minimisation) are not provided by this build.\n", exe);
     std::exit(EXIT_FAILURE);
 }
@@ -377,15 +381,17 @@ void build_usage(const char *exe)
 int build_main(int argc, char *argv[])
 {
     bns::BuildOptions opt;
-    std::string spacing, tax_path, seq2taxpath, paths_file;
-    bool gz = false;
+    std::string spacing, tax_path, seq2taxpath, paths_file, add_path;
+    bool gz = false, k_given = false, w_given = false;
     int c;
     if (argc < 4) build_usage(argv[0]);
-    while ((c = getopt(argc, argv, "Cw:M:S:p:k:T:F:g:tefzHh?")) >= 0) {
+    while ((c = getopt(argc, argv, "Cw:M:S:p:k:T:F:g:A:B:tefzHh?")) >= 0) {
         switch (c) {
             case 'C': opt.canon = false; break;
-            case 'k': opt.k = (unsigned)std::atoi(optarg); break;
-            case 'w': opt.wsz = std::atoi(optarg); break;
+            case 'k': opt.k = (unsigned)std::atoi(optarg); k_given = true; break;
+            case 'w': opt.wsz = std::atoi(optarg); w_given = true; break;
+            case 'A': add_path = optarg; break;
+            case 'B': { const long long v = std::atoll(optarg); if (v < 1) build_usage(argv[0]); opt.batch_bases = (bns::u64)v; } break;
             case 'e': opt.entropy = true; break;
             case 'S': spacing = optarg; break;
             case 'T': tax_path = optarg; break;
@@ -428,13 +434,43 @@ int build_main(int argc, char *argv[])
         if (seq2taxpath.empty()) throw bns::Error("seq2taxpath required for final database generation.");
         if (tax_path.empty()) throw bns::Error("Tax path required. [See -T option.]");
         if (opt.k < 1 || opt.k > 32) throw bns::Error("k must be in [1,32]");
-        opt.spacing = bns::parse_spacing(spacing.c_str(), opt.k);
+        // -A: k, w and the spacing are the file's; what the command line says about them must agree (checked before any device is opened)
+        std::unique_ptr<bns::Database> old_db;
+        if (!add_path.empty()) {
+            old_db.reset(new bns::Database(add_path.c_str()));
+            const bns::Database &o = *old_db;
+            if (o.k_ < 1 || o.k_ > 32 || o.s_.size() + 1 != o.k_) throw bns::Error("-A " + add_path + ": not a db this build can extend");
+            if (k_given && opt.k != o.k_)
+                throw bns::Error("-k " + std::to_string(opt.k) + " disagrees with k = " + std::to_string(o.k_) + " of -A " + add_path);
+            unsigned comb = o.k_;
+            for (bns::u16 g : o.s_) comb += g;
+            if (w_given) {
+                const unsigned w_eff = (unsigned)std::max<int>((int)comb, std::max<int>(opt.wsz, (int)o.k_));
+                if (w_eff != o.w_)
+                    throw bns::Error("-w " + std::to_string(opt.wsz) + " (window " + std::to_string(w_eff) + ") disagrees with w = " +
+                                     std::to_string(o.w_) + " of -A " + add_path);
+            }
+            if (!spacing.empty() && bns::parse_spacing(spacing.c_str(), o.k_) != o.s_) {
+                std::string have;
+                for (size_t i = 0; i < o.s_.size(); ++i) have += (i ? "," : "") + std::to_string(o.s_[i]);
+                throw bns::Error("-S " + spacing + " disagrees with the spacing " + have + " of -A " + add_path);
+            }
+            opt.k = o.k_; opt.wsz = (int)o.w_; opt.spacing = o.s_;
+            opt.seed = old_db.get();
+        } else {
+            opt.spacing = bns::parse_spacing(spacing.c_str(), opt.k);
+        }
         const std::vector<bns::u32> taxmap = bns::build_parent_map(tax_path.c_str());
         std::fprintf(stderr, "Final map will be written to %s\n", dbpath.c_str());
         const bns::Database db = bns::lca_map(inpaths, taxmap, seq2taxpath.c_str(), opt);
         // spacing entries as 1 byte each for the plain file (what Database(const char*) reads, database.h:46-48) and
         // 2 bytes each for .gz (what the reference's gz writer emits, database.h:89); this reader takes both
-        db.write(dbpath.c_str(), gz ? 2 : 1);
+        // (through a temporary file beside it: the db may be the -A file itself, and a failed write leaves no half db under its name)
+        const size_t slash = dbpath.rfind('/');
+        const std::string tmp = (slash == std::string::npos ? std::string() : dbpath.substr(0, slash + 1)) + ".tmp." +
+                                std::to_string((long long)getpid()) + "." + (slash == std::string::npos ? dbpath : dbpath.substr(slash + 1));
+        try { db.write(tmp.c_str(), gz ? 2 : 1); } catch (...) { std::remove(tmp.c_str()); throw; }
+        if (std::rename(tmp.c_str(), dbpath.c_str()) != 0) { std::remove(tmp.c_str()); throw bns::Error("Could not write " + dbpath); }
         std::fprintf(stderr, "Wrote %llu keys in %llu buckets\n", (unsigned long long)db.db_.size, (unsigned long long)db.db_.n_buckets);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "[E] %s\n", e.what());

@@ -398,6 +398,45 @@ int bns_build_table_device(bns_ctx *ctx, const char *d_bases, const uint64_t *d_
                            uint32_t *d_flags, uint64_t *d_keys, uint32_t *d_vals, uint64_t *header4,
                            void *stream);
 
+/* ---- build session (version 109): a table that persists in the context, grows, and can start from a bns.db -------------------
+ * bns_build_table_device wants all sequences in one call and a table size guessed in advance.  A session takes them batch by
+ * batch: the table lives in the context, doubles when a batch does not fit, and may be seeded from an existing khash table, so a
+ * db can be extended with new genomes alone.  The stored value is the lca() of all contributing taxids and the fold is
+ * order-free, so a seeded table plus new sequences is the table of a build over the union.
+ *   bns_build_begin   needs a loaded taxonomy and encoder, refuses what bns_build_table_device refuses (k == 32 forward contiguous,
+ *                     a spaced seed without spaced_intended), and allocates max(4, n_buckets_hint rounded up to a power of two)
+ *                     empty buckets.  A second begin -- and bns_set_encoder, bns_set_window or bns_load_taxonomy while the session
+ *                     is open -- returns BNS_ERR_STATE.
+ *   bns_build_seed    host arrays in bns_load_table's form; once, between begin and the first add.  Every slot whose flag pair is 0
+ *                     (present) goes in with its value as it is; empty AND deleted slots are skipped whatever their key and value
+ *                     words hold.  The session table is first sized so that the seeded keys sit at a load <= 0.77.
+ *   bns_build_add     one batch of whole sequences, the inputs of bns_build_table_device (device arrays; n_seqs + 1 offsets, the
+ *                     bases readable 8 bytes past the end).  Inserts the batch's keys and folds its taxids into the values.  When
+ *                     the table fills up, or more than 0.77 n_buckets keys are in, the table is doubled (rehashed on the device) and
+ *                     the SAME batch applied again -- inserting and folding are idempotent --, until it fits; earlier batches are
+ *                     never encoded again.  Returns when the device is done with the batch: the caller may free it.
+ *   bns_build_finish  compacts to khash's own size (the smallest power of two nb >= 4 with (uint64_t)(nb * 0.77 + 0.5) >= size),
+ *                     writes the flags, zeroes empty slots, and reports header4 = {n_buckets, n_occupied, size, upper_bound}.  A
+ *                     session without a key finishes as a valid empty table of 4 buckets.
+ *   bns_build_export  the finished arrays to the host, sized by header4 as bns_load_table's inputs are.
+ *   bns_build_stats   out6 = {batches added, grows, keys seeded, keys in the table, microseconds of wall time inside bns_build_add so
+ *                     far, the part of them spent growing} of the open session.
+ *   bns_build_end     frees the session; legal at any point (no session: nothing happens).  bns_destroy ends an open session.
+ * add / finish / export / seed / stats without a session, add after finish, export before finish and seed after an add return
+ * BNS_ERR_STATE.
+ * Memory: the table takes 12 bytes a bucket while it is built (12.25 finished).  A grow holds the old table and the new one side
+ * by side, so growing from n to 2n buckets needs 36 n bytes for a moment.  A grow that cannot be allocated returns BNS_ERR_TABLE
+ * with a message and faults nothing; after it -- as after any failed add -- the session holds keys without their values and
+ * accepts bns_build_end only. */
+int bns_build_begin(bns_ctx *ctx, uint64_t n_buckets_hint);
+int bns_build_seed(bns_ctx *ctx, uint64_t n_buckets, const uint32_t *flags, const uint64_t *keys, const uint32_t *vals);
+int bns_build_add(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bases,
+                  const uint32_t *d_taxid, void *stream);
+int bns_build_finish(bns_ctx *ctx, uint64_t *header4);
+int bns_build_export(bns_ctx *ctx, uint32_t *flags, uint64_t *keys, uint32_t *vals);
+int bns_build_stats(const bns_ctx *ctx, uint64_t *out6);
+int bns_build_end(bns_ctx *ctx);
+
 /* ---- instrumentation -------------------------------------------------------------------------- */
 /* HIP-event timing of the dominant kernel (classify_kernel / probe_kernel), recorded on the stream the
  * kernel is launched on.  bns_set_timing(ctx, 1) enables and clears.  bns_last_kernel_ms: most recent
