@@ -49,22 +49,16 @@ constexpr size_t SMALL_CLASSIFY_ZERO = offsetof(SmallLayout, max_len) + sizeof(u
 static_assert(sizeof(SmallLayout) <= SMALL_BYTES, "ctx->small is allocated with SMALL_BYTES");
 static_assert(offsetof(SmallLayout, load_cnt) >= SMALL_CLASSIFY_ZERO, "classify's memset must not reach the other entry points' words");
 
-// bns_debug_set bits (tests and profiling; 0 in production)
-constexpr int BNS_DBG_PLACE_FAIL = 0x100;           // every 61st bucket pretends to have no perfect hash (-> overflow table)
-constexpr int BNS_DBG_SPACED_NOCLUSTER = 0x200;     // spaced seeds: m = k, every k-mer its own bucket
+// bns_debug_set bits (tests and profiling; 0 in production); the table load's -- 0x10, 0x20, 0x100, 0x200, 0x1000, bits 16-20 and
+// 24-28 -- are in bns_table_plan.hpp
 constexpr int BNS_DBG_PEXT_OFF = 0x400;             // spaced seeds: gather run by run instead of through the compress network
 constexpr int BNS_DBG_FORCE_RCCL = 0x800;           // bns_load_table_multi with ONE context still broadcasts through RCCL (1-rank communicator)
-constexpr int BNS_DBG_STREAM_LOAD = 0x1000;         // bns_load_table streams the host arrays even when they would fit
 constexpr int BNS_DBG_OVC_OFF = 0x2000;             // classify: never the cooperative overflow lookup (A/B of the two forms)
 constexpr int BNS_DBG_OVC_ON = 0x8000;              // classify: always the cooperative overflow lookup
-constexpr int BNS_DBG_PLAIN_FILL = 0x10;            // bns_load_table: keys in arrival order even into a crowded table (A/B of the group-aware fill)
-constexpr int BNS_DBG_GROUP_FILL = 0x20;            // bns_load_table: the group-aware fill even for a table with room (tests reach it on small tables)
 constexpr int BNS_DBG_BATCH_TINY = 0x40;            // bns_classify_text: a classify launch per >= 64 records (many batches on small texts)
 constexpr int BNS_DBG_INSPECT_TINY = 0x8;           // bns_table_tally: grids of at most 4 workgroups that flush their LDS counters every 3 rounds (tests: many rounds, a full LDS hash and the mid-walk flush on small tables; same counts)
 constexpr int BNS_DBG_INSPECT_WHOLE = 0x80;         // bns_table_tally: fetch whole 128-byte buckets instead of their upper halves (A/B; same counts)
 constexpr int BNS_DBG_SLICE_8K = 0x4000;            // bns_classify_batch uploads in 8 KiB slices (the slicing logic on small batches)
-constexpr int BNS_DBG_STREAM_CHUNK_SHIFT = 16, BNS_DBG_STREAM_CHUNK_MASK = 0x1F << 16;   // log2 of the streamed chunk (0 = 27)
-constexpr int BNS_DBG_SPACED_M_SHIFT = 24, BNS_DBG_SPACED_M_MASK = 0x1F << 24;           // spaced seeds: force the run minimizer's m
 
 // What the last classify dispatch launched (bns_debug_last_classify_form, a test aid): the template arguments of the
 // classify_kernel instantiation, of the classify_overflow_kernel one when units went there, and the launch geometry.  Written
@@ -124,7 +118,7 @@ struct bns_ctx {
     u64 n_keys = 0;
     u32 slots_log2_req = 0;
     u64 n_buckets_req = 0;          // bns_set_table_buckets: exact number of home buckets (0 = automatic)
-    int fill_req = -1;              // bns_set_table_fill (and replicas taking the root's choice): -1 the loader decides, 0 arrival order, 1 group-aware fill
+    int fill_req = -1;              // bns_set_table_fill: -1 the loader decides, 0 arrival order, 1 group-aware fill
     int wide_req = -1;              // bns_set_minimizer_identity: -1 chosen from the key count, 0 narrow (32-bit), 1 wide (52-bit)
     bool table_wide = false;        // the loaded MINBUCKET table's identity
     u32 table_span = 0;             // the window candidate (MIN_CANDS span: 15 / 11 / 8) the loaded table was built with; 0: none (spaced seed)
@@ -170,6 +164,8 @@ namespace {
             return _e == hipErrorOutOfMemory ? BNS_ERR_NOMEM : BNS_ERR_HIP;                        \
         }                                                                                         \
     } while (0)
+
+#define BNS_RC(x) do { const int rc__ = (x); if (rc__ != BNS_OK) return rc__; } while (0)
 
 int fail(bns_ctx *ctx, int code, const std::string &msg)
 {
@@ -302,6 +298,7 @@ int ready(bns_ctx *ctx, bool need_table, bool need_tax)
 }  // namespace
 
 #include "bns_build.hpp"
+#include "bns_table_load.hpp"
 
 namespace {
 // Every classify_kernel / classify_overflow_kernel launch goes through these two: the instantiation launched and the one
@@ -652,546 +649,18 @@ int bns_set_minimizer_identity(bns_ctx *ctx, int bits)
     return BNS_OK;
 }
 
-// Where the khash arrays are read from while a bucket table is built: resident on the device (one "chunk"), or on the host,
-// streamed through a device staging buffer 2^27 slots at a time -- for dbs whose arrays and table do not fit the HBM together
-// (8e9 keys: 210 GB of arrays + a 230 GB table).  The fill / overflow kernels see one chunk at a time.
-namespace {
-struct KhHost { const u32 *flags = nullptr; const u64 *keys = nullptr; const u32 *vals = nullptr; };
-inline u64 stream_chunk(const bns_ctx *ctx)                     // slots per streamed chunk (tests run many small ones: debug bits 16-20)
-{
-    const int l = (ctx->dbg & BNS_DBG_STREAM_CHUNK_MASK) >> BNS_DBG_STREAM_CHUNK_SHIFT;
-    return l >= 4 ? 1ULL << l : 1ULL << 27;
-}
-// a clustered table is filled to this fraction of its 10 keys per bucket unless the caller fixes its size: the knee of the
-// load sweep (profiles/): kernel time within 2 % of a table eight times the size, a quarter of the memory of round 2's default
-constexpr double MINB_TARGET_LOAD = 1.0 / 12.0;
-}
-static int load_table_impl(bns_ctx *ctx, uint64_t n_buckets, const uint32_t *d_flags, const uint64_t *d_keys,
-                           const uint32_t *d_vals, const KhHost &host, int layout, void *stream);
-
 int bns_load_table_device(bns_ctx *ctx, uint64_t n_buckets, const uint32_t *d_flags, const uint64_t *d_keys,
                           const uint32_t *d_vals, int layout, void *stream)
 {
     if (!ctx || !d_flags || !d_keys || !d_vals) return BNS_ERR_ARG;
-    return load_table_impl(ctx, n_buckets, d_flags, d_keys, d_vals, KhHost{}, layout, stream);
-}
-
-static int load_table_impl(bns_ctx *ctx, uint64_t n_buckets, const uint32_t *d_flags, const uint64_t *d_keys,
-                           const uint32_t *d_vals, const KhHost &host, int layout, void *stream)
-{
-    const bool streamed = host.flags != nullptr;                 // (then the d_ pointers are null)
-    if (n_buckets == 0 || (n_buckets & (n_buckets - 1))) return fail(ctx, BNS_ERR_TABLE, "n_buckets must be a power of two");
-    if (layout != BNS_LAYOUT_KHASH && layout != BNS_LAYOUT_BUCKET && layout != BNS_LAYOUT_MINBUCKET) return BNS_ERR_ARG;
-    if (layout == BNS_LAYOUT_MINBUCKET && !ctx->enc_set)
-        return fail(ctx, BNS_ERR_STATE, "BNS_LAYOUT_MINBUCKET needs the encoder (k) configured before the table is loaded");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    // keep caller-owned arrays alive across free_table when they are the same pointers
-    const bool same = !streamed && (d_flags == ctx->kflags);
-    if (!same) free_table(ctx);
-    else {
-        if (ctx->slots) (void)hipFree(ctx->slots);
-        if (ctx->ovf_slots) (void)hipFree(ctx->ovf_slots);
-        ctx->slots = nullptr; ctx->n_slots = 0; ctx->n_mb = 0; ctx->ovf_slots = nullptr; ctx->n_ovf_slots = 0; ctx->n_ovf_keys = 0;
-    }
-    ctx->warn.clear();
-
-    if (layout == BNS_LAYOUT_KHASH) {
-        if (streamed) return fail(ctx, BNS_ERR_ARG, "BNS_LAYOUT_KHASH probes the arrays themselves: they must be resident");
-        ctx->kflags = d_flags; ctx->kkeys = d_keys; ctx->kvals = d_vals; ctx->kh_nb = n_buckets;
-        ctx->layout = BNS_LAYOUT_KHASH;
-        // present keys (what kh_size would say): one pass over the flag words, so that bns_table_info says what the other layouts'
-        // loads say and bns_table_tally's sum(direct) can be held against it
-        unsigned long long *d_n = ((SmallLayout *)ctx->small.p)->load_cnt, n_present = 0;
-        HIPCHK(ctx, hipMemsetAsync(d_n, 0, 8, st));
-        hipLaunchKernelGGL(count_present_kernel, dim3(grid_for(ctx, std::max<u64>(1, n_buckets >> 4), 256)), dim3(256), 0, st, d_flags, (u64)n_buckets, d_n);
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(&n_present, d_n, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        ctx->n_keys = n_present;
-        return BNS_OK;
-    }
-    SmallLayout *sm = (SmallLayout *)ctx->small.p;
-    unsigned long long *d_cnt = sm->load_cnt;
-    // every pass over the khash arrays goes through here: fn(flags, keys, vals, n) once for resident arrays, once per chunk
-    // (uploaded into the staging buffers, stream-ordered behind the previous chunk's kernel) for streamed ones.  flags_only: the
-    // pass reads nothing else (the key count), so nothing else crosses PCIe; max_chunks: stop after that many (window sampling).
-    u32 *sf = nullptr; u64 *sk = nullptr; u32 *sv = nullptr;
-    struct Stage { u32 *&f; u64 *&k; u32 *&v; ~Stage() { if (f) (void)hipFree(f); if (k) (void)hipFree(k); if (v) (void)hipFree(v); } } stage{sf, sk, sv};
-    const u64 STREAM_CHUNK = stream_chunk(ctx);
-    if (streamed) {
-        const u64 cn = std::min<u64>(n_buckets, STREAM_CHUNK);
-        HIPCHK(ctx, hipMalloc((void **)&sf, std::max<u64>(1, cn >> 4) * 4));
-        HIPCHK(ctx, hipMalloc((void **)&sk, cn * 8));
-        HIPCHK(ctx, hipMalloc((void **)&sv, cn * 4));
-    }
-    auto for_chunks = [&](auto fn, bool flags_only = false, u64 max_chunks = ~0ULL, bool no_vals = false) -> int {
-        if (!streamed) { fn(d_flags, d_keys, d_vals, (u64)n_buckets); return BNS_OK; }
-        u64 done = 0;
-        for (u64 o = 0; o < n_buckets && done < max_chunks; o += STREAM_CHUNK, ++done) {
-            const u64 cn = std::min<u64>(STREAM_CHUNK, n_buckets - o);
-            HIPCHK(ctx, hipMemcpyAsync(sf, host.flags + (o >> 4), std::max<u64>(1, cn >> 4) * 4, hipMemcpyHostToDevice, st));
-            if (!flags_only) {
-                HIPCHK(ctx, hipMemcpyAsync(sk, host.keys + o, cn * 8, hipMemcpyHostToDevice, st));
-                if (!no_vals) HIPCHK(ctx, hipMemcpyAsync(sv, host.vals + o, cn * 4, hipMemcpyHostToDevice, st));
-            }
-            fn((const u32 *)sf, (const u64 *)sk, (const u32 *)sv, cn);
-            HIPCHK(ctx, hipGetLastError());
-        }
-        return BNS_OK;
-    };
-#define BNS_RC(x) do { const int rc__ = (x); if (rc__ != BNS_OK) return rc__; } while (0)
-    // present keys (what kh_size would say): the table is sized from them, not from the khash bucket count (a khash is
-    // anywhere between 38 % and 77 % full)
-    unsigned long long n_present = 0;
-    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, sizeof(sm->load_cnt), st));
-    BNS_RC(for_chunks([&](const u32 *cf, const u64 *, const u32 *, u64 cn) {
-        hipLaunchKernelGGL(count_present_kernel, dim3(grid_for(ctx, std::max<u64>(1, cn >> 4), 256)), dim3(256), 0, st, cf, cn, d_cnt);
-    }, true));
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(&n_present, d_cnt, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
-    Slot *slots = nullptr;
-    Slot *ovf = nullptr;
-    // tens of GB each: released on every early return below (HIPCHK returns from the function), kept on success
-    struct Release { Slot *&a; Slot *&b; bool keep = false; ~Release() { if (!keep) { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } } release{slots, ovf};
-    u64 n_slots = 0, n_mb = 0, n_ovf_slots = 0, n_ovf_keys = 0;
-    MinSpec table_spec{ctx->k, ctx->k, 0u, 1u, 0u};
-
-    if (layout == BNS_LAYOUT_BUCKET) {
-        // plain bucket layout: a power of two of 16-byte slots, 2x the khash bucket count by default; capacity must cover even a
-        // khash with every slot present, or the fill could never terminate
-        u32 lg = 0;
-        while ((1ULL << lg) < n_buckets) ++lg;
-        u32 want = ctx->slots_log2_req ? ctx->slots_log2_req : lg + 1;
-        if (want < 4) want = 4;
-        if (((size_t)16 << want) > free_b) return fail(ctx, BNS_ERR_NOMEM, "bucket table does not fit in free HBM");
-        n_slots = 1ULL << want;
-        if (n_slots <= n_buckets) return fail(ctx, BNS_ERR_ARG, "bucket_slots_log2 too small for this khash");
-        HIPCHK(ctx, hipMalloc((void **)&slots, n_slots * sizeof(Slot)));
-        HIPCHK(ctx, hipMemsetAsync(slots, 0, n_slots * sizeof(Slot), st));
-        HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, sizeof(sm->load_cnt), st));
-        BNS_RC(for_chunks([&](const u32 *cf, const u64 *ck, const u32 *cv, u64 cn) {
-            hipLaunchKernelGGL(rebucket_kernel, dim3(grid_for(ctx, cn, 256)), dim3(256), 0, st, cf, ck, cv, cn, slots, n_slots / 4 - 1, d_cnt);
-        }));
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipStreamSynchronize(st));
-    } else {
-        // ---- clustered layout: how many buckets.  Automatic: MINB_TARGET_LOAD, or what fits in three quarters of the free HBM
-        // (the overflow table and the caller's batches need room too); any count will do, the bucket index is a multiply-high.
-        const u64 mem_cap = (u64)(free_b / 4 * 3 / sizeof(MinBucket));
-        const u64 hard_cap = (1ULL << 31) - 8;                    // bucket indices are 31-bit
-        u64 want = ctx->n_buckets_req ? ctx->n_buckets_req
-                 : ctx->slots_log2_req ? std::max<u64>(1, (1ULL << ctx->slots_log2_req) / 8)
-                 : std::max<u64>(64, (u64)((double)n_present / (MINB_CAP * MINB_TARGET_LOAD)));
-        if (!ctx->n_buckets_req && !ctx->slots_log2_req) want = std::min(want, mem_cap);
-        if (want > hard_cap) {
-            if (ctx->n_buckets_req || ctx->slots_log2_req) return fail(ctx, BNS_ERR_ARG, "more than 2^31 buckets: bucket indices are 31-bit");
-            want = hard_cap;
-        }
-        n_mb = want;
-        const u64 n_alloc = n_mb + MINB_MAX_CHAIN - 1;             // spill-only buckets behind the last home: chains never wrap
-        if (n_alloc * sizeof(MinBucket) > free_b) return fail(ctx, BNS_ERR_NOMEM, "bucket table does not fit in free HBM");
-        if ((double)n_mb * MINB_CAP * 0.97 < (double)n_present) return fail(ctx, BNS_ERR_TABLE, "bucket table too small for the key count");
-        n_slots = n_alloc * 8;
-        HIPCHK(ctx, hipMalloc((void **)&slots, n_alloc * sizeof(MinBucket)));
-        HIPCHK(ctx, hipMemsetAsync(slots, 0, n_alloc * sizeof(MinBucket), st));
-        MinBucket *mb = reinterpret_cast<MinBucket *>(slots);
-        // ---- where the minimizer comes from.  Contiguous seeds: canonical m-mers of the whole key.  Spaced seeds: plain m-mers
-        // inside the mask's longest run of adjacent sampled bases, if there is one long enough -- m is then the smallest length
-        // with 4^m >= the number of keys (so that minimizer groups rarely share a value: groups are 2-3 keys, a bucket holds 10),
-        // at least run - 8 (a group must fit a bucket) and at most run - 1 (a window of two m-mers is the least that lets
-        // neighbours share); otherwise m = k: every k-mer its own bucket.
-        std::vector<MinSpec> cands;
-        std::vector<u32> cand_span;
-        if (ctx->spaced) {
-            MinSpec ms{ctx->k, ctx->k, 0u, 1u, 0u};
-            const u32 R = ctx->sp_run_len;
-            if (R >= 12 && !(ctx->dbg & BNS_DBG_SPACED_NOCLUSTER)) {
-                u32 m = 11;
-                while (m < 32 && (1ULL << (2 * m)) < n_present) ++m;
-                if (const int force = (ctx->dbg & BNS_DBG_SPACED_M_MASK) >> BNS_DBG_SPACED_M_SHIFT) m = (u32)std::max(8, force);   // profiling aid
-                const bool forced = ((ctx->dbg & BNS_DBG_SPACED_M_MASK) >> BNS_DBG_SPACED_M_SHIFT) != 0;
-                if (m + 8 < R) m = R - 8;
-                // one base shorter is tried first: a window of one more m-mer means a third fewer bucket fetches per run, and a kernel
-                // bound by its fetches gains from that as long as the groups still fit -- accepted below when fewer than 5 keys in
-                // 100 miss their home bucket (configs[2]'s 7.8e8-key db: m = 14 instead of 15, 4.4 % outside, 14.28 -> 13.45 ms; a
-                // 2.3e8-key db: m = 13 would leave 19 % outside, 12.1 -> 16.6 ms, and is refused)
-                if (!forced && m >= 9 && m + 7 >= R && m <= R) { cands.push_back(MinSpec{m - 1, R, ctx->sp_run_shift, 0u, 0u}); cand_span.push_back(0u); }
-                if (m + 1 <= R) ms = MinSpec{m, R, ctx->sp_run_shift, 0u, 0u};
-            }
-            cands.push_back(ms); cand_span.push_back(0u);
-        } else {
-            // Contiguous seeds: the widest minimizer window whose groups still fit their buckets (MIN_CANDS: k - m = 15, 11, 8; a
-            // wider window means fewer bucket fetches per read -- 16 instead of 25 per 150-bp read -- but groups of up to k - m + 1
-            // keys in buckets of 10).  A candidate is taken when fewer than 1 key in 100 misses its home bucket when the table is
-            // filled with it (tools/span_calib.sh); the last one always is.  A db of every k-mer fails the wide windows at once and
-            // ends at 8; a db of window minimizers (bonsai build -w 50: one k-mer in ten) takes 15.  bns_set_minimizer_span() fixes
-            // the window, bns_set_minimizer_identity() the identity (default: wide from WIDE_MIN_KEYS keys on).
-            // the identity: fixed by bns_set_minimizer_identity(), else both forms go into the trial (narrow ones first)
-            for (u32 wide = 0; wide < 2; ++wide) {
-                if (ctx->wide_req >= 0 && (u32)ctx->wide_req != wide) continue;
-                for (int ci = 0; ci < 3; ++ci) {
-                    const MinCand cand = MIN_CANDS[ci];
-                    if (ctx->min_span_req && cand.span != ctx->min_span_req) continue;
-                    const u32 m = minimizer_len(ctx->k, cand);
-                    if (wide && m >= ctx->k) continue;           // (no window, nothing to carry through it)
-                    if (!cands.empty() && cands.back().m == m && cands.back().wide == wide) continue;
-                    cands.push_back(MinSpec{m, ctx->k, 0u, 1u, wide}); cand_span.push_back(cand.span);
-                }
-            }
-            // (the wide identity asked for, but k so small that there is no window to carry it through: the narrow form it is)
-            if (cands.empty()) { cands.push_back(MinSpec{minimizer_len(ctx->k, MIN_CANDS[2]), ctx->k, 0u, 1u, 0u}); cand_span.push_back(MIN_CANDS[2].span); }
-        }
-        // ---- choose.  One pass over the khash arrays tries all candidates at once on a sample of the BUCKETS (every bucket for a
-        // small table, one in 2^j for a large one: whole minimizer groups, at the table's own load) and counts the keys that miss
-        // their home bucket (minbucket_trial_kernel); then ONE fill with the winner.  Streamed arrays cross PCIe twice (flags and
-        // keys for the trial, everything for the fill) whatever the number of candidates; round 2 filled the whole table once per
-        // candidate.
-        unsigned long long h2[5] = {0, 0, 0, 0, 0};
-        size_t pick = cands.size() - 1;
-        double trial_miss = 0.0;                                   // the chosen candidate's share of keys outside their home bucket
-        if (cands.size() > 1) {
-            u32 sample = (u32)n_mb;
-            while (sample > (1u << 22)) sample >>= 1;               // at most 4 M sampled buckets: plenty of groups
-            const size_t img = (size_t)(sample + MINB_MAX_CHAIN);
-            u32 *d_img = nullptr;
-            struct Img { u32 *&p; ~Img() { if (p) (void)hipFree(p); } } img_guard{d_img};
-            HIPCHK(ctx, hipMalloc((void **)&d_img, cands.size() * img * sizeof(u32)));
-            HIPCHK(ctx, hipMemsetAsync(d_img, 0, cands.size() * img * sizeof(u32), st));
-            unsigned long long *d_trial = nullptr;
-            struct Tr { unsigned long long *&p; ~Tr() { if (p) (void)hipFree(p); } } tr_guard{d_trial};
-            HIPCHK(ctx, hipMalloc((void **)&d_trial, 18 * sizeof(unsigned long long)));
-            HIPCHK(ctx, hipMemsetAsync(d_trial, 0, 18 * sizeof(unsigned long long), st));
-            TrialCands tc;
-            tc.n = (u32)cands.size();
-            for (size_t ci = 0; ci < cands.size(); ++ci) tc.c[ci] = cands[ci];
-            BNS_RC(for_chunks([&](const u32 *cf, const u64 *ck, const u32 *, u64 cn) {
-                hipLaunchKernelGGL(minbucket_trial_kernel, dim3(grid_for(ctx, cn, 256)), dim3(256), 0, st, cf, ck, cn, (u32)n_mb, sample, d_img, d_trial, ctx->k, tc);
-            }, false, ~0ULL, true));
-            HIPCHK(ctx, hipGetLastError());
-            unsigned long long tr[18] = {0};
-            HIPCHK(ctx, hipMemcpyAsync(tr, d_trial, sizeof(tr), hipMemcpyDeviceToHost, st));
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            auto missfrac = [&](size_t ci) { return tr[3 * ci] ? (double)(tr[3 * ci + 1] + tr[3 * ci + 2]) / (double)tr[3 * ci] : 0.0; };
-            // per identity: the widest window with fewer than 1 key in 100 outside its home bucket, else the narrowest
-            size_t best[2] = {cands.size(), cands.size()};
-            for (u32 wide = 0; wide < 2; ++wide) {
-                size_t last = cands.size();
-                for (size_t ci = 0; ci < cands.size(); ++ci) {
-                    if (cands[ci].wide != wide) continue;
-                    last = ci;
-                    if (missfrac(ci) < 0.01) break;
-                }
-                best[wide] = last;
-            }
-            // the wide identity costs ~7 % of kernel time (a 64-bit ring, v_min_f64 per window entry): worth it when the narrow
-            // table leaves more than 2 keys in 100 outside their home bucket and the wide one at most 60 % of that (calibrated:
-            // a 9e8-key db of window minimizers 0.4 % -> narrow, 6.49 vs 6.94 ms; every-k-mer dbs of 9e8 / 1.8e9 keys 6.9 % /
-            // 12 % -> wide, 8.05 vs 8.26 and 8.44 vs 9.26 ms)
-            pick = best[0] < cands.size() ? best[0] : best[1];
-            if (best[0] < cands.size() && best[1] < cands.size() && missfrac(best[0]) >= 0.02 && missfrac(best[1]) <= 0.6 * missfrac(best[0])) pick = best[1];
-            if (ctx->spaced) pick = missfrac(0) < 0.05 ? 0 : cands.size() - 1;       // (two candidates: the longer window when its groups fit)
-            trial_miss = missfrac(pick);
-        }
-        table_spec = cands[pick];
-        ctx->table_span = cand_span[pick];
-        // ---- fill.  A table with room takes its keys in arrival order; a crowded one -- the trial left more than 1 key in 100
-        // outside its home bucket, or (no trial: one candidate) the table is more than an eighth full -- is filled group by group
-        // (minbucket_tagcount_kernel: count, decide, residents, the rest): two more passes over the arrays, and about half as many
-        // of a read's runs need a second probe pass.  BNS_DBG_PLAIN_FILL / BNS_DBG_GROUP_FILL force one or the other (tests, A/B).
-        const bool crowded = cands.size() > 1 ? trial_miss >= 0.01 : (double)n_present > 0.125 * (double)n_mb * MINB_CAP;
-        const bool group_fill = ctx->fill_req >= 0 ? ctx->fill_req == 1 : (!(ctx->dbg & BNS_DBG_PLAIN_FILL) && (crowded || (ctx->dbg & BNS_DBG_GROUP_FILL)));
-        ctx->group_fill = group_fill;
-        {
-            HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, sizeof(sm->load_cnt), st));   // [0] present, [1] chain exhausted, [2] moved by place, [3] error, [4] spilled, [5] [6] decide
-            if (group_fill) {
-                BNS_RC(for_chunks([&](const u32 *cf, const u64 *ck, const u32 *, u64 cn) {
-                    hipLaunchKernelGGL(minbucket_tagcount_kernel, dim3(grid_for(ctx, cn, 256)), dim3(256), 0, st, cf, ck, cn, mb, (u32)n_mb, ctx->k, table_spec);
-                }, false, ~0ULL, true));
-                hipLaunchKernelGGL(minbucket_decide_kernel, dim3(grid_for(ctx, n_mb, 256)), dim3(256), 0, st, mb, n_mb, d_cnt + 5);
-                BNS_RC(for_chunks([&](const u32 *cf, const u64 *ck, const u32 *cv, u64 cn) {
-                    hipLaunchKernelGGL(minbucket_fill_kernel<1>, dim3(grid_for(ctx, cn, 256)), dim3(256), 0, st, cf, ck, cv, cn, mb, (u32)n_mb, d_cnt, ctx->k, table_spec);
-                }));
-                BNS_RC(for_chunks([&](const u32 *cf, const u64 *ck, const u32 *cv, u64 cn) {
-                    hipLaunchKernelGGL(minbucket_fill_kernel<2>, dim3(grid_for(ctx, cn, 256)), dim3(256), 0, st, cf, ck, cv, cn, mb, (u32)n_mb, d_cnt, ctx->k, table_spec);
-                }));
-            } else
-            BNS_RC(for_chunks([&](const u32 *cf, const u64 *ck, const u32 *cv, u64 cn) {
-                hipLaunchKernelGGL(minbucket_fill_kernel<0>, dim3(grid_for(ctx, cn, 256)), dim3(256), 0, st, cf, ck, cv, cn, mb, (u32)n_mb, d_cnt, ctx->k, table_spec);
-            }));
-            HIPCHK(ctx, hipGetLastError());
-            HIPCHK(ctx, hipMemcpyAsync(h2, d_cnt, 40, hipMemcpyDeviceToHost, st));
-            HIPCHK(ctx, hipStreamSynchronize(st));
-        }
-        ctx->n_spilled = h2[4];
-        if (h2[0] && (h2[4] + h2[1]) * 100ULL >= h2[0]) {
-            char buf[256];
-            std::snprintf(buf, sizeof(buf), "%llu of %llu keys (%.1f %%) are not in their home bucket (minimizer window %u, %.0f %% load): lookups of "
-                          "this table take extra probe passes; a larger table (bns_set_table_buckets) or a narrower window helps",
-                          (unsigned long long)(h2[4] + h2[1]), (unsigned long long)h2[0], 100.0 * (double)(h2[4] + h2[1]) / (double)h2[0],
-                          ctx->k - table_spec.m, 100.0 * (double)h2[0] / ((double)n_mb * MINB_CAP));
-            ctx->warn = buf;
-        }
-        n_ovf_keys = h2[1];
-        n_ovf_slots = 64;
-        // at most half full (+2048: room for the buckets minbucket_place_kernel may move here -- about one in 1e8; under the test
-        // switch that fails every 61st bucket, room for all of those)
-        const u64 place_room = 2048 + ((ctx->dbg & BNS_DBG_PLACE_FAIL) ? n_alloc / 61 * MINB_CAP + MINB_CAP : 0);
-        while (n_ovf_slots < 2 * (n_ovf_keys + place_room)) n_ovf_slots <<= 1;
-        HIPCHK(ctx, hipMalloc((void **)&ovf, n_ovf_slots * sizeof(Slot)));
-        HIPCHK(ctx, hipMemsetAsync(ovf, 0, n_ovf_slots * sizeof(Slot), st));
-        u32 *d_err = reinterpret_cast<u32 *>(d_cnt + 3);
-        if (n_ovf_keys)
-            BNS_RC(for_chunks([&](const u32 *cf, const u64 *ck, const u32 *cv, u64 cn) {
-                hipLaunchKernelGGL(minbucket_overflow_kernel, dim3(grid_for(ctx, cn, 256)), dim3(256), 0, st, cf, ck, cv, cn,
-                                   (const MinBucket *)mb, (u32)n_mb, ovf, n_ovf_slots / 4 - 1, ctx->k, table_spec, d_err);
-            }));
-        hipLaunchKernelGGL(minbucket_place_kernel, dim3(grid_for(ctx, n_alloc, 4)), dim3(256), 0, st, mb, n_alloc, (u32)n_mb, ovf, n_ovf_slots / 4 - 1, d_cnt + 2, d_err,
-                           (u32)((ctx->dbg & BNS_DBG_PLACE_FAIL) ? 61 : 0), ctx->k, table_spec);
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(h2, d_cnt, 32, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        n_ovf_keys += h2[2];
-        if (h2[3]) return fail(ctx, BNS_ERR_TABLE, "overflow table full while placing bucket keys");
-    }
-    unsigned long long h_cnt = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&h_cnt, d_cnt, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (layout == BNS_LAYOUT_BUCKET && h_cnt >= n_slots) return fail(ctx, BNS_ERR_TABLE, "bucket table too small for the key count");
-    release.keep = true;
-    ctx->slots = slots; ctx->n_slots = n_slots; ctx->n_mb = (u32)n_mb; ctx->n_keys = h_cnt;
-    ctx->ovf_slots = ovf; ctx->n_ovf_slots = n_ovf_slots; ctx->n_ovf_keys = n_ovf_keys;
-    ctx->layout = layout; ctx->table_k = ctx->k;
-    ctx->table_m = table_spec.m; ctx->table_len = table_spec.len; ctx->table_shift = table_spec.shift; ctx->table_canon = table_spec.canon;
-    ctx->table_wide = table_spec.wide != 0;
-    if (same && ctx->own_khash) {                     // host-upload path: the khash copy is no longer needed
-        (void)hipFree((void *)ctx->kflags); (void)hipFree((void *)ctx->kkeys); (void)hipFree((void *)ctx->kvals);
-        ctx->own_khash = false;
-    }
-    ctx->kflags = nullptr; ctx->kkeys = nullptr; ctx->kvals = nullptr; ctx->kh_nb = 0;
-    return BNS_OK;
+    return load_table_resident(ctx, n_buckets, d_flags, d_keys, d_vals, layout, stream);
 }
 
 int bns_load_table(bns_ctx *ctx, uint64_t n_buckets, const uint32_t *flags, const uint64_t *keys, const uint32_t *vals, int layout)
 {
     if (!ctx || !flags || !keys || !vals) return BNS_ERR_ARG;
-    if (n_buckets == 0 || (n_buckets & (n_buckets - 1))) return fail(ctx, BNS_ERR_TABLE, "n_buckets must be a power of two");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    free_table(ctx);
-    const size_t fs = n_buckets < 16 ? 1 : (size_t)(n_buckets >> 4);
-    if (layout != BNS_LAYOUT_KHASH) {
-        // a db whose arrays and a useful table (16 bytes per khash bucket) do not fit the HBM together is streamed from the host
-        // buffers instead of being uploaded whole (BNS_DBG_STREAM_LOAD forces that path: tests)
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
-        const size_t arrays = fs * 4 + (size_t)n_buckets * 12;
-        if ((ctx->dbg & BNS_DBG_STREAM_LOAD) || arrays + (size_t)n_buckets * 16 > free_b / 100 * 85)
-            return load_table_impl(ctx, n_buckets, nullptr, nullptr, nullptr, KhHost{flags, keys, vals}, layout, ctx->stream);
-    }
-    u32 *df = nullptr; u64 *dk = nullptr; u32 *dv = nullptr;
-    // each pointer goes into the context as soon as it exists, so free_table() releases it whatever fails next
-    ctx->own_khash = true; ctx->kh_nb = n_buckets;
-    HIPCHK(ctx, hipMalloc((void **)&df, fs * 4));
-    ctx->kflags = df;
-    HIPCHK(ctx, hipMalloc((void **)&dk, (size_t)n_buckets * 8));
-    ctx->kkeys = dk;
-    HIPCHK(ctx, hipMalloc((void **)&dv, (size_t)n_buckets * 4));
-    ctx->kvals = dv;
-    HIPCHK(ctx, hipMemcpyAsync(df, flags, fs * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(dk, keys, (size_t)n_buckets * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(dv, vals, (size_t)n_buckets * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    const int rc = bns_load_table_device(ctx, n_buckets, df, dk, dv, layout, ctx->stream);
-    if (rc == BNS_OK && layout == BNS_LAYOUT_KHASH) ctx->own_khash = true;
-    return rc;
+    return load_table_host(ctx, n_buckets, flags, keys, vals, layout);
 }
-
-// ---- multi-GPU table load: one upload, RCCL broadcast over xGMI, one device-side re-hash per GPU -------------------------
-// librccl is opened lazily and privately (RTLD_LOCAL) the first time a broadcast is wanted: a single-GPU process never maps it,
-// and a host that already carries its own RCCL (PyTorch ships one) does not get a second set of nccl* symbols in its global
-// namespace.  The entry points' types come from <rccl/rccl.h> itself (decltype of the declarations): a signature or enum that
-// drifts is a compile error here, not a silent ABI mismatch behind dlsym.
-namespace {
-struct Rccl {
-    void *lib = nullptr;
-    decltype(&ncclCommInitAll) CommInitAll = nullptr;
-    decltype(&ncclCommDestroy) CommDestroy = nullptr;
-    decltype(&ncclGroupStart) GroupStart = nullptr;
-    decltype(&ncclGroupEnd) GroupEnd = nullptr;
-    decltype(&ncclBroadcast) Broadcast = nullptr;
-    decltype(&ncclGetErrorString) GetErrorString = nullptr;
-    decltype(&ncclGetVersion) GetVersion = nullptr;
-    int version = 0, last_ranks = 0;            // what bns_rccl_info reports: the library's version code, the ranks of the last broadcast
-    std::once_flag once;
-    std::string open_err;
-    bool ok = false;
-    bool open(std::string &err)
-    {
-        std::call_once(once, [this] {
-            for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-                lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-                if (lib) break;
-            }
-            if (!lib) { const char *de = dlerror(); open_err = std::string("cannot open librccl: ") + (de ? de : "?"); return; }
-            auto sym = [&](const char *n) { void *q = dlsym(lib, n); if (!q && open_err.empty()) open_err = std::string("librccl lacks ") + n; return q; };
-            CommInitAll = (decltype(CommInitAll))sym("ncclCommInitAll");
-            CommDestroy = (decltype(CommDestroy))sym("ncclCommDestroy");
-            GroupStart = (decltype(GroupStart))sym("ncclGroupStart");
-            GroupEnd = (decltype(GroupEnd))sym("ncclGroupEnd");
-            Broadcast = (decltype(Broadcast))sym("ncclBroadcast");
-            GetErrorString = (decltype(GetErrorString))sym("ncclGetErrorString");
-            GetVersion = (decltype(GetVersion))dlsym(lib, "ncclGetVersion");
-            if (GetVersion) (void)GetVersion(&version);
-            ok = CommInitAll && CommDestroy && GroupStart && GroupEnd && Broadcast && GetErrorString;
-        });
-        if (!ok) err = open_err;
-        return ok;
-    }
-};
-Rccl g_rccl;
-
-// One communicator over the contexts' devices (a single process driving several devices: every rank's call inside one group),
-// one grouped ncclBroadcast per array from rank 0.  n_ctx == 1 is legal (a one-rank communicator: how a one-GPU box executes the
-// real RCCL calls); duplicate devices are not (RCCL admits a device once per communicator).
-int rccl_broadcast(bns_ctx **ctxs, int n_ctx, const std::vector<std::array<void *, 3>> &dev, const size_t bytes[3], std::string &err)
-{
-    if (!g_rccl.open(err)) return BNS_ERR_HIP;
-    std::vector<int> devs((size_t)n_ctx);
-    for (int i = 0; i < n_ctx; ++i) devs[(size_t)i] = ctxs[i]->device;
-    std::vector<ncclComm_t> comms((size_t)n_ctx, nullptr);
-    ncclResult_t rc = g_rccl.CommInitAll(comms.data(), n_ctx, devs.data());
-    if (rc != ncclSuccess) { err = std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(rc); return BNS_ERR_HIP; }
-    bool hip_fail = false;
-    for (int a = 0; a < 3 && rc == ncclSuccess && !hip_fail; ++a) {
-        rc = g_rccl.GroupStart();
-        for (int i = 0; i < n_ctx && rc == ncclSuccess; ++i) {
-            if (hipSetDevice(ctxs[i]->device) != hipSuccess) { hip_fail = true; break; }
-            // (every rank passes its OWN buffer as send and receive buffer: in place on the root, ignored as a source elsewhere)
-            rc = g_rccl.Broadcast(dev[(size_t)i][a], dev[(size_t)i][a], bytes[a], ncclUint8, 0, comms[(size_t)i], ctxs[i]->stream);
-        }
-        const ncclResult_t rc2 = g_rccl.GroupEnd();
-        if (rc == ncclSuccess) rc = rc2;
-    }
-    for (int i = 0; i < n_ctx; ++i) { (void)hipSetDevice(ctxs[i]->device); (void)hipStreamSynchronize(ctxs[i]->stream); }
-    for (int i = 0; i < n_ctx; ++i) if (comms[(size_t)i]) (void)g_rccl.CommDestroy(comms[(size_t)i]);
-    if (rc == ncclSuccess && !hip_fail) g_rccl.last_ranks = n_ctx;
-    if (rc != ncclSuccess || hip_fail) {
-        err = std::string("RCCL broadcast of the table: ") + (hip_fail ? "hipSetDevice failed" : g_rccl.GetErrorString(rc));
-        return BNS_ERR_HIP;
-    }
-    return BNS_OK;
-}
-
-// HIPCHK for the multi-context loader: remembers WHICH context failed, so the wrapper can hand its message to the root
-#define HIPCHK_M(c, expr) do { failed = (c); HIPCHK((c), expr); failed = nullptr; } while (0)
-
-int load_table_multi_impl(bns_ctx **ctxs, int n_ctx, uint64_t n_buckets, const uint32_t *flags, const uint64_t *keys,
-                          const uint32_t *vals, int layout, bns_ctx *&failed)
-{
-    bns_ctx *root = ctxs[0];
-    const size_t fs = n_buckets < 16 ? 1 : (size_t)(n_buckets >> 4);
-    const size_t bytes[3] = {fs * 4, (size_t)n_buckets * 8, (size_t)n_buckets * 4};
-    const void *host[3] = {flags, keys, vals};
-    // 0. a db whose arrays do not fit the HBM next to its table cannot be replicated array by array: every context streams the
-    //    host buffers into its own table (bns_load_table), the first alone (its table size and minimizer window are everyone's),
-    //    the others side by side -- each over its own PCIe link
-    if (layout != BNS_LAYOUT_KHASH) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK_M(root, hipSetDevice(root->device));
-        HIPCHK_M(root, hipMemGetInfo(&free_b, &total_b));
-        if ((root->dbg & BNS_DBG_STREAM_LOAD) || bytes[0] + bytes[1] + bytes[2] + (size_t)n_buckets * 16 > free_b / 100 * 85) {
-            failed = root;
-            int rc = bns_load_table(root, n_buckets, flags, keys, vals, layout);
-            if (rc != BNS_OK) return rc;
-            failed = nullptr;
-            const u64 buckets_used = layout == BNS_LAYOUT_MINBUCKET ? root->n_mb : 0;
-            u32 lg_used = 0;
-            if (layout == BNS_LAYOUT_BUCKET) while ((1ULL << lg_used) < root->n_slots) ++lg_used;
-            const u32 span_used = layout == BNS_LAYOUT_MINBUCKET ? root->table_span : 0u;
-            const int wide_used = layout == BNS_LAYOUT_MINBUCKET ? (root->table_wide ? 1 : 0) : -1;      // the root's minimizer identity
-            std::vector<int> rcs((size_t)n_ctx, BNS_OK);
-            std::vector<std::thread> th;
-            for (int i = 1; i < n_ctx; ++i)
-                th.emplace_back([&, i] {
-                    bns_ctx *c = ctxs[i];
-                    const u64 saved = c->n_buckets_req; const u32 saved_span = c->min_span_req, saved_lg = c->slots_log2_req; const int saved_dbg = c->dbg;
-                    const int saved_wide = c->wide_req, saved_fill = c->fill_req;
-                    if (layout == BNS_LAYOUT_MINBUCKET) c->fill_req = root->group_fill ? 1 : 0;
-                    if (buckets_used) { c->n_buckets_req = buckets_used; c->slots_log2_req = 0; }
-                    if (lg_used) c->slots_log2_req = lg_used;
-                    // the root's window AND identity: one candidate left, so its trial pass (flags + keys over PCIe once more) is not
-                    // repeated and every replica is the same table
-                    if (span_used) c->min_span_req = span_used;
-                    if (span_used && wide_used >= 0) c->wide_req = wide_used;
-                    c->dbg |= root->dbg & (BNS_DBG_STREAM_LOAD | BNS_DBG_STREAM_CHUNK_MASK);
-                    rcs[(size_t)i] = bns_load_table(c, n_buckets, flags, keys, vals, layout);
-                    c->n_buckets_req = saved; c->min_span_req = saved_span; c->slots_log2_req = saved_lg; c->dbg = saved_dbg; c->wide_req = saved_wide;
-                    c->fill_req = saved_fill;
-                });
-            for (auto &t : th) t.join();
-            for (int i = 1; i < n_ctx; ++i) if (rcs[(size_t)i] != BNS_OK) { failed = ctxs[i]; return rcs[(size_t)i]; }
-            return BNS_OK;
-        }
-    }
-    // 1. device copies of the khash arrays on every context's device (owned by the contexts: free_table releases them)
-    std::vector<std::array<void *, 3>> dev((size_t)n_ctx, std::array<void *, 3>{nullptr, nullptr, nullptr});
-    for (int i = 0; i < n_ctx; ++i) {
-        bns_ctx *c = ctxs[i];
-        HIPCHK_M(c, hipSetDevice(c->device));
-        free_table(c);
-        c->own_khash = true; c->kh_nb = n_buckets;
-        HIPCHK_M(c, hipMalloc(&dev[i][0], bytes[0])); c->kflags = (const u32 *)dev[i][0];
-        HIPCHK_M(c, hipMalloc(&dev[i][1], bytes[1])); c->kkeys = (const u64 *)dev[i][1];
-        HIPCHK_M(c, hipMalloc(&dev[i][2], bytes[2])); c->kvals = (const u32 *)dev[i][2];
-    }
-    // 2. ONE host-to-device upload (root), then device-to-device replication
-    HIPCHK_M(root, hipSetDevice(root->device));
-    for (int a = 0; a < 3; ++a) HIPCHK_M(root, hipMemcpyAsync(dev[0][a], host[a], bytes[a], hipMemcpyHostToDevice, root->stream));
-    HIPCHK_M(root, hipStreamSynchronize(root->stream));
-    bool distinct = true;
-    for (int i = 0; i < n_ctx; ++i) for (int j = 0; j < i; ++j) if (ctxs[i]->device == ctxs[j]->device) distinct = false;
-    if (distinct) {
-        std::string err;
-        const int rc = rccl_broadcast(ctxs, n_ctx, dev, bytes, err);       // RCCL over xGMI
-        if (rc != BNS_OK) { failed = root; return fail(root, rc, err); }
-    } else {
-        // several contexts on ONE device (how a one-GPU box exercises the shard / stitch logic; RCCL refuses duplicate devices):
-        // plain copies
-        for (int i = 1; i < n_ctx; ++i) {
-            HIPCHK_M(ctxs[i], hipSetDevice(ctxs[i]->device));
-            for (int a = 0; a < 3; ++a) HIPCHK_M(ctxs[i], hipMemcpyAsync(dev[(size_t)i][a], dev[0][a], bytes[a], hipMemcpyDeviceToDevice, ctxs[i]->stream));
-            HIPCHK_M(ctxs[i], hipStreamSynchronize(ctxs[i]->stream));
-        }
-    }
-    // 3. every device lays out its own table; one size and one minimizer window for all (the first context's choice), whatever
-    //    each finds free
-    u64 buckets_used = 0;
-    u32 span_used = 0, lg_used = 0;
-    int wide_used = -1;
-    for (int i = 0; i < n_ctx; ++i) {
-        bns_ctx *c = ctxs[i];
-        const u64 saved = c->n_buckets_req; const u32 saved_span = c->min_span_req, saved_lg = c->slots_log2_req;
-        const int saved_wide = c->wide_req, saved_fill = c->fill_req;
-        if (i > 0 && layout == BNS_LAYOUT_MINBUCKET) c->fill_req = ctxs[0]->group_fill ? 1 : 0;
-        if (i > 0 && buckets_used) { c->n_buckets_req = buckets_used; c->slots_log2_req = 0; }
-        if (i > 0 && lg_used) c->slots_log2_req = lg_used;
-        if (i > 0 && span_used) { c->min_span_req = span_used; if (wide_used >= 0) c->wide_req = wide_used; }   // (one candidate: no second trial)
-        failed = c;
-        const int rc = bns_load_table_device(c, n_buckets, c->kflags, c->kkeys, c->kvals, layout, c->stream);
-        c->n_buckets_req = saved; c->min_span_req = saved_span; c->slots_log2_req = saved_lg; c->wide_req = saved_wide; c->fill_req = saved_fill;
-        if (rc != BNS_OK) return rc;
-        failed = nullptr;
-        if (layout == BNS_LAYOUT_KHASH) c->own_khash = true;
-        if (i == 0 && layout == BNS_LAYOUT_MINBUCKET) { buckets_used = c->n_mb; span_used = c->table_span; wide_used = c->table_wide ? 1 : 0; }
-        if (i == 0 && layout == BNS_LAYOUT_BUCKET) while ((1ULL << lg_used) < c->n_slots) ++lg_used;
-    }
-    return BNS_OK;
-}
-}  // namespace
 
 int bns_load_table_multi(bns_ctx **ctxs, int n_ctx, uint64_t n_buckets, const uint32_t *flags, const uint64_t *keys,
                          const uint32_t *vals, int layout)
@@ -1202,9 +671,9 @@ int bns_load_table_multi(bns_ctx **ctxs, int n_ctx, uint64_t n_buckets, const ui
     // (BNS_DBG_FORCE_RCCL, tests: a single context still takes the replicate path -- a one-rank communicator and real ncclBroadcast
     // calls -- so that a one-GPU box executes the RCCL code)
     if (n_ctx == 1 && !(root->dbg & BNS_DBG_FORCE_RCCL)) return bns_load_table(root, n_buckets, flags, keys, vals, layout);
-    if (n_buckets == 0 || (n_buckets & (n_buckets - 1))) return fail(root, BNS_ERR_TABLE, "n_buckets must be a power of two");
+    BNS_RC(check_n_buckets(root, n_buckets));
     bns_ctx *failed = nullptr;
-    const int rc = load_table_multi_impl(ctxs, n_ctx, n_buckets, flags, keys, vals, layout, failed);
+    const int rc = load_table_multi(ctxs, n_ctx, n_buckets, flags, keys, vals, layout, failed);
     if (rc != BNS_OK) {
         // the caller reads bns_last_error(ctxs[0]); and no context keeps half a replica (raw khash copies next to built tables)
         if (failed && failed != root) root->err = failed->err;

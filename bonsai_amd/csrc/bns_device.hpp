@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include "bns_table_plan.hpp"     // MinCand, MIN_CANDS, minimizer_len, MinSpec, MINB_CAP, MINB_MAX_CHAIN: shared with the table load's decisions
 
 namespace bns {
 
@@ -210,7 +211,7 @@ __device__ __forceinline__ u64 ovf_bucket(u64 key, u64 ovf_mask) { return (wang6
 // function of the key -- and a full bucket spills to the NEXT bucket.  Consecutive k-mers of a read share their
 // minimizer for ~(k-m+2)/2 positions, so their lookups land in the same 128-byte bucket: one DRAM fetch serves
 // several lookups instead of one.  The key->value map is unchanged.
-//   m = k for k <= 19 (no clustering: 4^m must dwarf the db or groups outgrow buckets), else k - 8, k - 11 or k - 15 (minimizer_len below);
+//   m = k for k <= 19 (no clustering: 4^m must dwarf the db or groups outgrow buckets), else k - 8, k - 11 or k - 15 (minimizer_len, bns_table_plan.hpp);
 //   m = k for spaced seeds too (consecutive spaced keys share no m-mers, so clustering buys nothing).
 //   bucket = 128 B: u64 keys[10] | u32 vals[10] | u32 n (header word, bits below) | u32 pad (the bucket's perfect-hash
 //   multiplier, see mph_slot below).  A minimizer group has up to k-m+1 keys (9 / 12 / 16 for the windows 8 / 11 / 15), a
@@ -222,7 +223,6 @@ struct alignas(16) MinBucket {
     u32 pad;
 };
 static_assert(sizeof(MinBucket) == 128, "MinBucket must be one 128-byte line");
-constexpr u32 MINB_CAP = 10;
 // Inside a bucket a key sits at slot mph_slot(mph_fold(key), S), S being a per-bucket odd multiplier found when the table
 // is loaded such that the bucket's keys land on distinct slots (a minimal perfect hash of <= 10 keys: about 2755 candidates
 // for a full bucket, tried 64 at a time).  The header word `n` holds count | occupancy << 8, `pad` holds S.  A bucket without
@@ -259,18 +259,8 @@ __device__ __forceinline__ u32 mph_candidate(u64 bucket, u32 t)
     return z | 1u;
 }
 
-// Minimizer length m (contiguous seeds): the window of a k-mer is its k - m + 1 m-mers.  A wider window means fewer minimizer runs
-// per read (density 2 / (k - m + 2): 25 bucket fetches per 150-bp read at k - m = 8, 16 at 15) but groups of up to k - m + 1
-// keys -- of which a bucket holds 10.  Which one a table uses is decided when it is loaded (bns_load_table_device): a db of every
-// k-mer fills its groups and needs the narrow window; a db of window minimizers (bonsai build -w 50: one k-mer in ten) leaves
-// them nearly empty and takes the wide one.  m never goes below `floor`: 4^m must dwarf the number of minimizer groups.  The
-// wide candidate is k - 15 rather than k - 14 because for k = 31 that is m = 16: an m-mer that fits ONE word, whose canonical
-// form is a v_min_u32 (round_minhash) -- 2 % faster than m = 17, while m = 15 (k - 16) puts unrelated k-mers into one group.
-struct MinCand { u32 span, floor; };
-constexpr MinCand MIN_CANDS[3] = {{15u, 16u}, {11u, 19u}, {8u, 19u}};        // widest first; the last one always fits (groups <= 9)
+// (MinCand, MIN_CANDS, minimizer_len: bns_table_plan.hpp -- which window a table uses is decided when it is loaded)
 constexpr int BNS_MAX_SPAN = 15;                                              // round_minhash unrolls windows of up to this + 1
-__device__ __host__ constexpr u32 minimizer_len(u32 k, MinCand c) { return k <= c.floor ? k : (k - c.span > c.floor ? k - c.span : c.floor); }
-__device__ __host__ constexpr u32 minimizer_len(u32 k) { return minimizer_len(k, MIN_CANDS[2]); }     // the narrow window
 // 32-bit mix of a folded m-mer: ONE multiply.  Only the ORDER of the values matters here (the smallest wins, and minhash_bucket
 // re-mixes the winner before it is masked), and the order is decided by the product's high bits, which every input bit
 // reaches.  (The murmur3 finaliser shape this replaced -- xorshift, multiply, xorshift -- cost four more VALU instructions per
@@ -285,13 +275,7 @@ __device__ __forceinline__ u64 canon_mmer(u64 fw, u32 m)
     const u64 r = revcomp(fw, m);
     return fw < r ? fw : r;
 }
-// Which part of a key the minimizer is taken from: m-mers of `len` consecutive key bases whose last base sits `shift` bits above
-// the key's low end.  Contiguous seeds: the whole key (len = k, shift = 0), canonical m-mers -- the m-mer sets of a k-mer and of
-// its reverse complement coincide.  Spaced seeds: the k sampled bases are not consecutive in the read except inside a run of
-// adjacent sampled positions; the LONGEST such run (16 bases for 1x15,0x15) is the only thing neighbouring spaced k-mers share
-// position by position (k-mers j and j+1 overlap in len-1 of its bases), so the minimizer is taken inside it, over plain m-mers
-// (spaced k-mers are never canonicalised, encoder.h:148-150).  len == m == k: no clustering, the one m-mer.
-struct MinSpec { u32 m, len, shift, canon, wide; };
+// (MinSpec, which part of a key the minimizer is taken from: bns_table_plan.hpp)
 // 32-bit minimizer value -> bucket in [0, n_mb): multiply, xorshift (a minimum of hashes is biased towards small values: re-mix
 // first; the product's top bits alone spread the groups worse -- 50 % more keys outside their home bucket), then a
 // multiply-high range reduction of the bit-reversed word, so that the bucket count need not be a power of two (a table can take
@@ -406,7 +390,6 @@ __device__ __forceinline__ u32 key_minhash(u64 key, u32 k, u32 m)
 // (a per-bucket perfect hash, see mph_slot): header, key, value -- three LDS reads, one compare.
 // Runs ranked 16 and above simply stay pending for the next pass.
 // aux = per-wave LDS (u32 units): [0,64) bucket list, [64, 64 + 16*32) stage (16-byte aligned).
-constexpr u32 MINB_MAX_CHAIN = 4;              // a key lives in one of its first 4 buckets (40 keys) or in the overflow table
 constexpr int MINB_STRIDE = 8;                  // uint4 per staged bucket (the loads write LDS directly, lane-linear: no padding possible)
 constexpr int MINB_LIST_U32 = 64;               // bucket list in front of the stage
 constexpr int MINB_AUX_U32 = MINB_LIST_U32 + 16 * MINB_STRIDE * 4;

@@ -484,10 +484,13 @@ def test_cli_device_list_errors(cli_files):
         assert p.returncode != 0 and b"[E]" in p.stderr, bad
 
 
+@pytest.mark.parametrize("layout", [bonsai_amd.LAYOUT_MINBUCKET, bonsai_amd.LAYOUT_BUCKET])
 @pytest.mark.parametrize("streamed", [False, True])
-def test_load_table_multi_python(gpu_ctx, CL, streamed):
+def test_load_table_multi_python(gpu_ctx, CL, streamed, layout):
     """bns_load_table_multi through ctypes: three contexts on device 0, all classify like the single-context load -- replicated
-    array by array, or (what a db too big for that gets; forced here) every context streaming the host buffers into its own table."""
+    array by array, or (what a db too big for that gets; forced here) every context streaming the host buffers into its own table.
+    The replicas follow the root's plan without a request of their own being touched: a replica that then loads the db alone,
+    no setter called, builds what a fresh context builds."""
     import ctypes as C
     a, b, c3 = bonsai_amd.Context(0), bonsai_amd.Context(0), bonsai_amd.Context(0)
     try:
@@ -498,7 +501,7 @@ def test_load_table_multi_python(gpu_ctx, CL, streamed):
         arr = (C.c_void_p * 3)(a.h, b.h, c3.h)
         f = np.ascontiguousarray(CL["db_flags"]); k = np.ascontiguousarray(CL["db_keys_arr"]); v = np.ascontiguousarray(CL["db_vals_arr"])
         rc = a.L.bns_load_table_multi(arr, 3, int(CL["db_hdr"][0]), f.ctypes.data_as(C.POINTER(C.c_uint32)), k.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                      v.ctypes.data_as(C.POINTER(C.c_uint32)), bonsai_amd.LAYOUT_MINBUCKET)
+                                      v.ctypes.data_as(C.POINTER(C.c_uint32)), layout)
         assert rc == 0, a.L.bns_last_error(a.h)
         par = flat_parent(CL["tax_child"], CL["tax_parent"])
         for c in (a, b, c3):
@@ -508,6 +511,15 @@ def test_load_table_multi_python(gpu_ctx, CL, streamed):
         assert a.table_stats()["main_bytes"] == b.table_stats()["main_bytes"] == c3.table_stats()["main_bytes"]
         shape = lambda c: {k: v for k, v in c.table_geometry().items() if k in ("buckets", "m", "identity_bits", "span", "group_fill")}   # noqa: E731
         assert shape(a) == shape(b) == shape(c3)             # one size, one minimizer window, one identity for all
+        fresh = bonsai_amd.Context(0)
+        try:
+            fresh.set_encoder(int(CL["k"]), None, canonicalize=True)
+            for c in (b, fresh):
+                c.load_table(int(CL["db_hdr"][0]), f, k, v, layout=layout)
+            assert shape(b) == shape(fresh) and b.table_stats()["main_bytes"] == fresh.table_stats()["main_bytes"]
+            assert b.table_stats()["n_keys"] == fresh.table_stats()["n_keys"] == int(CL["db_keys"].size)
+        finally:
+            fresh.close()
     finally:
         a.close(); b.close(); c3.close()
 
