@@ -10,6 +10,10 @@ OK = 0
 LAYOUT_KHASH, LAYOUT_BUCKET, LAYOUT_MINBUCKET = 0, 1, 2
 SCORE_LEX, SCORE_ENTROPY_PATH, SCORE_ENTROPY_STRING = 0, 1, 2
 TAX_ABSENT = 0xFFFFFFFF
+# the window session's geometry (csrc/bns_windows.hpp: WIN_TILE, WIN_FAST_TAXA): window starts per wavefront of the vote pass, and the
+# distinct taxa of one window its register counter holds before it continues in memory
+WINDOWS_TILE, WINDOWS_FAST_TAXA = 256, 64
+WINDOWS_LDS_LIST = 11264            # (WIN_LDS_LIST_MAX) positions of tile + halo up to which the vote pass keeps its hit list in LDS
 
 u8p = C.POINTER(C.c_uint8)
 u16p = C.POINTER(C.c_uint16)
@@ -129,6 +133,11 @@ def load():
         "bns_build_export": (C.c_int, [vp, u32p, u64p, u32p]),
         "bns_build_stats": (C.c_int, [vp, u64p]),
         "bns_build_end": (C.c_int, [vp]),
+        "bns_windows_begin": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
+        "bns_windows_add": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp, vp]),
+        "bns_windows_read": (C.c_int, [vp, u32p, u32p, u64p, C.c_uint64, u64p, u64p, C.c_int]),
+        "bns_windows_timing": (C.c_int, [vp, C.POINTER(C.c_double), u64p]),
+        "bns_windows_end": (C.c_int, [vp]),
         "bns_set_timing": (C.c_int, [vp, C.c_int]),
         "bns_last_kernel_ms": (C.c_float, [vp]),
         "bns_timing_summary": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),

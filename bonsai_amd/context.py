@@ -564,6 +564,62 @@ class Context:
     def build_end(self):
         self._chk(self.L.bns_build_end(self.h), "bns_build_end")
 
+    # ---- window session: every window of window_len bases of every sequence, called as classify calls a read
+    def windows_begin(self, window_len, pair_cap=1 << 20):
+        """opens a session; needs table, encoder and taxonomy, and no confidence threshold"""
+        self._chk(self.L.bns_windows_begin(self.h, int(window_len), int(pair_cap)), "bns_windows_begin")
+
+    def windows_add(self, d_bases, d_offsets, n_seqs, total_bases, d_taxid, d_taxon=None, stream=None):
+        """one batch of whole sequences (device arrays, as build_add takes them).  d_taxon (total_bases uint32, or None): the call of
+        the window that starts at each base, 0xFFFFFFFF where none does.  Queued on the stream: sync() before reading d_taxon."""
+        self._chk(self.L.bns_windows_add(self.h, d_bases, d_offsets, n_seqs, total_bases, d_taxid, d_taxon, stream), "bns_windows_add")
+
+    def windows(self, reset=False):
+        """bns_windows_read -> (seq_taxid uint32[n], called uint32[n], count uint64[n], n_dropped), ascending by (seq_taxid, called)"""
+        n = C.c_uint64(); dropped = C.c_uint64()
+        self._chk(self.L.bns_windows_read(self.h, None, None, None, 0, C.byref(n), C.byref(dropped), 0), "bns_windows_read")
+        seq = np.zeros(n.value, dtype=np.uint32); called = np.zeros(n.value, dtype=np.uint32); count = np.zeros(n.value, dtype=np.uint64)
+        self._chk(self.L.bns_windows_read(self.h, _p(seq, u32p), _p(called, u32p), _p(count, u64p), n.value, C.byref(n), C.byref(dropped),
+                                          int(bool(reset))), "bns_windows_read")
+        return seq, called, count, int(dropped.value)
+
+    def windows_timing(self):
+        """bns_windows_timing -> ({"pack_ms", "lookup_ms", "vote_ms"} summed over the adds since the last call, n_adds); the session
+        must have begun with set_timing(True)"""
+        ms = (C.c_double * 3)(); n = C.c_uint64()
+        self._chk(self.L.bns_windows_timing(self.h, ms, C.byref(n)), "bns_windows_timing")
+        return {"pack_ms": ms[0], "lookup_ms": ms[1], "vote_ms": ms[2]}, int(n.value)
+
+    def windows_end(self):
+        self._chk(self.L.bns_windows_end(self.h), "bns_windows_end")
+
+    def classify_windows(self, bases, offsets, taxids, window_len, pair_cap=1 << 20):
+        """host arrays through one session of its own -> (d_taxon image uint32[total_bases], (seq_taxid, called, count, n_dropped))"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        taxids = np.ascontiguousarray(taxids, dtype=np.uint32)
+        n_seqs, total = offsets.size - 1, int(offsets[-1])
+        if taxids.size != n_seqs or bases.size < total:
+            raise ValueError("one taxid per sequence, and the bases the offsets name")
+        taxon = np.zeros(total, dtype=np.uint32)
+        bufs = []
+        self.windows_begin(window_len, pair_cap)
+        try:
+            for a in (bases[:total], offsets, taxids):
+                bufs.append(self.dev_alloc(a.nbytes + 8))           # (the bases are read up to 8 bytes past the end)
+                if a.nbytes:
+                    self.dev_upload(bufs[-1], a)
+            bufs.append(self.dev_alloc(taxon.nbytes + 8))
+            self.windows_add(bufs[0], bufs[1], n_seqs, total, bufs[2], bufs[3])
+            self.sync()
+            if total:
+                self.dev_download(bufs[3], taxon)
+            return taxon, self.windows()
+        finally:
+            self.windows_end()
+            for p in bufs:
+                self.dev_free(p)
+
     def set_timing(self, on=True):
         self._chk(self.L.bns_set_timing(self.h, int(on)), "bns_set_timing")
 

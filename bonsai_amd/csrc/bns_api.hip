@@ -73,12 +73,14 @@ struct ClassifyForm {
 
 struct bns_text_work;                                     // bns_ingest.hip: workspace of bns_classify_text
 namespace bns { struct BuildSession; }                    // bns_build.hpp: the table a build session grows
+namespace bns { struct WindowSession; }                   // bns_windows.hpp: window length, pair table and workspace of a window session
 void text_work_free(struct bns_ctx *ctx);
 
 struct bns_ctx {
     int device = 0;
     bns_text_work *text_work = nullptr;
     bns::BuildSession *build = nullptr;                  // bns_build_begin .. bns_build_end; while it is open the encoder, the window and the taxonomy stay
+    bns::WindowSession *windows = nullptr;               // bns_windows_begin .. bns_windows_end
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;                   // host-buffer entry points: uploads of the next slice while one is classified
     hipStream_t back_stream = nullptr;                   // ... and the copy-back of a classified slice's results, behind neither of the two
@@ -299,6 +301,7 @@ int ready(bns_ctx *ctx, bool need_table, bool need_tax)
 
 #include "bns_build.hpp"
 #include "bns_table_load.hpp"
+#include "bns_windows.hpp"
 
 namespace {
 // Every classify_kernel / classify_overflow_kernel launch goes through these two: the instantiation launched and the one
@@ -372,7 +375,7 @@ bool launch_fixed_k(ClassifyForm &f, const ClassifyParams &p, unsigned grid, hip
 
 extern "C" {
 
-int bns_version(void) { return 109; }
+int bns_version(void) { return 110; }
 
 int bns_device_pci_bus_id(int device, char *out, int cap)
 {
@@ -505,6 +508,7 @@ void bns_destroy(bns_ctx *ctx)
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     free_table(ctx);
     build_free(ctx);
+    windows_free(ctx);
     text_work_free(ctx);
     if (ctx->nodes) (void)hipFree(ctx->nodes);
     DevBuf *bufs[] = {&ctx->words, &ctx->nmask, &ctx->ovf_list, &ctx->scratch, &ctx->small, &ctx->records, &ctx->st_bases, &ctx->st_offsets,
@@ -1998,6 +2002,34 @@ int bns_build_end(bns_ctx *ctx)
 {
     if (!ctx) return BNS_ERR_ARG;
     build_free(ctx);
+    return BNS_OK;
+}
+
+int bns_windows_begin(bns_ctx *ctx, uint32_t window_len, uint32_t pair_cap) { return windows_begin(ctx, window_len, pair_cap); }
+int bns_windows_add(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bases,
+                    const uint32_t *d_taxid, uint32_t *d_taxon, void *stream)
+{
+    return windows_add(ctx, d_bases, d_offsets, n_seqs, total_bases, d_taxid, d_taxon, stream);
+}
+int bns_windows_read(bns_ctx *ctx, uint32_t *seq_taxid, uint32_t *called, uint64_t *count, uint64_t cap, uint64_t *n_pairs,
+                     uint64_t *n_dropped, int reset)
+{
+    return windows_read(ctx, seq_taxid, called, count, cap, n_pairs, n_dropped, reset);
+}
+int bns_windows_timing(bns_ctx *ctx, double *ms3, uint64_t *n_adds)
+{
+    if (!ctx || !ms3) return BNS_ERR_ARG;
+    if (!ctx->windows) return fail(ctx, BNS_ERR_STATE, "bns_windows_timing: no window session is open (bns_windows_begin)");
+    if (!ctx->windows->ev[0]) return fail(ctx, BNS_ERR_STATE, "bns_windows_timing: timing was off when the session began (bns_set_timing)");
+    for (int i = 0; i < 3; ++i) { ms3[i] = ctx->windows->ms[i]; ctx->windows->ms[i] = 0; }
+    if (n_adds) *n_adds = ctx->windows->n_adds;
+    ctx->windows->n_adds = 0;
+    return BNS_OK;
+}
+int bns_windows_end(bns_ctx *ctx)
+{
+    if (!ctx) return BNS_ERR_ARG;
+    windows_free(ctx);
     return BNS_OK;
 }
 

@@ -450,6 +450,23 @@ struct BuildOptions {
 Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &parent, const char *seq2tax_path,
                  const BuildOptions &opt);
 
+// ---- `bonsai distrib` (bns_distrib.cpp): how THIS db calls every read-length window of every genome ----------
+// The text of the file (Bracken's database<L>mers.kmer_distrib, as recalled) from the pairs bns_windows_read returns, ascending by
+// (seq_taxid, called):
+//   mapped_taxid\tgenome_taxids:kmers_mapped:total_genome_kmers
+//   <called taxid>\t<g>:<windows of g called here>:<all windows of g> <g'>:...:... ...
+// lines ascending by called taxid, entries ascending by genome taxid and one space apart, decimal numbers, '\n' line ends.  Called
+// taxid 0 gets no line; "all windows of g" does count the windows called 0.  Equal pairs that appear twice are added up.
+std::string format_distrib(const u32 *seq_taxid, const u32 *called, const u64 *count, u64 n_pairs);
+struct DistribOptions {
+    unsigned window_len = 150;      // -l
+    u32 pair_cap = 1u << 20;        // -P: slots of the session's pair table
+    u64 batch_bases = 1ULL << 30;   // -B: as BuildOptions::batch_bases (windows never span sequences: the output does not depend on it)
+};
+// The genome files (taxids by get_taxid, as `bonsai build` maps them) through one window session on the classifier's first context:
+// this thread uploads and adds batch n while a second one reads batch n + 1.  Pairs that found no slot are an error.
+void write_distrib(ClassifierGeneric &c, const std::vector<std::string> &paths, const char *seq2tax_path, const DistribOptions &opt, std::FILE *out);
+
 // ---- Encoder API surface (encoder.h:415-442, 448-530) -----------------------------------------------------
 // Synchronous, in sequence order, on the calling thread -- like the reference; the k-mers come from the GPU encoder.
 // Sequences of a FILE are read by SeqReader (kseq_read's records: klib/kseq.h:177-225) and handed to the device in batches of

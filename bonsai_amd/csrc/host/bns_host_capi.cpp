@@ -273,6 +273,29 @@ int bnsh_format_report(const uint64_t *direct, const uint64_t *clade, uint32_t n
     });
 }
 
+// format_distrib: the pairs of bns_windows_read -> the text of `bonsai distrib`, malloc'd in *out (*out_bytes bytes, NUL-terminated)
+int bnsh_format_distrib(const uint32_t *seq_taxid, const uint32_t *called, const uint64_t *count, uint64_t n_pairs, char **out, uint64_t *out_bytes)
+{
+    return guard([&] {
+        const std::string s = format_distrib(seq_taxid, called, count, n_pairs);
+        *out = static_cast<char *>(std::malloc(s.size() + 1));
+        std::memcpy(*out, s.c_str(), s.size() + 1);
+        *out_bytes = s.size();
+    });
+}
+
+// ... and written to a file
+int bnsh_write_distrib(const uint32_t *seq_taxid, const uint32_t *called, const uint64_t *count, uint64_t n_pairs, const char *path)
+{
+    return guard([&] {
+        const std::string s = format_distrib(seq_taxid, called, count, n_pairs);
+        std::FILE *fp = std::fopen(path, "w");
+        if (!fp) throw Error(std::string("Could not open ") + path);
+        const bool ok = std::fwrite(s.data(), 1, s.size(), fp) == s.size();
+        if (std::fclose(fp) != 0 || !ok) throw Error(std::string("Could not write ") + path);
+    });
+}
+
 // hll_estimate of 4096 one-byte registers
 uint64_t bnsh_hll_estimate(const uint8_t *reg) { return reg ? hll_estimate(reg) : 0; }
 

@@ -176,6 +176,68 @@ inline char *kraken_line_raw(char *w, const HitRuns &runs, tax_t taxon, u32 ambi
     return w;
 }
 
+// ---- genome files in batches of whole sequences (bns_host.cpp): what `bonsai build` (lca_map) and `bonsai distrib` (bns_distrib.cpp) read
+// device memory that is re-used from one batch to the next and only re-allocated for a larger one
+struct GrowMem {
+    bns_ctx *ctx; void *p = nullptr; size_t cap = 0;
+    explicit GrowMem(bns_ctx *c) : ctx(c) {}
+    ~GrowMem() { release(); }
+    void release() { if (p) bns_dev_free(ctx, p); p = nullptr; cap = 0; }
+    void ensure(size_t n)
+    {
+        if (n <= cap) return;
+        release();
+        chk(ctx, bns_dev_alloc(ctx, n, &p), "bns_dev_alloc");
+        cap = n;
+    }
+    GrowMem(const GrowMem &) = delete; GrowMem &operator=(const GrowMem &) = delete;
+};
+
+// whole sequences of at most batch_bases bases (one sequence longer than that is a batch of its own)
+struct BuildBatch {
+    std::string bases;
+    std::vector<u64> offsets{0};
+    std::vector<u32> taxids;
+    void clear() { bases.clear(); offsets.assign(1, 0); taxids.clear(); }
+};
+
+// one batch waits while the device works on the one before it and the reader fills the next
+class BatchQueue {
+public:
+    void push(BuildBatch &&b)
+    {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return !full_ || abandoned_; });
+        if (abandoned_) return;
+        slot_ = std::move(b); full_ = true;
+        cv_.notify_all();
+    }
+    bool abandoned() { std::lock_guard<std::mutex> lk(mu_); return abandoned_; }
+    void finish(std::exception_ptr e) { std::lock_guard<std::mutex> lk(mu_); done_ = true; err_ = e; cv_.notify_all(); }
+    bool pop(BuildBatch &out)
+    {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return full_ || done_; });
+        if (!full_) return false;
+        out = std::move(slot_); full_ = false;
+        cv_.notify_all();
+        return true;
+    }
+    void abandon() { std::lock_guard<std::mutex> lk(mu_); abandoned_ = true; cv_.notify_all(); }   // the consumer left early
+    void rethrow() { std::lock_guard<std::mutex> lk(mu_); if (err_) std::rethrow_exception(err_); }
+private:
+    std::mutex mu_;
+    std::condition_variable cv_;
+    BuildBatch slot_;
+    bool full_ = false, done_ = false, abandoned_ = false;
+    std::exception_ptr err_;
+};
+
+// every FASTA record of every genome file is one sequence under the genome's taxid (get_taxid); the reader thread's body: batches go to q,
+// then q.finish() with what it threw, if anything
+void read_build_batches(const std::vector<std::string> &paths, const std::vector<std::pair<std::string, tax_t>> &names, u64 batch_bases,
+                        BatchQueue &q);
+
 // ---- a chunk of host-parsed records on one device (bns_host.cpp): pack into the result's page-locked buffers, then the GPU call
 void pack_chunk(ClassifierGeneric &c, bns_ctx *ctx, const bseq1_t *bs, unsigned n, int is_paired, ChunkResult &r, unsigned copy_threads);
 void call_chunk(bns_ctx *ctx, ChunkResult &r);

@@ -359,6 +359,80 @@ int inspect_main(int argc, char *argv[])
     return EXIT_SUCCESS;
 }
 
+// `bonsai distrib`: for every genome, how the db calls each of its windows of read length (what an abundance estimator after Bracken
+// needs per db and read length), classified on the GPU with one table lookup per k-mer
+int distrib_main(int argc, char *argv[])
+{
+    auto distrib_usage = [&]() {
+        std::fprintf(stderr, "Usage: %s distrib [-l window length: 150] [-g device] [-L minbucket|bucket|khash] [-C: do not canonicalize]\n"
+                             "       [-B bases per batch] [-P pairs: slots of the (genome taxid, called taxid) table: 1048576] -M seq2tax [-F paths file]\n"
+                             "       [-o file] <dbpath> <tax_path> <genome paths...>\n"
+                             "Writes 'mapped_taxid<TAB>genome_taxids:kmers_mapped:total_genome_kmers', then a line per called taxid: the genomes with\n"
+                             "windows called there, as <genome taxid>:<windows called here>:<all windows of the genome>.\n", argv[0]);
+        return EXIT_FAILURE;
+    };
+    int co, device = 0, layout = BNS_LAYOUT_MINBUCKET;
+    bool canon = true;
+    bns::DistribOptions opt;
+    std::string seq2taxpath, paths_file;
+    const char *out_path = nullptr;
+    while ((co = getopt(argc, argv, "l:g:L:CB:P:M:F:o:h?")) >= 0) {
+        switch (co) {
+            case 'l': { const long long v = std::atoll(optarg); if (v < 1 || v > 0xFFFFFFFFLL) return distrib_usage(); opt.window_len = (unsigned)v; } break;
+            case 'g': device = std::atoi(optarg); break;
+            case 'C': canon = false; break;
+            case 'B': { const long long v = std::atoll(optarg); if (v < 1) return distrib_usage(); opt.batch_bases = (bns::u64)v; } break;
+            case 'P': { const long long v = std::atoll(optarg); if (v < 1 || v > (1LL << 31)) return distrib_usage(); opt.pair_cap = (bns::u32)v; } break;
+            case 'M': seq2taxpath = optarg; break;
+            case 'F': paths_file = optarg; break;
+            case 'o': out_path = optarg; break;
+            case 'L':
+                if (std::strcmp(optarg, "khash") == 0) layout = BNS_LAYOUT_KHASH;
+                else if (std::strcmp(optarg, "bucket") == 0) layout = BNS_LAYOUT_BUCKET;
+                else if (std::strcmp(optarg, "minbucket") == 0) layout = BNS_LAYOUT_MINBUCKET;
+                else return distrib_usage();
+                break;
+            default: return distrib_usage();
+        }
+    }
+    if (argc - optind < 2) return distrib_usage();
+    std::vector<std::string> inpaths;
+    if (!paths_file.empty()) {
+        std::FILE *fp = std::fopen(paths_file.c_str(), "r");
+        if (!fp) { std::fprintf(stderr, "[E] Could not open %s\n", paths_file.c_str()); return EXIT_FAILURE; }
+        char buf[4096];
+        while (std::fgets(buf, sizeof(buf), fp)) {
+            std::string l(buf);
+            while (!l.empty() && (l.back() == '\n' || l.back() == '\r')) l.pop_back();
+            if (!l.empty()) inpaths.push_back(l);
+        }
+        std::fclose(fp);
+    } else {
+        for (int i = optind + 2; i < argc; ++i) inpaths.emplace_back(argv[i]);
+    }
+    std::FILE *ofp = nullptr;
+    try {
+        if (inpaths.empty()) throw bns::Error("Need genome files from command line or file. See usage.");
+        if (seq2taxpath.empty()) throw bns::Error("seq2taxpath required: the genomes' taxids come from it. [See -M option.]");
+        bns::Database &db = *new bns::Database(argv[optind]);                // (never destroyed, as in classify)
+        unsigned comb = db.k_;
+        for (bns::u16 g : db.s_) comb += g;
+        if (opt.window_len < comb)
+            throw bns::Error("-l " + std::to_string(opt.window_len) + ": a window is at least as long as the db's seed (" + std::to_string(comb) + " bases)");
+        const std::vector<bns::u32> taxmap = bns::build_parent_map(argv[optind + 1]);
+        bns::ClassifierGeneric &c = *new bns::ClassifierGeneric(db, taxmap, std::vector<int>{device}, 1, 0, 0, 1, canon, layout);
+        ofp = out_path ? std::fopen(out_path, "w") : stdout;
+        if (!ofp) throw bns::Error("Could not open output file");
+        bns::write_distrib(c, inpaths, seq2taxpath.c_str(), opt, ofp);
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "[E] %s\n", e.what());
+        if (ofp && ofp != stdout) { std::fclose(ofp); std::remove(out_path); }
+        return EXIT_FAILURE;
+    }
+    if (ofp != stdout && std::fclose(ofp) != 0) { std::fprintf(stderr, "[E] Could not write the window distribution\n"); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
 // `bonsai build` (bin/bonsai.cpp:169-281, lex / entropy modes): db construction on the GPU.
 void build_usage(const char *exe)
 {
@@ -497,11 +571,13 @@ int main(int argc, char *argv[])
         return leave(build_main(argc - 1, argv + 1));                // bin/bonsai.cpp:527-529 aliases
     if (argc > 1 && std::strcmp(argv[1], "pack") == 0) return leave(pack_main(argc - 1, argv + 1));
     if (argc > 1 && std::strcmp(argv[1], "inspect") == 0) return leave(inspect_main(argc - 1, argv + 1));
-    std::fprintf(stderr, "Usage: %s <classify|build|pack|inspect> ...\n"
+    if (argc > 1 && std::strcmp(argv[1], "distrib") == 0) return leave(distrib_main(argc - 1, argv + 1));
+    std::fprintf(stderr, "Usage: %s <classify|build|pack|inspect|distrib> ...\n"
                          "  classify <opts> <dbpath> <tax_path> <inr1.fq> [<inr2.fq>]\n"
                          "  build    <opts> <out.path> <ignored> <genome paths>\n"
                          "  pack     -o <out.bnsp> <in1.fq> [<in2.fq>]      (reads -> 2-bit container for classify)\n"
                          "  inspect  <opts> <dbpath> <tax_path>             (the db's keys per taxon, in the layout of classify -R)\n"
+                         "  distrib  <opts> <dbpath> <tax_path> <genome paths>  (how the db calls every read-length window of every genome)\n"
                          "Other reference subcommands (prebuild, hist, metatree) are out of scope (DESIGN.md).\n", argv[0]);
     return EXIT_FAILURE;
 }

@@ -63,6 +63,10 @@ def lib():
         L.bnsh_format_report_coverage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_char_p,
                                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p),
                                                   C.POINTER(C.c_uint64)]
+        L.bnsh_format_distrib.restype = C.c_int
+        L.bnsh_format_distrib.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.bnsh_write_distrib.restype = C.c_int
+        L.bnsh_write_distrib.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p]
         _lib = L
     return _lib
 
@@ -101,6 +105,22 @@ def hll_estimate(registers):
     if registers.size != 4096:
         raise ValueError("a sketch has 4096 registers")
     return int(lib().bnsh_hll_estimate(registers.ctypes.data))
+
+
+def format_distrib(seq_taxid, called, count, path=None):
+    """the `bonsai distrib` text (bns::format_distrib) from the pairs Context.windows() returns: a header, then a line per called
+    taxid != 0 with <genome taxid>:<windows called here>:<all windows of the genome> entries.  With path the text is written there
+    (and returned all the same)."""
+    s = np.ascontiguousarray(seq_taxid, dtype=np.uint32); t = np.ascontiguousarray(called, dtype=np.uint32)
+    n = np.ascontiguousarray(count, dtype=np.uint64)
+    if not s.size == t.size == n.size:
+        raise ValueError("seq_taxid, called and count are one entry per pair")
+    if path is not None and lib().bnsh_write_distrib(s.ctypes.data, t.ctypes.data, n.ctypes.data, s.size, str(path).encode()) != 0:
+        raise HostIOError(lib().bnsh_last_error().decode())
+    out, ob = C.c_void_p(), C.c_uint64()
+    if lib().bnsh_format_distrib(s.ctypes.data, t.ctypes.data, n.ctypes.data, s.size, C.byref(out), C.byref(ob)) != 0:
+        raise HostIOError(lib().bnsh_last_error().decode())
+    return _take_blob(out, ob.value).decode()
 
 
 def format_report(direct, clade, parent, ranks=None, names=None, sketch_bins=None, sketch_registers=None, db_keys=None):

@@ -437,6 +437,45 @@ int bns_build_export(bns_ctx *ctx, uint32_t *flags, uint64_t *keys, uint32_t *va
 int bns_build_stats(const bns_ctx *ctx, uint64_t *out6);
 int bns_build_end(bns_ctx *ctx);
 
+/* ---- window session (version 110): every window of L bases of every sequence, called as a read (`bonsai distrib`) -------------
+ * With L = window_len, sequence s of n bases has max(0, n - L + 1) windows; window p is its bases [p, p + L).  The CALL of a window is
+ * the taxon bns_classify_batch returns for that substring as a single unpaired read on this context -- its table layout, encoder
+ * (canonical or not; a spaced seed without spaced_intended emits nothing, so every call is 0), taxonomy, and classify's handling of N,
+ * other bytes and lower case -- bit for bit.  Each k-mer of a batch is looked up once, not once per window that holds it.
+ *   bns_windows_begin  needs a loaded table, encoder and taxonomy, and no confidence threshold (bns_set_confidence), else
+ *                      BNS_ERR_STATE; a second begin: BNS_ERR_STATE.  window_len must be at least the seed's span c, and
+ *                      window_len - c + 1 <= 65535 (the vote's counts are 16 bits wide, as the reference's: inside the bound none can
+ *                      wrap), else BNS_ERR_ARG.  pair_cap slots of the pair table, rounded up to a power of two; 0: BNS_ERR_ARG.  The
+ *                      table starts empty.
+ *   bns_windows_add    one batch of whole sequences, bns_build_add's inputs (device arrays; n_seqs + 1 offsets, the bases readable
+ *                      8 bytes past the end, a taxid per sequence).  d_taxon may be NULL; else it has total_bases entries: the call of
+ *                      window p of sequence s goes to d_taxon[offsets[s] + p] (the convention of `hits`), and every base that starts no
+ *                      window -- the last L - 1 of a sequence, all of a sequence shorter than L -- gets 0xFFFFFFFF.  Every window adds 1
+ *                      to the count of the pair (d_taxid[s], call), calls of 0 included.  A pair that finds no free slot adds to
+ *                      n_dropped instead: the pairs in the table are always exact, the sum of their counts plus n_dropped is the
+ *                      number of windows added, and which pairs get in when the table is full is not defined.  (The pair
+ *                      (0xFFFFFFFF, 0xFFFFFFFF) -- BNS_TAX_ABSENT as a sequence's taxid -- is always dropped.)  The work is queued
+ *                      on `stream` (NULL: the context's) and the call returns: the batch and d_taxon are the device's until that
+ *                      stream has been waited for.  A confidence threshold set since begin: BNS_ERR_STATE.
+ *   bns_windows_read   waits for the device, then the pairs ascending by (seq_taxid, called); any of the three arrays may be NULL.
+ *                      cap < *n_pairs: BNS_ERR_ARG with *n_pairs set (bns_sketch_read's rule).  reset empties the table and zeroes
+ *                      n_dropped.
+ *   bns_windows_timing a session begun while bns_set_timing is on brackets the three stages of every add with events -- packing the
+ *                      bases and clearing the outputs | the lookup pass | the vote pass -- and WAITS for the batch at the end of the
+ *                      add; ms3 receives the milliseconds summed over the *n_adds adds since the last call.  A session begun with
+ *                      timing off: BNS_ERR_STATE.
+ *   bns_windows_end    frees the session; legal at any point.  bns_destroy ends an open session.
+ * add, read or timing without a session: BNS_ERR_STATE.  bns_set_min_base_quality does not apply (sequences carry no quality); the
+ * bns_tally_enable tally and the sketches are not touched (as with bns_resolve_batch).  Without a session nothing is allocated or
+ * launched. */
+int bns_windows_begin(bns_ctx *ctx, uint32_t window_len, uint32_t pair_cap);
+int bns_windows_add(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bases,
+                    const uint32_t *d_taxid, uint32_t *d_taxon, void *stream);
+int bns_windows_read(bns_ctx *ctx, uint32_t *seq_taxid, uint32_t *called, uint64_t *count, uint64_t cap, uint64_t *n_pairs,
+                     uint64_t *n_dropped, int reset);
+int bns_windows_timing(bns_ctx *ctx, double *ms3, uint64_t *n_adds);
+int bns_windows_end(bns_ctx *ctx);
+
 /* ---- instrumentation -------------------------------------------------------------------------- */
 /* HIP-event timing of the dominant kernel (classify_kernel / probe_kernel), recorded on the stream the
  * kernel is launched on.  bns_set_timing(ctx, 1) enables and clears.  bns_last_kernel_ms: most recent
