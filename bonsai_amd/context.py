@@ -158,7 +158,7 @@ class Context:
         return self.L.bns_table_warning(self.h).decode()
 
     def debug_set(self, bits):
-        """test / profiling switches (BNS_DBG_* in bns_api.hip and bns_table_plan.hpp); not part of the public header"""
+        """test / profiling switches (BNS_DBG_* in bns_api.hip, bns_table_plan.hpp and bns_classify_plan.hpp); not part of the public header"""
         self._chk(self.L.bns_debug_set(self.h, bits), "bns_debug_set")
 
     def debug_claim_waves(self, waves):

@@ -1,4 +1,5 @@
-// bns_api.hip -- the C ABI of include/bonsai_amd.h: context, HBM residency, kernel launches.
+// bns_api.hip -- the C ABI of include/bonsai_amd.h: context, HBM residency, and the entry points; classify, table load, build and
+// window sessions are thin forwards into bns_classify.hpp, bns_table_load.hpp, bns_build.hpp and bns_windows.hpp.
 // Single translation unit for the device library: the kernels are included so their templates are visible.
 #include "../../include/bonsai_amd.h"
 #include "bns_kernels.hip"
@@ -50,11 +51,9 @@ static_assert(sizeof(SmallLayout) <= SMALL_BYTES, "ctx->small is allocated with 
 static_assert(offsetof(SmallLayout, load_cnt) >= SMALL_CLASSIFY_ZERO, "classify's memset must not reach the other entry points' words");
 
 // bns_debug_set bits (tests and profiling; 0 in production); the table load's -- 0x10, 0x20, 0x100, 0x200, 0x1000, bits 16-20 and
-// 24-28 -- are in bns_table_plan.hpp
+// 24-28 -- are in bns_table_plan.hpp, the classify launch's -- 0x2000, 0x8000 -- in bns_classify_plan.hpp
 constexpr int BNS_DBG_PEXT_OFF = 0x400;             // spaced seeds: gather run by run instead of through the compress network
 constexpr int BNS_DBG_FORCE_RCCL = 0x800;           // bns_load_table_multi with ONE context still broadcasts through RCCL (1-rank communicator)
-constexpr int BNS_DBG_OVC_OFF = 0x2000;             // classify: never the cooperative overflow lookup (A/B of the two forms)
-constexpr int BNS_DBG_OVC_ON = 0x8000;              // classify: always the cooperative overflow lookup
 constexpr int BNS_DBG_BATCH_TINY = 0x40;            // bns_classify_text: a classify launch per >= 64 records (many batches on small texts)
 constexpr int BNS_DBG_INSPECT_TINY = 0x8;           // bns_table_tally: grids of at most 4 workgroups that flush their LDS counters every 3 rounds (tests: many rounds, a full LDS hash and the mid-walk flush on small tables; same counts)
 constexpr int BNS_DBG_INSPECT_WHOLE = 0x80;         // bns_table_tally: fetch whole 128-byte buckets instead of their upper halves (A/B; same counts)
@@ -202,62 +201,6 @@ inline unsigned grid_for(const bns_ctx *ctx, u64 items, unsigned per_block, unsi
     return (unsigned)std::max<u64>(1, std::min(need, cap));
 }
 
-void fill_params(const bns_ctx *ctx, ClassifyParams &p)
-{
-    std::memset(&p, 0, sizeof(p));
-    p.words = (const u64 *)ctx->words.p;
-    p.nmask = (const u32 *)ctx->nmask.p;
-    p.slots = ctx->layout == BNS_LAYOUT_MINBUCKET ? ctx->ovf_slots : ctx->slots;
-    p.ovf_mask = ctx->n_ovf_slots ? ctx->n_ovf_slots / 4 - 1 : 0;
-    p.minb = reinterpret_cast<const MinBucket *>(ctx->slots);
-    p.bucket_mask = (ctx->n_slots && ctx->layout == BNS_LAYOUT_BUCKET) ? ctx->n_slots / 4 - 1 : 0;
-    p.n_mb = ctx->layout == BNS_LAYOUT_MINBUCKET ? ctx->n_mb : 0u;
-    p.min_wide = ctx->table_wide ? 1u : 0u;
-    p.kflags = ctx->kflags; p.kkeys = ctx->kkeys; p.kvals = ctx->kvals; p.kh_nb = ctx->kh_nb;
-    p.nodes = ctx->nodes; p.n_nodes = ctx->n_nodes;
-    p.k = ctx->k; p.c = ctx->c; p.canon = ctx->canon ? 1 : 0; p.dbg = ctx->dbg;
-    std::memcpy(p.pos, ctx->pos, sizeof(p.pos));
-    p.n_runs = ctx->n_runs; p.sample_mask = ctx->sample_mask; p.m = ctx->table_m ? ctx->table_m : ctx->k;
-    p.min_len = ctx->table_m ? ctx->table_len : ctx->k; p.min_shift = ctx->table_m ? ctx->table_shift : 0; p.min_canon = ctx->table_m ? ctx->table_canon : 1;
-    p.w = ctx->win > ctx->c ? ctx->win : ctx->c; p.score = ctx->score;
-    if (ctx->score == BNS_SCORE_ENTROPY_STRING) {                        // CircusEnt::value() terms, entropy.h:46-47 (qszinv_ = 1./qsz)
-        const double qi = 1. / (double)ctx->k;
-        for (u32 n = 1; n <= ctx->k && n <= 32; ++n) p.ent_tbl[n] = (double)n * qi * std::log((double)n * qi);
-    }
-    std::memcpy(p.run_start, ctx->run_start, sizeof(p.run_start)); std::memcpy(p.run_len, ctx->run_len, sizeof(p.run_len));
-    p.pext_on = (ctx->dbg & BNS_DBG_PEXT_OFF) ? 0 : ctx->pext_on; p.pext_n1 = ctx->pext_n1;
-    std::memcpy(p.pext_steps, ctx->pext_steps, sizeof(p.pext_steps)); std::memcpy(p.pext_mask, ctx->pext_mask, sizeof(p.pext_mask));
-    std::memcpy(p.pext_top, ctx->pext_top, sizeof(p.pext_top));
-    std::memcpy(p.pext_mv, ctx->pext_mv, sizeof(p.pext_mv));
-}
-
-// pack ASCII reads (device) into ctx->words / ctx->nmask
-int pack_reads(bns_ctx *ctx, const char *d_bases, const u64 *d_offsets, u64 n_reads, u64 total_bases, hipStream_t st)
-{
-    const size_t n_words = (size_t)(total_bases >> 5) + n_reads + 2;
-    int rc;
-    if ((rc = ensure(ctx, ctx->words, n_words * 8)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->nmask, n_words * 4)) != BNS_OK) return rc;
-    if (n_reads == 0) return BNS_OK;
-    hipLaunchKernelGGL(pack_kernel, dim3(grid_for(ctx, n_reads, 4)), dim3(256), 0, st, (const u8 *)d_bases, d_offsets,
-                       n_reads, (u64 *)ctx->words.p, (u32 *)ctx->nmask.p);
-    HIPCHK(ctx, hipGetLastError());
-    return BNS_OK;
-}
-
-// windows over the emitted stream (-C, real-entropy score) wider than 64 k-mers keep their queue image in global memory
-int set_win_scratch(bns_ctx *ctx, ClassifyParams &p, unsigned grid)
-{
-    p.win_scratch = nullptr;
-    const bool stream_windows = !ctx->spaced && (!ctx->canon || ctx->score == BNS_SCORE_ENTROPY_STRING);
-    if (!stream_windows || ctx->win <= ctx->c || ctx->win - ctx->c + 1 <= 64) return BNS_OK;
-    const size_t per_wave = (size_t)2 * (ctx->win - ctx->c + 65u) * 8;
-    const int rc = ensure(ctx, ctx->scratch, (size_t)grid * 4 * per_wave);
-    if (rc != BNS_OK) return rc;
-    p.win_scratch = (u64 *)ctx->scratch.p;
-    return BNS_OK;
-}
-
 template <class F>
 void dispatch_sp_layout(bool spaced, int layout, F &&f)
 {
@@ -299,79 +242,10 @@ int ready(bns_ctx *ctx, bool need_table, bool need_tax)
 
 }  // namespace
 
+#include "bns_classify.hpp"
 #include "bns_build.hpp"
 #include "bns_table_load.hpp"
 #include "bns_windows.hpp"
-
-namespace {
-// Every classify_kernel / classify_overflow_kernel launch goes through these two: the instantiation launched and the one
-// recorded in the form are the same template arguments.
-// max_blocks: the workgroups that are resident at once (or fewer: bns_debug_set_claim_waves).  Units per claim: the full chunk when
-// that leaves every one of their wavefronts at least one, else an even share (>= 4: a claim is an offsets load); the grid and
-// the start of the dynamic claims follow from it (bns_claims.hpp).
-template <bool SP, int LY, int KT, int NM, int SPAN, bool OVC, bool WIDE, bool PACKED>
-void launch_classify(ClassifyForm &f, const ClassifyParams &p0, unsigned max_blocks, hipStream_t st)
-{
-    ClassifyParams p = p0;
-    u32 grid;
-    const u32 full = classify_chunk((u32)p.nmates);
-    claim_geometry(p.n_units, max_blocks, full, p.chunk, grid);
-    p.claim_base = claim_dynamic_start(p.n_units, grid * 4u, p.chunk, full);
-    if (p.chunk < full) p.work_counter = nullptr;          // dealt out by the static claims alone: the kernel asks no counter
-    f = ClassifyForm{};
-    f.w[ClassifyForm::VALID] = 1; f.w[ClassifyForm::SPACED] = SP; f.w[ClassifyForm::LAYOUT] = LY; f.w[ClassifyForm::KT] = KT;
-    f.w[ClassifyForm::NM] = NM; f.w[ClassifyForm::SPAN] = SPAN; f.w[ClassifyForm::OVC] = OVC; f.w[ClassifyForm::WIDE] = WIDE;
-    f.w[ClassifyForm::PACKED] = PACKED; f.w[ClassifyForm::CHUNK] = p.chunk; f.w[ClassifyForm::GRID] = grid;
-    hipLaunchKernelGGL((classify_kernel<SP, LY, KT, NM, SPAN, OVC, WIDE, PACKED>), dim3(grid), dim3(256), 0, st, p);
-}
-template <bool SP, int LY, bool WIDE, bool PACKED>
-void launch_classify_overflow(ClassifyForm &f, const ClassifyParams &p, u32 n_units, unsigned grid, hipStream_t st, u32 *scratch, u64 total_bases)
-{
-    f.w[ClassifyForm::OVF_LAUNCHED] = 1; f.w[ClassifyForm::OVF_SPACED] = SP; f.w[ClassifyForm::OVF_LAYOUT] = LY;
-    f.w[ClassifyForm::OVF_WIDE] = WIDE; f.w[ClassifyForm::OVF_PACKED] = PACKED; f.w[ClassifyForm::OVF_UNITS] = n_units;
-    f.w[ClassifyForm::OVF_GRID] = grid;
-    hipLaunchKernelGGL((classify_overflow_kernel<SP, LY, WIDE, PACKED>), dim3(grid), dim3(64), 0, st, p, scratch, total_bases);
-}
-
-// classify_kernel<false, MINBUCKET, KT, NM, SPAN, OVC, WIDE> for the (k, window) pairs the loader can produce with a common k.
-// FULL: every form of the overflow lookup and the minimizer identity; otherwise the usual form only (the rest falls back to the
-// generic kernel, which reads k from its arguments).
-template <int KT, int SPAN, bool FULL>
-bool launch_kt(ClassifyForm &f, const ClassifyParams &p, unsigned grid, hipStream_t st, bool ovc, bool wide, bool packed)
-{
-    if ((int)p.k != KT || KT - (int)p.m != SPAN || !p.canon) return false;     // (non-canonical contiguous seeds: the generic kernel)
-    if (!FULL && (ovc || wide || packed)) return false;
-    if (packed && (ovc || wide)) return false;                   // (packed input: the usual form only; the rest goes to the generic kernels)
-    auto go = [&](auto nm) {
-        constexpr int NM = decltype(nm)::value;
-        if constexpr (FULL) {
-            if (packed) { launch_classify<false, 2, KT, NM, SPAN, false, false, true>(f, p, grid, st); return; }
-            if (wide) {
-                if (ovc) launch_classify<false, 2, KT, NM, SPAN, true, true, false>(f, p, grid, st);
-                else     launch_classify<false, 2, KT, NM, SPAN, false, true, false>(f, p, grid, st);
-                return;
-            }
-            if (ovc) { launch_classify<false, 2, KT, NM, SPAN, true, false, false>(f, p, grid, st); return; }
-        }
-        launch_classify<false, 2, KT, NM, SPAN, false, false, false>(f, p, grid, st);
-    };
-    if (p.nmates == 1) go(std::integral_constant<int, 1>{}); else go(std::integral_constant<int, 2>{});
-    return true;
-}
-template <int KT, bool FULL>
-bool launch_k(ClassifyForm &f, const ClassifyParams &p, unsigned grid, hipStream_t st, bool ovc, bool wide, bool packed)
-{
-    constexpr int S0 = KT - (int)minimizer_len(KT, MIN_CANDS[0]), S1 = KT - (int)minimizer_len(KT, MIN_CANDS[1]), S2 = KT - (int)minimizer_len(KT, MIN_CANDS[2]);
-    return launch_kt<KT, S0, FULL>(f, p, grid, st, ovc, wide, packed) || launch_kt<KT, S1, FULL>(f, p, grid, st, ovc, wide, packed) ||
-           launch_kt<KT, S2, FULL>(f, p, grid, st, ovc, wide, packed);
-}
-bool launch_fixed_k(ClassifyForm &f, const ClassifyParams &p, unsigned grid, hipStream_t st, bool ovc, bool wide, bool packed)
-{
-    return launch_k<31, true>(f, p, grid, st, ovc, wide, packed) || launch_k<21, false>(f, p, grid, st, ovc, wide, packed) ||
-           launch_k<25, false>(f, p, grid, st, ovc, wide, packed) || launch_k<27, false>(f, p, grid, st, ovc, wide, packed) ||
-           launch_k<32, false>(f, p, grid, st, ovc, wide, packed);
-}
-}  // namespace
 
 extern "C" {
 
@@ -1122,132 +996,15 @@ int bns_timing_summary(bns_ctx *ctx, double *sum_ms, int *count)
     return BNS_OK;
 }
 
-// One batch, inputs resident: ASCII (d_bases) or packed (d_words [+ d_nmask]); exactly one of d_bases / d_words is set.
-static int classify_device_impl(bns_ctx *ctx, const char *d_bases, const uint64_t *d_words, const uint32_t *d_nmask, const uint64_t *d_offsets,
-                                uint64_t n_reads, uint64_t total_bases, uint32_t max_read_len, int paired, uint32_t *d_taxon,
-                                uint32_t *d_missing, uint32_t *d_ambig, uint32_t *d_n_hits, uint32_t *d_hits, void *stream)
-{
-    int rc = ready(ctx, true, true);
-    if (rc != BNS_OK) return rc;
-    const bool packed = d_words != nullptr;
-    if (!d_offsets || !d_taxon || (!d_bases && !d_words && total_bases)) return BNS_ERR_ARG;
-    if (paired && (n_reads & 1)) return fail(ctx, BNS_ERR_ARG, "paired input needs an even number of reads");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    const int nm = paired ? 2 : 1;
-    const u64 n_units = n_reads / (u64)nm;
-    if (n_units == 0) return BNS_OK;
-    if (n_units >= (1ULL << 32) - (1ULL << 22)) return fail(ctx, BNS_ERR_ARG, "more than 2^32 - 2^22 units in one batch: split it");   // (headroom: every wavefront draws one claim past the end)
-
-    SmallLayout *sm = (SmallLayout *)ctx->small.p;
-    u32 *d_ovf = &sm->ovf_count;
-    u32 *d_work = &sm->work_counter;
-    HIPCHK(ctx, hipMemsetAsync(sm, 0, SMALL_CLASSIFY_ZERO, st));   // work_counter, ovf_count, max_len in one memset
-    if (max_read_len == 0) {
-        hipLaunchKernelGGL(max_len_kernel, dim3(grid_for(ctx, n_reads, 256)), dim3(256), 0, st, d_offsets, (u64)n_reads, &sm->max_len);
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(&max_read_len, &sm->max_len, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-    }
-    const u64 max_unit_kmers = max_read_len >= ctx->c ? (u64)nm * (max_read_len - ctx->c + 1) : 0;
-    const bool can_overflow = max_unit_kmers > LDS_CAP;
-    if (can_overflow && (rc = ensure(ctx, ctx->ovf_list, (size_t)n_units * 8)) != BNS_OK) return rc;
-
-    ClassifyParams p;
-    fill_params(ctx, p);
-    p.offsets = d_offsets; p.n_units = n_units; p.nmates = nm; p.bases = (const u8 *)d_bases;
-    if (packed) { p.words = (const u64 *)d_words; p.nmask = (const u32 *)d_nmask; }
-    p.taxon = d_taxon; p.missing = d_missing; p.ambig = d_ambig; p.n_hits = d_n_hits; p.hits = d_hits;
-    if ((ctx->conf_num || ctx->sketch_cap) && !d_hits) {   // the confidence and sketch passes read the hit stream: into a buffer of ours when the caller takes none
-        if ((rc = ensure(ctx, ctx->conf_hits, (size_t)total_bases * 4 + 4)) != BNS_OK) return rc;
-        p.hits = (u32 *)ctx->conf_hits.p;
-    }
-    p.want_hits = p.hits ? 1 : 0;
-    if ((rc = ensure(ctx, ctx->records, (size_t)n_units * 16)) != BNS_OK) return rc;
-    p.records = (uint4 *)ctx->records.p;
-    p.ovf_count = d_ovf; p.ovf_list = can_overflow ? (u64 *)ctx->ovf_list.p : nullptr;
-    p.work_counter = d_work;
-    // reference behaviour for a spaced seed through the string for_each: nothing is emitted
-    p.emit_none = (ctx->spaced && !ctx->spaced_intended) ? 1 : 0;
-
-    // persistent grid: at most the workgroups that are resident at once, 8 of 4 wavefronts per CU (launch_classify sizes the claims by it)
-    unsigned grid = (unsigned)ctx->n_cu * 8u;
-    if (ctx->claim_waves) grid = std::max(1u, std::min(grid, ctx->claim_waves / 4u));
-    const int evi = ctx->ev_head;
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev0[evi], st));
-    // Contiguous seeds on the clustered table with a common k: k, the mates per unit and the minimizer window are compile-time
-    // constants (k = 31 in every form -- either overflow lookup, either minimizer identity; k = 21, 25, 27, 32 in the usual one).
-    // (the form of the overflow-table lookup: cooperative when more than 1 key in 1000 lives there, see probe_minbucket)
-    const bool ovf_heavy = (ctx->dbg & BNS_DBG_OVC_ON) || (!(ctx->dbg & BNS_DBG_OVC_OFF) && ctx->n_ovf_keys * 1000ULL > ctx->n_keys);
-    const bool clustered = !ctx->spaced && ctx->layout == BNS_LAYOUT_MINBUCKET;
-    bool launched = false;
-    ClassifyForm &form = ctx->last_form;
-    if (clustered) launched = launch_fixed_k(form, p, grid, st, ovf_heavy, ctx->table_wide, packed);
-    if (!launched && clustered && ctx->table_wide) {
-        if (packed) launch_classify<false, 2, 0, 0, 8, false, true, true>(form, p, grid, st);
-        else        launch_classify<false, 2, 0, 0, 8, false, true, false>(form, p, grid, st);
-        launched = true;
-    }
-    if (!launched)
-        dispatch_sp_layout(ctx->spaced, ctx->layout, [&](auto sp, auto ly) {
-            constexpr bool SP = decltype(sp)::value;
-            constexpr int LY = decltype(ly)::value;
-            // (a wide probe stage takes more LDS per block than 8 per CU allow)
-            auto go = [&](auto pk) {
-                constexpr bool PK = decltype(pk)::value;
-                int per_cu = 8;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, classify_kernel<SP, LY, 0, 0, 8, false, false, PK>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 8;
-                const unsigned g = std::min<unsigned>(grid, (unsigned)ctx->n_cu * (unsigned)std::min(per_cu, 8));
-                launch_classify<SP, LY, 0, 0, 8, false, false, PK>(form, p, g, st);
-            };
-            if (packed) go(std::true_type{}); else go(std::false_type{});
-        });
-    HIPCHK(ctx, hipGetLastError());
-    if (ctx->timing) {
-        HIPCHK(ctx, hipEventRecord(ctx->ev1[evi], st));
-        ctx->ev_head = (evi + 1) % bns_ctx::EV_RING;
-        ctx->ev_count = std::min(ctx->ev_count + 1, (int)bns_ctx::EV_RING);
-    }
-
-    if (can_overflow) {
-        u32 h_ovf = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&h_ovf, d_ovf, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        if (h_ovf) {
-            if ((rc = ensure(ctx, ctx->scratch, (size_t)total_bases * 16)) != BNS_OK) return rc;
-            const dim3 og(std::min<u32>(h_ovf, (u32)ctx->n_cu * 8));
-            u32 *const scr = (u32 *)ctx->scratch.p;
-            if (clustered && ctx->table_wide) {
-                if (packed) launch_classify_overflow<false, 2, true, true>(form, p, h_ovf, og.x, st, scr, (u64)total_bases);
-                else        launch_classify_overflow<false, 2, true, false>(form, p, h_ovf, og.x, st, scr, (u64)total_bases);
-            } else
-            dispatch_sp_layout(ctx->spaced, ctx->layout, [&](auto sp, auto ly) {
-                if (packed) launch_classify_overflow<decltype(sp)::value, decltype(ly)::value, false, true>(form, p, h_ovf, og.x, st, scr, (u64)total_bases);
-                else        launch_classify_overflow<decltype(sp)::value, decltype(ly)::value, false, false>(form, p, h_ovf, og.x, st, scr, (u64)total_bases);
-            });
-            HIPCHK(ctx, hipGetLastError());
-        }
-    }
-    if (ctx->conf_num) {                             // bns_set_confidence: the taxa of the records walked up to theta's clade
-        hipLaunchKernelGGL(confidence_kernel, dim3(grid_for(ctx, (n_units + CONF_GROUP - 1) / CONF_GROUP, 4)), dim3(256), 0, st, (uint4 *)ctx->records.p,
-                           (const u64 *)d_offsets, (u32)nm, (const u32 *)p.hits, (u64)n_units, (const TaxNode *)ctx->nodes, ctx->n_nodes, ctx->conf_num,
-                           ctx->conf_den);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    hipLaunchKernelGGL(unpack_kernel, dim3(grid_for(ctx, n_units, 256)), dim3(256), 0, st, (const uint4 *)ctx->records.p, (u64)n_units,
-                       d_taxon, d_missing, d_ambig, d_n_hits);
-    HIPCHK(ctx, hipGetLastError());
-    if ((rc = tally_units(ctx, d_taxon, n_units, st)) != BNS_OK || !ctx->sketch_cap) return rc;   // (every classifying entry point comes through here, once per unit)
-    return sketch_units(ctx, p, d_bases, n_reads, total_bases, st);
-}
-
+// ---- classify: thin forwards into bns_classify.hpp -------------------------------------------------------------------------
 int bns_classify_batch_device(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
                               uint64_t total_bases, uint32_t max_read_len, int paired, uint32_t *d_taxon,
                               uint32_t *d_missing, uint32_t *d_ambig, uint32_t *d_n_hits, uint32_t *d_hits, void *stream)
 {
     if (!d_bases && total_bases) return BNS_ERR_ARG;
-    return classify_device_impl(ctx, d_bases, nullptr, nullptr, d_offsets, n_reads, total_bases, max_read_len, paired, d_taxon, d_missing, d_ambig,
-                                d_n_hits, d_hits, stream);
+    ClassifyIn in;
+    in.bases = d_bases; in.offsets = d_offsets; in.n_reads = n_reads; in.total_bases = total_bases; in.max_read_len = max_read_len; in.paired = paired;
+    return classify_device_impl(ctx, in, UnitOut{d_taxon, d_missing, d_ambig, d_n_hits, d_hits}, stream);
 }
 
 int bns_classify_batch_packed_device(bns_ctx *ctx, const uint64_t *d_words, const uint32_t *d_nmask, const uint64_t *d_offsets,
@@ -1255,102 +1012,13 @@ int bns_classify_batch_packed_device(bns_ctx *ctx, const uint64_t *d_words, cons
                                      uint32_t *d_missing, uint32_t *d_ambig, uint32_t *d_n_hits, uint32_t *d_hits, void *stream)
 {
     if (!d_words) return BNS_ERR_ARG;
-    return classify_device_impl(ctx, nullptr, d_words, d_nmask, d_offsets, n_reads, total_bases, max_read_len, paired, d_taxon, d_missing, d_ambig,
-                                d_n_hits, d_hits, stream);
+    ClassifyIn in;
+    in.words = d_words; in.nmask = d_nmask; in.offsets = d_offsets; in.n_reads = n_reads; in.total_bases = total_bases; in.max_read_len = max_read_len;
+    in.paired = paired;
+    return classify_device_impl(ctx, in, UnitOut{d_taxon, d_missing, d_ambig, d_n_hits, d_hits}, stream);
 }
 
-// ---- packed reads on the host side ---------------------------------------------------------------------------------------
 uint64_t bns_packed_words(uint64_t total_bases, uint64_t n_reads) { return (total_bases >> 5) + n_reads + 1; }
-
-namespace {
-// 32 ASCII bases -> one image word (2-bit codes, first base in the top two bits) + 32 invalid-base flags (bit 31 - i = base i).
-// alphabet.h:128 semantics: A/C/G/T in either case, everything else invalid (its code bits are 0).
-inline void pack32_scalar(const unsigned char *s, unsigned n, u64 &word, u32 &bad)
-{
-    u64 w = 0; u32 b = 0;
-    for (unsigned i = 0; i < n; ++i) {
-        const unsigned c = s[i] & 0xDFu, h = (c >> 1) & 3u;                    // A0 C1 T2 G3
-        const bool ok = c == (unsigned)"ACTG"[h];
-        const u64 code = ok ? (h ^ (h >> 1)) : 0u;                             // A0 C1 G2 T3
-        w |= code << (62u - 2u * i);
-        b |= (ok ? 0u : 1u) << (31u - i);
-    }
-    word = w; bad = b;
-}
-#if defined(__x86_64__)
-__attribute__((target("avx2,bmi2"))) inline void pack32_avx2(const unsigned char *s, u64 &word, u32 &bad)
-{
-    const __m256i x = _mm256_loadu_si256((const __m256i *)s);
-    const __m256i fold = _mm256_and_si256(x, _mm256_set1_epi8((char)0xDF));
-    const __m256i h = _mm256_and_si256(_mm256_srli_epi16(x, 1), _mm256_set1_epi8(3));            // A0 C1 T2 G3
-    const __m256i tbl = _mm256_setr_epi8('A', 'C', 'T', 'G', 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 'A', 'C', 'T', 'G', 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0);
-    const __m256i ok = _mm256_cmpeq_epi8(fold, _mm256_shuffle_epi8(tbl, h));
-    const __m256i code = _mm256_and_si256(_mm256_xor_si256(h, _mm256_and_si256(_mm256_srli_epi16(h, 1), _mm256_set1_epi8(1))), ok);   // A0 C1 G2 T3, 0 where invalid
-    const u32 lo = (u32)_mm256_movemask_epi8(_mm256_slli_epi16(code, 7));                        // bit i = low code bit of base i
-    const u32 hi = (u32)_mm256_movemask_epi8(_mm256_slli_epi16(code, 6));
-    const u32 okm = (u32)_mm256_movemask_epi8(ok);
-    // base 0 to the top: reverse the 32-bit planes, then interleave them (hi plane on the odd bits)
-    word = _pdep_u64((u64)__builtin_bitreverse32(hi), 0xAAAAAAAAAAAAAAAAULL) | _pdep_u64((u64)__builtin_bitreverse32(lo), 0x5555555555555555ULL);
-    bad = __builtin_bitreverse32(~okm);
-}
-#endif
-struct BadList { std::vector<u64> idx; std::vector<u32> mask; };
-// src(r) = where read r's bases are (offsets[] say how many)
-extern "C++" template <class Src>
-void pack_range(Src src, const u64 *offsets, u64 r0, u64 r1, u64 n_total, u64 *words, BadList &bl, bool simd)
-{
-    for (u64 r = r0; r < r1; ++r) {
-        const u64 o = offsets[r], L = offsets[r + 1] - o, wb = (o >> 5) + r;
-        const unsigned char *s = (const unsigned char *)src(r);
-        const u64 full = L >> 5;
-        for (u64 w = 0; w <= full; ++w) {
-            const unsigned n = w < full ? 32u : (unsigned)(L & 31u);
-            if (!n) break;
-            u64 word; u32 bad;
-#if defined(__x86_64__)
-            if (simd && n == 32u) pack32_avx2(s + 32 * w, word, bad); else
-#endif
-            pack32_scalar(s + 32 * w, n, word, bad);
-            words[wb + w] = word;
-            if (bad) { bl.idx.push_back(wb + w); bl.mask.push_back(bad); }
-        }
-        // the slack word(s) between this read's last word and the next read's first -- and the one behind the last read -- are
-        // zeroed: the image is then a pure function of the reads (recycled buffers upload no stale bytes, images compare byte for byte)
-        for (u64 w = wb + ((L + 31u) >> 5), e = (offsets[r + 1] >> 5) + r + 1; w <= e && (w < e || r + 1 == n_total); ++w) words[w] = 0;
-    }
-}
-}  // namespace
-
-extern "C++" template <class Src>
-static int pack_reads_impl(Src src, const uint64_t *offsets, uint64_t n_reads, uint64_t *words, uint64_t *bad_word,
-                           uint32_t *bad_mask, uint64_t bad_cap, uint64_t *n_bad, int threads)
-{
-    bool simd = false;
-#if defined(__x86_64__)
-    simd = __builtin_cpu_supports("avx2") && __builtin_cpu_supports("bmi2");
-#endif
-    const unsigned nt = (unsigned)std::max(1, std::min<int>(threads, (int)(n_reads / 4096 + 1)));
-    std::vector<BadList> bl(nt);
-    if (nt == 1) pack_range(src, offsets, 0, n_reads, n_reads, words, bl[0], simd);
-    else {
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < nt; ++t)
-            th.emplace_back([&, t] { pack_range(src, offsets, n_reads * t / nt, n_reads * (t + 1) / nt, n_reads, words, bl[t], simd); });
-        for (auto &x : th) x.join();
-    }
-    u64 tot = 0;
-    for (auto &b : bl) tot += b.idx.size();
-    *n_bad = tot;
-    if (tot > bad_cap || (tot && (!bad_word || !bad_mask))) return BNS_ERR_ARG;       // (*n_bad says how much room is needed)
-    u64 at = 0;
-    for (auto &b : bl) {                                           // (thread ranges are contiguous: the list comes out sorted by word)
-        if (b.idx.empty()) continue;
-        std::memcpy(bad_word + at, b.idx.data(), b.idx.size() * 8);
-        std::memcpy(bad_mask + at, b.mask.data(), b.mask.size() * 4);
-        at += b.idx.size();
-    }
-    return BNS_OK;
-}
 
 int bns_pack_reads(const char *bases, const uint64_t *offsets, uint64_t n_reads, uint64_t *words, uint64_t *bad_word,
                    uint32_t *bad_mask, uint64_t bad_cap, uint64_t *n_bad, int threads)
@@ -1368,240 +1036,25 @@ int bns_pack_reads_ptrs(const char *const *seqs, const uint32_t *lens, uint64_t 
     return pack_reads_impl([=](u64 r) { return seqs[r]; }, offsets, n_reads, words, bad_word, bad_mask, bad_cap, n_bad, threads);
 }
 
-namespace {
-__global__ void scatter_mask_kernel(const u64 *__restrict__ idx, const u32 *__restrict__ mask, u64 n, u32 *__restrict__ dense)
-{
-    const u64 stride = (u64)gridDim.x * blockDim.x;
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dense[idx[i]] = mask[i];
-}
-
-// What a host batch is made of: ASCII bases, or packed words + the sparse list of words that hold an invalid base.
-struct HostIn { const char *bases = nullptr; const u64 *words = nullptr; const u64 *bad_word = nullptr; const u32 *bad_mask = nullptr; u64 n_bad = 0; };
-
-// Upload + classify of one host batch, results left in ctx->st_out[0..3] (+ st_hits): large batches go up in slices on a second
-// stream, slice i+1 while slice i is classified (the upload is the longer leg: 150 -- packed 40 -- bytes per read over PCIe against
-// ~0.6 ns of kernel).  A slice is a unit-aligned read range; device offsets stay absolute, so a slice is just a shifted offsets
-// pointer and a shifted output pointer.
-// Where the per-unit results of a host batch go; a sliced batch copies each slice's results back as soon as that slice is classified
-// (the copy runs while the next slice is uploaded: the two directions of the link are separate), and says so in `copied`.
-struct HostOut { uint32_t *taxon = nullptr, *missing = nullptr, *ambig = nullptr, *n_hits = nullptr; bool copied = false; };
-
-int classify_host_impl(bns_ctx *ctx, const HostIn &in, const uint64_t *offsets, uint64_t n_reads, int paired, bool want_missing, bool want_ambig,
-                       bool want_nhits, bool want_hits, HostOut *out = nullptr)
-{
-    int rc;
-    const bool packed = in.words != nullptr;
-    const u64 total = offsets[n_reads];
-    const u64 n_units = n_reads / (paired ? 2 : 1);
-    // the longest read of a range of the batch (what a launch sizes its rounds by): scanned per slice, next to that slice's
-    // launch, so that the scan of 10 M offsets (80 MB) runs under the uploads instead of in front of them
-    auto longest = [&](u64 r0, u64 r1) { u32 m = 0; for (u64 r = r0; r < r1; ++r) m = std::max<u32>(m, (u32)(offsets[r + 1] - offsets[r])); return m; };
-    const u64 n_words = bns_packed_words(total, n_reads);
-    if (packed) {
-        if ((rc = ensure(ctx, ctx->st_words, (size_t)n_words * 8 + 8)) != BNS_OK) return rc;
-        if (in.n_bad && (rc = ensure(ctx, ctx->st_nmask, (size_t)n_words * 4 + 4)) != BNS_OK) return rc;
-        if (in.n_bad && (rc = ensure(ctx, ctx->st_bad, (size_t)in.n_bad * 12)) != BNS_OK) return rc;
-    } else if ((rc = ensure(ctx, ctx->st_bases, (size_t)total + 8)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_offsets, (size_t)(n_reads + 1) * 8)) != BNS_OK) return rc;
-    for (int i = 0; i < 4; ++i) if ((rc = ensure(ctx, ctx->st_out[i], (size_t)n_units * 4)) != BNS_OK) return rc;
-    if (want_hits && (rc = ensure(ctx, ctx->st_hits, (size_t)total * 4 + 4)) != BNS_OK) return rc;
-    hipStream_t st = ctx->stream;
-    const u32 *d_nmask = nullptr;
-    if (packed && in.n_bad) {
-        // the dense flag words the kernel reads: zero, then the few words that hold an invalid base scattered in
-        u64 *d_idx = (u64 *)ctx->st_bad.p;
-        u32 *d_msk = (u32 *)((char *)ctx->st_bad.p + (size_t)in.n_bad * 8);
-        HIPCHK(ctx, hipMemsetAsync(ctx->st_nmask.p, 0, (size_t)n_words * 4, st));
-        HIPCHK(ctx, hipMemcpyAsync(d_idx, in.bad_word, (size_t)in.n_bad * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(d_msk, in.bad_mask, (size_t)in.n_bad * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(scatter_mask_kernel, dim3(grid_for(ctx, in.n_bad, 256)), dim3(256), 0, st, (const u64 *)d_idx, (const u32 *)d_msk, (u64)in.n_bad,
-                           (u32 *)ctx->st_nmask.p);
-        HIPCHK(ctx, hipGetLastError());
-        d_nmask = (const u32 *)ctx->st_nmask.p;
-    }
-    auto run = [&](u64 r0, u64 nr, u64 u0) -> int {
-        u32 *o0 = (u32 *)ctx->st_out[0].p + u0, *o1 = want_missing ? (u32 *)ctx->st_out[1].p + u0 : nullptr, *o2 = want_ambig ? (u32 *)ctx->st_out[2].p + u0 : nullptr;
-        u32 *o3 = (want_nhits || want_hits) ? (u32 *)ctx->st_out[3].p + u0 : nullptr, *oh = want_hits ? (u32 *)ctx->st_hits.p : nullptr;
-        // (packed: the word base of a read is (offsets[r] >> 5) + r with r counted from the START of the batch, so a slice hands the
-        // kernel word / flag pointers advanced by r0 words: read r0 + i of the batch is read i of the launch)
-        return classify_device_impl(ctx, packed ? nullptr : (const char *)ctx->st_bases.p, packed ? (const u64 *)ctx->st_words.p + r0 : nullptr,
-                                    (packed && d_nmask) ? d_nmask + r0 : nullptr, (const u64 *)ctx->st_offsets.p + r0, nr, total, std::max<u32>(longest(r0, r0 + nr), 1),
-                                    paired, o0, o1, o2, o3, oh, st);
-    };
-    auto upload = [&](u64 r0, u64 r1, hipStream_t cs) -> int {
-        const u64 b0 = offsets[r0], b1 = offsets[r1];
-        if (packed) {
-            const u64 w0 = (b0 >> 5) + r0, w1 = r1 == n_reads ? n_words : (b1 >> 5) + r1;
-            if (w1 > w0) HIPCHK(ctx, hipMemcpyAsync((u64 *)ctx->st_words.p + w0, in.words + w0, (size_t)(w1 - w0) * 8, hipMemcpyHostToDevice, cs));
-        } else if (b1 > b0) HIPCHK(ctx, hipMemcpyAsync((char *)ctx->st_bases.p + b0, in.bases + b0, (size_t)(b1 - b0), hipMemcpyHostToDevice, cs));
-        HIPCHK(ctx, hipMemcpyAsync((u64 *)ctx->st_offsets.p + r0, offsets + r0, (size_t)(r1 - r0 + 1) * 8, hipMemcpyHostToDevice, cs));
-        return BNS_OK;
-    };
-    size_t slice_bytes = (size_t)64 << 20;                                // (8 .. 128 MiB measured within 5 % of each other; 64 the best)
-    if (ctx->dbg & BNS_DBG_SLICE_8K) slice_bytes = (size_t)8 << 10;       // (tests force slicing on small batches)
-    const int nmr = paired ? 2 : 1;
-    const u64 in_bytes = packed ? n_words * 8 : total;
-    u64 n_slices = std::min<u64>(16, std::max<u64>(1, in_bytes / slice_bytes));
-    if (n_slices > n_units) n_slices = n_units;
-    if (n_slices > 1) {
-        if (!ctx->copy_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-        if (out && !ctx->back_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->back_stream, hipStreamNonBlocking));
-        for (u64 i = 0; i < n_slices; ++i) {
-            if (!ctx->slice_ev[i]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->slice_ev[i], hipEventDisableTiming));
-            if (out && !ctx->done_ev[i]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->done_ev[i], hipEventDisableTiming));
-        }
-        // size the per-call workspaces for the largest slice up front: growing one mid-loop would hipFree, i.e. drain the GPU
-        const u64 max_slice_units = n_units / n_slices + 2;
-        if ((rc = ensure(ctx, ctx->records, (size_t)max_slice_units * 16)) != BNS_OK) return rc;
-        if ((rc = ensure(ctx, ctx->ovf_list, (size_t)max_slice_units * 8)) != BNS_OK) return rc;
-        HIPCHK(ctx, hipStreamSynchronize(st));                            // the staging buffers may still be read by earlier work
-        hipStream_t cs = ctx->copy_stream;              // (two alternating copy streams were tried: the link, not the DMA engine, is the limit)
-        auto slice_end = [&](u64 i) { return (i + 1 == n_slices) ? n_units : n_units * (i + 1) / n_slices; };
-        auto send = [&](u64 i) -> int {                 // slice i's upload, and the event the classify stream waits for
-            const u64 a = i ? slice_end(i - 1) : 0, b = slice_end(i);
-            int rc2 = upload(a * nmr, b * nmr, cs);
-            if (rc2 != BNS_OK) return rc2;
-            HIPCHK(ctx, hipEventRecord(ctx->slice_ev[i], cs));
-            return BNS_OK;
-        };
-        if ((rc = send(0)) != BNS_OK) return rc;
-        u64 u0 = 0;
-        for (u64 i = 0; i < n_slices; ++i) {
-            const u64 u1 = slice_end(i);
-            // slice i + 1 is on its way before slice i is classified (a launch whose units can overflow the in-LDS counter ends
-            // with a host-side wait: the next upload must not queue up behind that)
-            if (i + 1 < n_slices && (rc = send(i + 1)) != BNS_OK) { (void)hipStreamSynchronize(cs); return rc; }
-            HIPCHK(ctx, hipStreamWaitEvent(st, ctx->slice_ev[i], 0));
-            if (u1 > u0 && (rc = run(u0 * nmr, (u1 - u0) * nmr, u0)) != BNS_OK) { (void)hipStreamSynchronize(cs); return rc; }
-            if (out && u1 > u0) {
-                // (on a stream of their own: queued on the classify stream these copies held up the next slice's launch, and with it
-                // the upload after that -- 711 -> 860 M reads/s with all four arrays coming back)
-                const size_t nb = (size_t)(u1 - u0) * 4;
-                hipStream_t bs = ctx->back_stream;
-                HIPCHK(ctx, hipEventRecord(ctx->done_ev[i], st));
-                HIPCHK(ctx, hipStreamWaitEvent(bs, ctx->done_ev[i], 0));
-                HIPCHK(ctx, hipMemcpyAsync(out->taxon + u0, (u32 *)ctx->st_out[0].p + u0, nb, hipMemcpyDeviceToHost, bs));
-                if (out->missing) HIPCHK(ctx, hipMemcpyAsync(out->missing + u0, (u32 *)ctx->st_out[1].p + u0, nb, hipMemcpyDeviceToHost, bs));
-                if (out->ambig) HIPCHK(ctx, hipMemcpyAsync(out->ambig + u0, (u32 *)ctx->st_out[2].p + u0, nb, hipMemcpyDeviceToHost, bs));
-                if (out->n_hits) HIPCHK(ctx, hipMemcpyAsync(out->n_hits + u0, (u32 *)ctx->st_out[3].p + u0, nb, hipMemcpyDeviceToHost, bs));
-            }
-            u0 = u1;
-        }
-        if (out) {
-            out->copied = true;
-            HIPCHK(ctx, hipStreamSynchronize(ctx->back_stream));       // (the caller's arrays are complete when this returns)
-        }
-        return BNS_OK;
-    }
-    if ((rc = upload(0, n_reads, st)) != BNS_OK) return rc;
-    return run(0, n_reads, 0);
-}
-}  // namespace
-
-static int classify_host_entry(bns_ctx *ctx, const HostIn &in, const uint64_t *offsets, uint64_t n_reads, int paired,
-                               uint32_t *taxon, uint32_t *missing, uint32_t *ambig, uint32_t *n_hits, uint32_t *hits)
-{
-    int rc = ready(ctx, true, true);
-    if (rc != BNS_OK) return rc;
-    if (!offsets || !taxon) return BNS_ERR_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const u64 total = offsets[n_reads];
-    const u64 n_units = n_reads / (paired ? 2 : 1);
-    if (n_units == 0) return BNS_OK;
-    HostOut out; out.taxon = taxon; out.missing = missing; out.ambig = ambig; out.n_hits = n_hits;
-    if ((rc = classify_host_impl(ctx, in, offsets, n_reads, paired, missing != nullptr, ambig != nullptr, n_hits != nullptr, hits != nullptr, &out)) != BNS_OK) {
-        (void)hipStreamSynchronize(ctx->stream);                  // (copies into the caller's arrays may be in flight)
-        if (ctx->back_stream) (void)hipStreamSynchronize(ctx->back_stream);
-        return rc;
-    }
-    hipStream_t st = ctx->stream;
-    if (!out.copied) {
-        HIPCHK(ctx, hipMemcpyAsync(taxon, ctx->st_out[0].p, (size_t)n_units * 4, hipMemcpyDeviceToHost, st));
-        if (missing) HIPCHK(ctx, hipMemcpyAsync(missing, ctx->st_out[1].p, (size_t)n_units * 4, hipMemcpyDeviceToHost, st));
-        if (ambig) HIPCHK(ctx, hipMemcpyAsync(ambig, ctx->st_out[2].p, (size_t)n_units * 4, hipMemcpyDeviceToHost, st));
-        if (n_hits) HIPCHK(ctx, hipMemcpyAsync(n_hits, ctx->st_out[3].p, (size_t)n_units * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (hits && total) HIPCHK(ctx, hipMemcpyAsync(hits, ctx->st_hits.p, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return BNS_OK;
-}
-
 int bns_classify_batch(bns_ctx *ctx, const char *bases, const uint64_t *offsets, uint64_t n_reads, int paired,
                        uint32_t *taxon, uint32_t *missing, uint32_t *ambig, uint32_t *n_hits, uint32_t *hits)
 {
-    HostIn in; in.bases = bases;
-    return classify_host_entry(ctx, in, offsets, n_reads, paired, taxon, missing, ambig, n_hits, hits);
+    return classify_host_entry(ctx, HostIn::ascii(bases), offsets, n_reads, paired, UnitOut{taxon, missing, ambig, n_hits, hits});
 }
 
 int bns_classify_batch_packed(bns_ctx *ctx, const uint64_t *words, const uint64_t *bad_word, const uint32_t *bad_mask, uint64_t n_bad,
                               const uint64_t *offsets, uint64_t n_reads, int paired,
                               uint32_t *taxon, uint32_t *missing, uint32_t *ambig, uint32_t *n_hits, uint32_t *hits)
 {
-    if (!words || (n_bad && (!bad_word || !bad_mask))) return BNS_ERR_ARG;
-    HostIn in; in.words = words; in.bad_word = bad_word; in.bad_mask = bad_mask; in.n_bad = n_bad;
-    return classify_host_entry(ctx, in, offsets, n_reads, paired, taxon, missing, ambig, n_hits, hits);
-}
-
-static int classify_runs_entry(bns_ctx *ctx, const HostIn &in, const uint64_t *offsets, uint64_t n_reads, int paired,
-                               uint32_t *taxon, uint32_t *missing, uint32_t *ambig, uint32_t *n_hits, uint64_t *run_start,
-                               uint32_t *n_runs, const uint32_t **run_tax, const uint32_t **run_len, uint64_t *n_runs_total)
-{
-    int rc = ready(ctx, true, true);
-    if (rc != BNS_OK) return rc;
-    if (!offsets || !taxon || !run_start || !n_runs || !run_tax || !run_len) return BNS_ERR_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const u64 total = offsets[n_reads];
-    const int nm = paired ? 2 : 1;
-    const u64 n_units = n_reads / (u64)nm;
-    *run_tax = *run_len = nullptr;
-    if (n_runs_total) *n_runs_total = 0;
-    if (n_units == 0) return BNS_OK;
-    if ((rc = ensure(ctx, ctx->st_runs[0], (size_t)n_units * 8)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_runs[1], (size_t)n_units * 4)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_runs[2], (size_t)total * 4 + 4)) != BNS_OK) return rc;      // a run per hit at worst
-    if ((rc = ensure(ctx, ctx->st_runs[3], (size_t)total * 4 + 4)) != BNS_OK) return rc;
-    if ((rc = classify_host_impl(ctx, in, offsets, n_reads, paired, true, true, true, true)) != BNS_OK) return rc;
-    hipStream_t st = ctx->stream;
-    unsigned long long *d_cur = &((SmallLayout *)ctx->small.p)->runs_cursor;
-    HIPCHK(ctx, hipMemsetAsync(d_cur, 0, 8, st));
-    hipLaunchKernelGGL(hit_runs_kernel, dim3(grid_for(ctx, (n_units + HIT_RUNS_GROUP - 1) / HIT_RUNS_GROUP, 4)), dim3(256), 0, st, (const u32 *)ctx->st_hits.p,
-                       (const u64 *)ctx->st_offsets.p, (u32)nm, (const u32 *)ctx->st_out[3].p, (u64)n_units, (u64 *)ctx->st_runs[0].p,
-                       (u32 *)ctx->st_runs[1].p, (u32 *)ctx->st_runs[2].p, (u32 *)ctx->st_runs[3].p, d_cur);
-    HIPCHK(ctx, hipGetLastError());
-    unsigned long long n_tot = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&n_tot, d_cur, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(taxon, ctx->st_out[0].p, (size_t)n_units * 4, hipMemcpyDeviceToHost, st));
-    if (missing) HIPCHK(ctx, hipMemcpyAsync(missing, ctx->st_out[1].p, (size_t)n_units * 4, hipMemcpyDeviceToHost, st));
-    if (ambig) HIPCHK(ctx, hipMemcpyAsync(ambig, ctx->st_out[2].p, (size_t)n_units * 4, hipMemcpyDeviceToHost, st));
-    if (n_hits) HIPCHK(ctx, hipMemcpyAsync(n_hits, ctx->st_out[3].p, (size_t)n_units * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(run_start, ctx->st_runs[0].p, (size_t)n_units * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(n_runs, ctx->st_runs[1].p, (size_t)n_units * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));                    // n_tot is known from here on
-    if (ctx->h_run_cap < n_tot) {
-        if (ctx->h_run_tax) (void)hipHostFree(ctx->h_run_tax);
-        if (ctx->h_run_len) (void)hipHostFree(ctx->h_run_len);
-        ctx->h_run_tax = ctx->h_run_len = nullptr; ctx->h_run_cap = 0;
-        const size_t want = (size_t)n_tot + (size_t)n_tot / 2;
-        HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_run_tax, want * 4, hipHostMallocDefault));
-        HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_run_len, want * 4, hipHostMallocDefault));
-        ctx->h_run_cap = want;
-    }
-    if (n_tot) {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_run_tax, ctx->st_runs[2].p, (size_t)n_tot * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_run_len, ctx->st_runs[3].p, (size_t)n_tot * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-    }
-    *run_tax = ctx->h_run_tax; *run_len = ctx->h_run_len;
-    if (n_runs_total) *n_runs_total = n_tot;
-    return BNS_OK;
+    return classify_host_entry(ctx, HostIn::of_words(words, bad_word, bad_mask, n_bad), offsets, n_reads, paired, UnitOut{taxon, missing, ambig, n_hits, hits});
 }
 
 int bns_classify_batch_runs(bns_ctx *ctx, const char *bases, const uint64_t *offsets, uint64_t n_reads, int paired,
                             uint32_t *taxon, uint32_t *missing, uint32_t *ambig, uint32_t *n_hits, uint64_t *run_start,
                             uint32_t *n_runs, const uint32_t **run_tax, const uint32_t **run_len, uint64_t *n_runs_total)
 {
-    HostIn in; in.bases = bases;
-    return classify_runs_entry(ctx, in, offsets, n_reads, paired, taxon, missing, ambig, n_hits, run_start, n_runs, run_tax, run_len, n_runs_total);
+    return classify_runs_entry(ctx, HostIn::ascii(bases), offsets, n_reads, paired, UnitOut{taxon, missing, ambig, n_hits, nullptr}, run_start, n_runs,
+                               run_tax, run_len, n_runs_total);
 }
 
 int bns_classify_batch_packed_runs(bns_ctx *ctx, const uint64_t *words, const uint64_t *bad_word, const uint32_t *bad_mask, uint64_t n_bad,
@@ -1609,9 +1062,8 @@ int bns_classify_batch_packed_runs(bns_ctx *ctx, const uint64_t *words, const ui
                                    uint32_t *taxon, uint32_t *missing, uint32_t *ambig, uint32_t *n_hits, uint64_t *run_start,
                                    uint32_t *n_runs, const uint32_t **run_tax, const uint32_t **run_len, uint64_t *n_runs_total)
 {
-    if (!words || (n_bad && (!bad_word || !bad_mask))) return BNS_ERR_ARG;
-    HostIn in; in.words = words; in.bad_word = bad_word; in.bad_mask = bad_mask; in.n_bad = n_bad;
-    return classify_runs_entry(ctx, in, offsets, n_reads, paired, taxon, missing, ambig, n_hits, run_start, n_runs, run_tax, run_len, n_runs_total);
+    return classify_runs_entry(ctx, HostIn::of_words(words, bad_word, bad_mask, n_bad), offsets, n_reads, paired, UnitOut{taxon, missing, ambig, n_hits, nullptr},
+                               run_start, n_runs, run_tax, run_len, n_runs_total);
 }
 
 int bns_encode_batch_device(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_reads,

@@ -23,7 +23,7 @@
 // past the size at which three times the current table no longer fits beside the batch's workspace.  A grow that cannot be allocated
 // is refused with BNS_ERR_TABLE; the table as it was stays in the session, which then only bns_build_end may follow.
 //
-// Included by bns_api.hip after its helpers (fail, ensure, grid_for, pack_reads, set_win_scratch, ready): the host half below uses them.
+// Included by bns_api.hip after its helpers (fail, ensure, grid_for, ready) and bns_classify.hpp (pack_reads, set_win_scratch): the host half below uses them.
 #pragma once
 
 namespace bns {

@@ -791,9 +791,12 @@ int text_flush_batch(bns_ctx *ctx, TextWork &tw, TextCall &tc)
     unsigned long long *d_cur = &((SmallLayout *)ctx->small.p)->runs_cursor;     // (zeroed at the start of the call: it runs on over the batches)
     if (!parse_only) {
         if (ctx->timing) HIPCHK(ctx, hipEventRecord(tw.tc0[q], st));
-        frc = classify_device_impl(ctx, nullptr, (const u64 *)tw.words.p, (const u32 *)tw.nmask.p, (const u64 *)tw.offsets.p, n_reads, tc.acc_bases,
-                                   std::max<u32>(tc.acc_max_len, 1u), ns == 2 ? 1 : 0, o0, out->missing || need_runs ? o1 : nullptr,
-                                   out->ambig || need_runs ? o2 : nullptr, (out->n_hits || need_runs) ? o3 : nullptr, need_runs ? (u32 *)tw.hits.p : nullptr, st);
+        ClassifyIn ci;
+        ci.words = (const u64 *)tw.words.p; ci.nmask = (const u32 *)tw.nmask.p; ci.offsets = (const u64 *)tw.offsets.p;
+        ci.n_reads = n_reads; ci.total_bases = tc.acc_bases; ci.max_read_len = std::max<u32>(tc.acc_max_len, 1u); ci.paired = ns == 2 ? 1 : 0;
+        const UnitOut dev{o0, out->missing || need_runs ? o1 : nullptr, out->ambig || need_runs ? o2 : nullptr, (out->n_hits || need_runs) ? o3 : nullptr,
+                          need_runs ? (u32 *)tw.hits.p : nullptr};
+        frc = classify_device_impl(ctx, ci, dev, st);
         if (frc != BNS_OK) return frc;
         ++tc.n_launches;
         tc.prev_units = n_units;
@@ -842,10 +845,7 @@ int text_flush_batch(bns_ctx *ctx, TextWork &tw, TextCall &tc)
     HIPCHK(ctx, hipEventRecord(tw.ev_done[q], st));
     HIPCHK(ctx, hipStreamWaitEvent(bs, tw.ev_done[q], 0));
     if (!parse_only) {
-        HIPCHK(ctx, hipMemcpyAsync(out->taxon + u_done, o0, (size_t)n_units * 4, hipMemcpyDeviceToHost, bs));
-        if (out->missing) HIPCHK(ctx, hipMemcpyAsync(out->missing + u_done, o1, (size_t)n_units * 4, hipMemcpyDeviceToHost, bs));
-        if (out->ambig) HIPCHK(ctx, hipMemcpyAsync(out->ambig + u_done, o2, (size_t)n_units * 4, hipMemcpyDeviceToHost, bs));
-        if (out->n_hits) HIPCHK(ctx, hipMemcpyAsync(out->n_hits + u_done, o3, (size_t)n_units * 4, hipMemcpyDeviceToHost, bs));
+        BNS_RC(copy_units_back(ctx, UnitOut{out->taxon, out->missing, out->ambig, out->n_hits, nullptr}, UnitOut{o0, o1, o2, o3, nullptr}, u_done, n_units, bs));
         if (want_runs) {
             HIPCHK(ctx, hipMemcpyAsync(out->run_start + u_done, tw.runs[q][0].p, (size_t)n_units * 8, hipMemcpyDeviceToHost, bs));
             HIPCHK(ctx, hipMemcpyAsync(out->n_runs + u_done, tw.runs[q][1].p, (size_t)n_units * 4, hipMemcpyDeviceToHost, bs));

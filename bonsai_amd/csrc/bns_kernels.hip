@@ -1279,7 +1279,7 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
                     pad_lds<BNS_PAD_LDS>(lane);
                     const u64 kf = kmer;
                     const u64 krc = SPACED ? 0ULL : revcomp_top(win, k);
-                    if (!SPACED && (KT != 0 || p.canon)) kmer = kf < krc ? kf : krc;      // (the fixed-k instantiations are canonical-only: launch_kt)
+                    if (!SPACED && (KT != 0 || p.canon)) kmer = kf < krc ? kf : krc;      // (the fixed-k instantiations are canonical-only: choose_form)
                     ProbeResult pr;
 #ifdef BNS_ABLATION                                           // profiling builds only (tools/ablate.sh): results are wrong
                     if (p.dbg & 1) { pr.found = valid && (kmer & 1); pr.val = 1000u + (u32)(kmer & 3); }
@@ -2478,21 +2478,8 @@ __global__ __launch_bounds__(64) void resolve_kernel(const u32 *__restrict__ key
 }
 
 // ---- explicit instantiations used by the host side ------------------------------------------------------
-#define BNS_INST(SP, LY)                                                                            \
-    template __global__ void classify_kernel<SP, LY, 0, 0>(ClassifyParams);                            \
-    template __global__ void classify_overflow_kernel<SP, LY>(ClassifyParams, u32 *, u64);
-BNS_INST(false, 0) BNS_INST(false, 1) BNS_INST(true, 0) BNS_INST(true, 1) BNS_INST(false, 2) BNS_INST(true, 2)
-#undef BNS_INST
-template __global__ void classify_kernel<false, 2, 0, 0, 8, false, true>(ClassifyParams);
-template __global__ void classify_overflow_kernel<false, 2, true>(ClassifyParams, u32 *, u64);
-// packed input: the generic kernels of every layout (the k = 31 ones are instantiated where they are launched)
-#define BNS_INSTP(SP, LY)                                                                           \
-    template __global__ void classify_kernel<SP, LY, 0, 0, 8, false, false, true>(ClassifyParams);     \
-    template __global__ void classify_overflow_kernel<SP, LY, false, true>(ClassifyParams, u32 *, u64);
-BNS_INSTP(false, 0) BNS_INSTP(false, 1) BNS_INSTP(true, 0) BNS_INSTP(true, 1) BNS_INSTP(false, 2) BNS_INSTP(true, 2)
-#undef BNS_INSTP
-template __global__ void classify_kernel<false, 2, 0, 0, 8, false, true, true>(ClassifyParams);
-template __global__ void classify_overflow_kernel<false, 2, true, true>(ClassifyParams, u32 *, u64);
+// (classify_kernel / classify_overflow_kernel have none: each form on the lists of bns_classify_plan.hpp is instantiated where
+// bns_classify.hpp launches it)
 template __global__ void encode_kernel<false>(ClassifyParams, u64 *, u32 *);
 template __global__ void encode_kernel<true>(ClassifyParams, u64 *, u32 *);
 template __global__ void probe_kernel<0>(ClassifyParams, const u64 *, u64, u32 *, u8 *);

@@ -2,6 +2,7 @@
 #pragma once
 #include "bns_device.hpp"
 #include "bns_claims.hpp"
+#include "bns_classify_plan.hpp"
 
 namespace bns {
 
@@ -16,7 +17,7 @@ namespace bns {
 #define BNS_CLASSIFY_CHUNK2 31
 #endif
 constexpr u32 classify_chunk(u32 nmates) { return nmates == 1 ? BNS_CLASSIFY_CHUNK1 : BNS_CLASSIFY_CHUNK2; }
-constexpr u32 LDS_CAP = 128;   // distinct taxa per unit held in LDS; beyond that the overflow kernel takes over
+// (LDS_CAP, the distinct taxa per unit held in LDS, is in bns_classify_plan.hpp: the launch decides by it as well)
 
 struct ClassifyParams {
     // reads: ASCII (classify packs in-kernel) and pre-packed words (encode / build kernels)

@@ -28,7 +28,7 @@
 // 0xFFFFFFFF is BNS_TAX_ABSENT, no sequence's taxon: such a pair with call 0xFFFFFFFF counts as dropped).  A pair that meets no free
 // slot within the table's length adds its windows to `dropped`, so stored counts are exact and nothing is lost from the total.
 //
-// Included by bns_api.hip after its helpers (fail, ensure, grid_for, fill_params, ready, dispatch_sp_layout).
+// Included by bns_api.hip after its helpers (fail, ensure, grid_for, ready, dispatch_sp_layout) and bns_classify.hpp (fill_params).
 #pragma once
 #include "bns_device.hpp"
 #include "bns_kernels.hpp"

@@ -1,6 +1,8 @@
 """The forms classify_kernel is compiled in, restated from the dispatch RULE (not from the C++), the matrix of cases that runs
 every one of them, the read set those cases share, and a host restatement of the minimizer window (bucket_of / round_minhash,
 bns_device.hpp) that says where in its window every k-mer of that read set has its minimum.  A helper module, not a conftest:
+tests/test_classify_plan.py (CPU tier) holds it against the library's one statement of the rule, choose_form / choose_overflow_form
+and the lists of forms in bonsai_amd/csrc/bns_classify_plan.hpp, on every point of image()'s domain;
 tests/test_classify_forms_built.py (CPU tier) holds it against the built library, tests/test_gpu_classify_forms.py (GPU tier)
 runs it against the oracle.
 

@@ -563,3 +563,72 @@ def test_wide_identity_asked_for_a_windowless_k(gpu_ctx, oracle, k):
         gpu_ctx.set_minimizer_identity(0)
     reads = synth.simulate_reads(np.random.default_rng(k), w.genomes, 400, length=100, sub_rate=0.01, n_rate=0.002)
     check_classify(gpu_ctx, oracle, w, reads)
+
+
+SENTINEL = 0xA5A5A5A5
+
+
+@pytest.mark.parametrize("paired", [False, True])
+def test_unit_arrays_copied_back_as_requested(gpu_ctx, oracle, small_world, paired):
+    """The four per-unit arrays come back through one shared copy (copy_units_back) from every host entry point: bns_classify_batch,
+    bns_classify_batch_packed and the two _runs variants, unsliced and sliced (BNS_DBG_SLICE_8K, where each slice's arrays go back on
+    a stream of their own).  For every subset of {missing, ambig, n_hits} asked for (the others NULL), every array that is asked for
+    equals the all-requested unsliced ASCII result, and nothing is written behind its n_units entries."""
+    import ctypes as C
+    import itertools
+    import bonsai_amd
+    w = small_world
+    load_world(gpu_ctx, w, 2)
+    rng = np.random.default_rng(61)
+    reads = synth.simulate_reads(rng, w.genomes, 120, length=300, sub_rate=0.01, n_rate=0.002)
+    reads += [synth.rand_seq(rng, int(n)) for n in rng.integers(0, 700, size=120)]
+    order = rng.permutation(len(reads))
+    reads = [reads[i] for i in order]
+    bases, offsets = synth.concat(reads)
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    words, bw, bm = bonsai_amd.pack_reads(bases, offsets, threads=2)
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    bw = np.ascontiguousarray(bw, dtype=np.uint64)
+    bm = np.ascontiguousarray(bm, dtype=np.uint32)
+    assert bw.size > 0 and words.size * 8 >= 2 * 8192      # invalid bases to scatter; at least two slices even when packed
+    n_reads = offsets.size - 1
+    n_units = n_reads // (2 if paired else 1)
+    ref = gpu_ctx.classify(bases, offsets, paired=paired)
+    assert (ref["taxon"] != 0).mean() > 0.3 and ref["missing"].any() and ref["n_hits"].any()
+    L, h = gpu_ctx.L, gpu_ctx.h
+    u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+
+    def ptr(a, t):
+        return a.ctypes.data_as(t)
+
+    def call(entry, want):
+        arr = {k: np.full(n_units + 8, SENTINEL, dtype=np.uint32) for k in ("taxon",) + want}
+        outs = [ptr(arr[k], u32p) if k in arr else None for k in ("taxon", "missing", "ambig", "n_hits")]
+        packed_in = [ptr(words, u64p), ptr(bw, u64p), ptr(bm, u32p), bw.size]
+        if entry == "ascii":
+            rc = L.bns_classify_batch(h, bases.ctypes.data, ptr(offsets, u64p), n_reads, int(paired), *outs, None)
+        elif entry == "packed":
+            rc = L.bns_classify_batch_packed(h, *packed_in, ptr(offsets, u64p), n_reads, int(paired), *outs, None)
+        else:
+            run_start = np.zeros(n_units, dtype=np.uint64)
+            n_runs = np.zeros(n_units, dtype=np.uint32)
+            rt, rl, tot = u32p(), u32p(), C.c_uint64()
+            tail = [ptr(run_start, u64p), ptr(n_runs, u32p), C.byref(rt), C.byref(rl), C.cast(C.byref(tot), u64p)]
+            if entry == "ascii_runs":
+                rc = L.bns_classify_batch_runs(h, bases.ctypes.data, ptr(offsets, u64p), n_reads, int(paired), *outs, *tail)
+            else:
+                rc = L.bns_classify_batch_packed_runs(h, *packed_in, ptr(offsets, u64p), n_reads, int(paired), *outs, *tail)
+        assert rc == 0, (entry, want, L.bns_last_error(h))
+        return arr
+
+    subsets = [s for n in range(4) for s in itertools.combinations(("missing", "ambig", "n_hits"), n)]
+    try:
+        for dbg, entry, want in itertools.product((0, 0x4000), ("ascii", "packed", "ascii_runs", "packed_runs"), subsets):
+            gpu_ctx.debug_set(dbg)
+            arr = call(entry, want)
+            for k, a in arr.items():
+                assert np.array_equal(a[:n_units], ref[k]), (dbg, entry, want, k)
+                assert (a[n_units:] == SENTINEL).all(), (dbg, entry, want, k)
+    finally:
+        gpu_ctx.debug_set(0)
