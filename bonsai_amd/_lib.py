@@ -133,6 +133,9 @@ def load():
         "bns_build_export": (C.c_int, [vp, u32p, u64p, u32p]),
         "bns_build_stats": (C.c_int, [vp, u64p]),
         "bns_build_end": (C.c_int, [vp]),
+        "bns_build_minimize_begin": (C.c_int, [vp, C.c_uint32, C.c_uint64]),
+        "bns_build_minimize_add": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint64, vp]),
+        "bns_build_minimize_stats": (C.c_int, [vp, u64p]),
         "bns_windows_begin": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
         "bns_windows_add": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp, vp]),
         "bns_windows_read": (C.c_int, [vp, u32p, u32p, u64p, C.c_uint64, u64p, u64p, C.c_int]),

@@ -564,6 +564,24 @@ class Context:
     def build_end(self):
         self._chk(self.L.bns_build_end(self.h), "bns_build_end")
 
+    # ---- taxonomic-depth minimizers: the session's table of all k-mers (F) thinned to the deepest-LCA k-mer of every window (M)
+    def build_minimize_begin(self, w, n_buckets=0):
+        """freezes F (build_add / build_seed are refused from here on) and opens M with max(4, n_buckets rounded up to a power of
+        two) buckets; build_finish / build_end then act on M"""
+        self._chk(self.L.bns_build_minimize_begin(self.h, int(w), int(n_buckets)), "bns_build_minimize_begin")
+
+    def build_minimize_add(self, d_bases, d_offsets, n_seqs, total_bases, stream=None):
+        """one batch of the sequences F was built from (device arrays, as build_add takes them, without taxids)"""
+        self._chk(self.L.bns_build_minimize_add(self.h, d_bases, d_offsets, n_seqs, total_bases, stream), "bns_build_minimize_add")
+
+    def build_minimize_stats(self):
+        """{batches, grows, scored_keys (in F), keys (in M), lookups (positions looked up in F), add_s}"""
+        out = np.zeros(6, dtype=np.uint64)
+        self._chk(self.L.bns_build_minimize_stats(self.h, _p(out, u64p)), "bns_build_minimize_stats")
+        d = dict(zip(("batches", "grows", "scored_keys", "keys", "lookups"), (int(x) for x in out[:5])))
+        d["add_s"] = float(out[5]) * 1e-6
+        return d
+
     # ---- window session: every window of window_len bases of every sequence, called as classify calls a read
     def windows_begin(self, window_len, pair_cap=1 << 20):
         """opens a session; needs table, encoder and taxonomy, and no confidence threshold"""

@@ -1,5 +1,5 @@
 // bns_api.hip -- the C ABI of include/bonsai_amd.h: context, HBM residency, and the entry points; classify, table load, build and
-// window sessions are thin forwards into bns_classify.hpp, bns_table_load.hpp, bns_build.hpp and bns_windows.hpp.
+// window sessions are thin forwards into bns_classify.hpp, bns_table_load.hpp, bns_build.hpp (+ bns_minimize.hpp) and bns_windows.hpp.
 // Single translation unit for the device library: the kernels are included so their templates are visible.
 #include "../../include/bonsai_amd.h"
 #include "bns_kernels.hip"
@@ -244,12 +244,13 @@ int ready(bns_ctx *ctx, bool need_table, bool need_tax)
 
 #include "bns_classify.hpp"
 #include "bns_build.hpp"
+#include "bns_minimize.hpp"
 #include "bns_table_load.hpp"
 #include "bns_windows.hpp"
 
 extern "C" {
 
-int bns_version(void) { return 110; }
+int bns_version(void) { return 111; }
 
 int bns_device_pci_bus_id(int device, char *out, int cap)
 {
@@ -1450,6 +1451,12 @@ int bns_build_stats(const bns_ctx *ctx, uint64_t *out6)
     out6[4] = (u64)(ctx->build->s_add * 1e6); out6[5] = (u64)(ctx->build->s_grow * 1e6);
     return BNS_OK;
 }
+int bns_build_minimize_begin(bns_ctx *ctx, uint32_t w, uint64_t n_buckets_hint) { return minimize_begin(ctx, w, n_buckets_hint); }
+int bns_build_minimize_add(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bases, void *stream)
+{
+    return minimize_add(ctx, d_bases, d_offsets, n_seqs, total_bases, stream);
+}
+int bns_build_minimize_stats(const bns_ctx *ctx, uint64_t *out6) { return minimize_stats(ctx, out6); }
 int bns_build_end(bns_ctx *ctx)
 {
     if (!ctx) return BNS_ERR_ARG;

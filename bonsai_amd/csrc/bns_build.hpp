@@ -67,6 +67,15 @@ struct BuildSession {
     u64 n_keys = 0, n_seeded = 0, n_batches = 0, n_grows = 0;
     double s_add = 0, s_grow = 0;    // wall seconds inside bns_build_add, and the part of them spent growing (bns_build_stats)
     bool added = false, seeded = false, finished = false, failed = false;
+    // bns_build_minimize_begin (bns_minimize.hpp): the table above becomes M, the one it held until then is F, kept here and only read
+    bool minimizing = false;
+    u32 min_w = 0;                   // the window in bases, at least the comb
+    u64 f_nb = 0, f_n_keys = 0;
+    u64 *f_keys = nullptr;
+    u32 *f_vals = nullptr;
+    u32 *depth = nullptr;            // depth[id] for id in [0, n_nodes): nodes on the chain id -> root, 0 where the chain reaches none
+    u64 m_batches = 0, m_grows = 0, m_lookups = 0;
+    double s_min = 0;                // wall seconds inside bns_build_minimize_add
 };
 
 inline u64 build_upper(u64 nb) { return (u64)(nb * 0.77 + 0.5); }                  // khash64.h:198
@@ -88,6 +97,9 @@ void build_free(bns_ctx *ctx)
     if (s->keys) (void)hipFree(s->keys);
     if (s->vals) (void)hipFree(s->vals);
     if (s->flags) (void)hipFree(s->flags);
+    if (s->f_keys) (void)hipFree(s->f_keys);
+    if (s->f_vals) (void)hipFree(s->f_vals);
+    if (s->depth) (void)hipFree(s->depth);
     delete s;
     ctx->build = nullptr;
 }
@@ -171,6 +183,7 @@ int build_seed(bns_ctx *ctx, u64 n_buckets, const u32 *flags, const u64 *keys, c
     BuildSession *s;
     int rc = build_session(ctx, &s, "bns_build_seed");
     if (rc != BNS_OK) return rc;
+    if (s->minimizing) return fail(ctx, BNS_ERR_STATE, "bns_build_seed after bns_build_minimize_begin: the scored table is frozen");
     if (s->added || s->seeded || s->finished) return fail(ctx, BNS_ERR_STATE, "bns_build_seed comes once, between bns_build_begin and the first bns_build_add");
     if (n_buckets && (!flags || !keys || !vals)) return BNS_ERR_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -217,6 +230,7 @@ int build_add(bns_ctx *ctx, const char *d_bases, const u64 *d_offsets, u64 n_seq
     int rc = build_session(ctx, &s, "bns_build_add");
     if (rc != BNS_OK) return rc;
     if (s->finished) return fail(ctx, BNS_ERR_STATE, "bns_build_add after bns_build_finish");
+    if (s->minimizing) return fail(ctx, BNS_ERR_STATE, "bns_build_add after bns_build_minimize_begin: the scored table is frozen");
     if (n_seqs == 0) { s->added = true; ++s->n_batches; return BNS_OK; }
     if (!d_offsets || !d_taxid) return BNS_ERR_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));

@@ -855,13 +855,21 @@ Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &
     unsigned c = k;
     for (u16 g : gaps) c += g;
     const unsigned w = std::max<int>((int)c, std::max<int>(opt.wsz, (int)k));                 // bonsai.cpp:217 + spacer.h:61
-    const unsigned span = w > c ? w : c;
+    // -D (taxonomic-depth minimizers): pass A scores every k-mer (the window unset), pass B streams the same files again and selects
+    const unsigned w_enc = opt.taxdepth ? c : w;
+    const unsigned span = w_enc > c ? w_enc : c;
+    if (opt.taxdepth)                                                                          // (before any device is opened)
+        for (const std::string &path : paths) {
+            struct stat sb;
+            if (::stat(path.c_str(), &sb) != 0) die("Could not read from file " + path);
+            if (!S_ISREG(sb.st_mode)) die("-D reads every genome file twice: " + path + " is not a regular file");
+        }
 
     bns_ctx *ctx = nullptr;
     chk(nullptr, bns_create(opt.device, &ctx), "bns_create");
     struct Guard { bns_ctx *c; ~Guard() { bns_destroy(c); } } guard{ctx};
     chk(ctx, bns_set_encoder(ctx, k, gaps.data(), opt.canon ? 1 : 0, 1), "bns_set_encoder");
-    chk(ctx, bns_set_window(ctx, w, opt.entropy ? BNS_SCORE_ENTROPY_PATH : BNS_SCORE_LEX), "bns_set_window");
+    chk(ctx, bns_set_window(ctx, w_enc, opt.entropy && !opt.taxdepth ? BNS_SCORE_ENTROPY_PATH : BNS_SCORE_LEX), "bns_set_window");
     chk(ctx, bns_load_taxonomy(ctx, parent.data(), (u32)parent.size()), "bns_load_taxonomy");
 
     // The genome files go to the device's build session (bns_build_begin .. bns_build_end) in batches of whole sequences: this thread
@@ -869,58 +877,91 @@ Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &
     // batch; the table grows on the device as it must, and only the batch that did not fit is encoded again.
     u64 batch_bases = opt.batch_bases ? opt.batch_bases : 1;
     if (const char *e = std::getenv("BNS_BUILD_BATCH")) { const long long v = std::atoll(e); if (v > 0) batch_bases = (u64)v; }
-    BatchQueue q;
-    std::thread reader([&] { read_build_batches(paths, names, batch_bases, q); });
-    struct Join { BatchQueue &q; std::thread &t; ~Join() { q.abandon(); if (t.joinable()) t.join(); } } join{q, reader};
 
     GrowMem d_bases(ctx), d_off(ctx), d_tx(ctx);
-    bool begun = false;
-    BuildBatch b;
+    bool begun = false, begun_m = false;
+    u64 stats_a[6] = {0, 0, 0, 0, 0, 0}, mstats[6] = {0, 0, 0, 0, 0, 0};
     double t_wait = 0, t_upload = 0, t_finish = 0;                                             // seconds of this thread (BNS_CLI_TIMING)
-    for (;;) {
-        const double tw0 = tnow();
-        const bool more = q.pop(b);
-        t_wait += tnow() - tw0;
-        if (!more) break;
-        if (!begun) {
-            u64 upper = 0;                                                                     // emitted values of the first batch <= this
-            for (size_t i = 0; i + 1 < b.offsets.size(); ++i) {
-                const u64 L = b.offsets[i + 1] - b.offsets[i];
-                if (L >= span) upper += L - span + 1;
-                else if (L >= c) upper += 1;    // the emitted-stream modes (-C -w, real-entropy) flush one minimum for a sequence
-            }                                   // that never fills a window (encoder.h:304-305)
-            // windowed dbs keep roughly 2/(ws+1) of the positions; the session starts there and grows from it
-            const u64 ws = w - c + 1;
-            u64 hint = 4;
-            const u64 est = ws > 1 ? std::max<u64>(1024, upper * 3 / (ws + 1)) : upper;
-            while ((u64)(hint * 0.77 + 0.5) < est) hint <<= 1;
-            chk(ctx, bns_build_begin(ctx, hint), "bns_build_begin");
-            if (opt.seed)
-                chk(ctx, bns_build_seed(ctx, opt.seed->db_.n_buckets, opt.seed->db_.flags.data(), opt.seed->db_.keys.data(),
-                                        opt.seed->db_.vals.data()), "bns_build_seed");
-            begun = true;
+    // one pass over the files: bns_build_add of every batch, or (minimize) bns_build_minimize_add of every batch
+    auto stream_pass = [&](bool minimize) {
+        BatchQueue q;
+        std::thread reader([&] { read_build_batches(paths, names, batch_bases, q); });
+        struct Join { BatchQueue &q; std::thread &t; ~Join() { q.abandon(); if (t.joinable()) t.join(); } } join{q, reader};
+        BuildBatch b;
+        for (;;) {
+            const double tw0 = tnow();
+            const bool more = q.pop(b);
+            t_wait += tnow() - tw0;
+            if (!more) break;
+            if (!begun) {
+                u64 upper = 0;                                                                 // emitted values of the first batch <= this
+                for (size_t i = 0; i + 1 < b.offsets.size(); ++i) {
+                    const u64 L = b.offsets[i + 1] - b.offsets[i];
+                    if (L >= span) upper += L - span + 1;
+                    else if (L >= c) upper += 1;    // the emitted-stream modes (-C -w, real-entropy) flush one minimum for a sequence
+                }                                   // that never fills a window (encoder.h:304-305)
+                // windowed dbs keep roughly 2/(ws+1) of the positions; the session starts there and grows from it
+                const u64 ws = w_enc - c + 1;
+                u64 hint = 4;
+                const u64 est = ws > 1 ? std::max<u64>(1024, upper * 3 / (ws + 1)) : upper;
+                while ((u64)(hint * 0.77 + 0.5) < est) hint <<= 1;
+                chk(ctx, bns_build_begin(ctx, hint), "bns_build_begin");
+                if (opt.seed)
+                    chk(ctx, bns_build_seed(ctx, opt.seed->db_.n_buckets, opt.seed->db_.flags.data(), opt.seed->db_.keys.data(),
+                                            opt.seed->db_.vals.data()), "bns_build_seed");
+                begun = true;
+            }
+            if (minimize && !begun_m) {
+                // M starts from the first batch as the session table did: roughly 2/(ws+1) of its windows, and grows from there
+                u64 windows = 0;
+                for (size_t i = 0; i + 1 < b.offsets.size(); ++i) {
+                    const u64 L = b.offsets[i + 1] - b.offsets[i];
+                    if (L >= w) windows += L - w + 1;
+                }
+                const u64 ws = w - c + 1;
+                u64 hint = 4;
+                const u64 est = ws > 1 ? std::max<u64>(1024, windows * 3 / (ws + 1)) : stats_a[3];
+                while ((u64)(hint * 0.77 + 0.5) < est) hint <<= 1;
+                chk(ctx, bns_build_minimize_begin(ctx, w, hint), "bns_build_minimize_begin");
+                begun_m = true;
+            }
+            const u64 total = b.offsets.back();
+            b.bases.resize(b.bases.size() + 8, 'N');                                           // 4-byte readable tail
+            const double tu0 = tnow();
+            d_bases.ensure(b.bases.size()); d_off.ensure(b.offsets.size() * 8);
+            chk(ctx, bns_dev_upload(ctx, d_bases.p, b.bases.data(), b.bases.size()), "upload");
+            chk(ctx, bns_dev_upload(ctx, d_off.p, b.offsets.data(), b.offsets.size() * 8), "upload");
+            if (!minimize) {
+                d_tx.ensure(b.taxids.size() * 4);
+                chk(ctx, bns_dev_upload(ctx, d_tx.p, b.taxids.data(), b.taxids.size() * 4), "upload");
+            }
+            std::string().swap(b.bases);                                                       // (the device has them)
+            t_upload += tnow() - tu0;
+            if (minimize)
+                chk(ctx, bns_build_minimize_add(ctx, (const char *)d_bases.p, (const u64 *)d_off.p, b.taxids.size(), total, nullptr),
+                    "bns_build_minimize_add");
+            else
+                chk(ctx, bns_build_add(ctx, (const char *)d_bases.p, (const u64 *)d_off.p, b.taxids.size(), total, (const u32 *)d_tx.p, nullptr),
+                    "bns_build_add");
         }
-        const u64 total = b.offsets.back();
-        b.bases.resize(b.bases.size() + 8, 'N');                                               // 4-byte readable tail
-        const double tu0 = tnow();
-        d_bases.ensure(b.bases.size()); d_off.ensure(b.offsets.size() * 8); d_tx.ensure(b.taxids.size() * 4);
-        chk(ctx, bns_dev_upload(ctx, d_bases.p, b.bases.data(), b.bases.size()), "upload");
-        chk(ctx, bns_dev_upload(ctx, d_off.p, b.offsets.data(), b.offsets.size() * 8), "upload");
-        chk(ctx, bns_dev_upload(ctx, d_tx.p, b.taxids.data(), b.taxids.size() * 4), "upload");
-        std::string().swap(b.bases);                                                           // (the device has them)
-        t_upload += tnow() - tu0;
-        chk(ctx, bns_build_add(ctx, (const char *)d_bases.p, (const u64 *)d_off.p, b.taxids.size(), total, (const u32 *)d_tx.p, nullptr),
-            "bns_build_add");
-    }
-    q.rethrow();
+        q.rethrow();
+    };
+    stream_pass(false);
     if (!begun) die("Need input files from command line or file. See usage.");
+    if (opt.taxdepth) {
+        chk(ctx, bns_build_stats(ctx, stats_a), "bns_build_stats");
+        stream_pass(true);
+        if (!begun_m) chk(ctx, bns_build_minimize_begin(ctx, w, 0), "bns_build_minimize_begin");
+        chk(ctx, bns_build_minimize_stats(ctx, mstats), "bns_build_minimize_stats");
+    }
     d_bases.release(); d_off.release(); d_tx.release();
 
     Database db;
     u64 hdr[4] = {0, 0, 0, 0}, stats[6] = {0, 0, 0, 0, 0, 0};
     const double tf0 = tnow();
     chk(ctx, bns_build_finish(ctx, hdr), "bns_build_finish");
-    chk(ctx, bns_build_stats(ctx, stats), "bns_build_stats");
+    if (opt.taxdepth) std::memcpy(stats, stats_a, sizeof(stats));                              // (pass A's; the key count below is M's)
+    else chk(ctx, bns_build_stats(ctx, stats), "bns_build_stats");
     const u64 nb = hdr[0];
     db.k_ = k; db.w_ = w; db.s_ = gaps;
     db.db_.n_buckets = hdr[0]; db.db_.n_occupied = hdr[1]; db.db_.size = hdr[2]; db.db_.upper_bound = hdr[3];
@@ -933,6 +974,11 @@ Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &
                      t_wait, t_upload, (double)stats[4] * 1e-6, (double)stats[5] * 1e-6, t_finish);
         std::fprintf(stderr, "build: %llu batches, %llu grows, %llu seeded keys, %llu keys in %llu buckets\n", (unsigned long long)stats[0],
                      (unsigned long long)stats[1], (unsigned long long)stats[2], (unsigned long long)hdr[2], (unsigned long long)nb);
+        if (opt.taxdepth)
+            std::fprintf(stderr, "minimize: %llu batches, %llu grows, %llu scored keys, %llu lookups, %llu keys in %llu buckets\n",
+                         (unsigned long long)mstats[0], (unsigned long long)mstats[1], (unsigned long long)mstats[2], (unsigned long long)mstats[4],
+                         (unsigned long long)hdr[2], (unsigned long long)nb);
+        if (opt.taxdepth) std::fprintf(stderr, "[timing] minimize: add %.3f s\n", (double)mstats[5] * 1e-6);
     }
     return db;
 }

@@ -436,6 +436,8 @@ struct BuildOptions {
     spvec_t spacing;             // k-1 extra gaps (empty = contiguous)
     bool canon = true;
     bool entropy = false;        // -e: score::Entropy (path-overload rule) instead of score::Lex
+    bool taxdepth = false;       // -D: every window keeps the k-mer whose LCA over ALL genomes lies deepest in the taxonomy (DESIGN.md,
+                                 // "Defined behaviour"): the files are read twice, so every path must be a regular file; excludes entropy and seed
     int device = 0;
     u64 batch_bases = 1ULL << 30;   // -B: the genome files reach the device in batches of whole sequences of at most this many bases
                                     // (a longer sequence is a batch of its own); the environment's BNS_BUILD_BATCH overrides it

@@ -448,7 +448,9 @@ void build_usage(const char *exe)
                  "-A: Add to this db (old.bns[.gz]): the new db holds its keys and those of <paths>, as a build over all genomes would.\n"
                  "    k, w and the spacing are taken from the file; a -k, -w or -S that disagrees is an error.  A db records neither -C\n"
                  "    nor -e: repeat them as they were given when the db was built.  <out.path> may be the -A path itself.\n"
-                 "-t / -f (tax-depth / feature-count minimisation) are not provided by this build.\n", exe);
+                 "-D: Taxonomic-depth minimizers: every window of -w bases keeps the k-mer whose LCA over all genomes lies deepest in\n"
+                 "    the taxonomy (then the smaller taxid, then the smaller k-mer).  Reads every genome file twice; excludes -e and -A.\n"
+                 "-t / -f build the entropy-minimized map the reference builds for them; tax-depth minimisation is -D.\n", exe);
     std::exit(EXIT_FAILURE);
 }
 
@@ -459,9 +461,10 @@ int build_main(int argc, char *argv[])
     bool gz = false, k_given = false, w_given = false;
     int c;
     if (argc < 4) build_usage(argv[0]);
-    while ((c = getopt(argc, argv, "Cw:M:S:p:k:T:F:g:A:B:tefzHh?")) >= 0) {
+    while ((c = getopt(argc, argv, "Cw:M:S:p:k:T:F:g:A:B:DtefzHh?")) >= 0) {
         switch (c) {
             case 'C': opt.canon = false; break;
+            case 'D': opt.taxdepth = true; break;
             case 'k': opt.k = (unsigned)std::atoi(optarg); k_given = true; break;
             case 'w': opt.wsz = std::atoi(optarg); w_given = true; break;
             case 'A': add_path = optarg; break;
@@ -508,6 +511,11 @@ int build_main(int argc, char *argv[])
         if (seq2taxpath.empty()) throw bns::Error("seq2taxpath required for final database generation.");
         if (tax_path.empty()) throw bns::Error("Tax path required. [See -T option.]");
         if (opt.k < 1 || opt.k > 32) throw bns::Error("k must be in [1,32]");
+        if (opt.taxdepth && opt.entropy)
+            throw bns::Error("-D and -e exclude each other: a window keeps its k-mer by one score, taxonomic depth or entropy");
+        if (opt.taxdepth && !add_path.empty())
+            throw bns::Error("-D and -A exclude each other: tax-depth selection scores every k-mer of every genome, and a db does not hold "
+                             "the table of all k-mers it was selected from");
         // -A: k, w and the spacing are the file's; what the command line says about them must agree (checked before any device is opened)
         std::unique_ptr<bns::Database> old_db;
         if (!add_path.empty()) {

@@ -437,6 +437,33 @@ int bns_build_export(bns_ctx *ctx, uint32_t *flags, uint64_t *keys, uint32_t *va
 int bns_build_stats(const bns_ctx *ctx, uint64_t *out6);
 int bns_build_end(bns_ctx *ctx);
 
+/* ---- taxonomic-depth minimizers (version 111): the session's table thinned by the deepest LCA of every window -------------------
+ * A session that has added every sequence with the window unset holds F: every k-mer -> the lca() of all sequences holding it.
+ * Minimizing streams the SAME sequences a second time.  Sequence s of n bases has max(0, n - w + 1) windows; window p holds the
+ * k-mers that start at p .. p + w - c (c = the comb).  With depth(t) = nodes on the chain t -> root, root included (0 for
+ * 0xFFFFFFFF, for an id that is no node and for a chain that reaches no root) and score(x) = (0xFFFFFFFF - depth(F[x])) << 32 | F[x],
+ * a window selects, among its valid k-mers (every sampled base A/C/G/T in either case; a spaced all-T 32-mer is not valid), the one
+ * with the smallest (score, k-mer): the deeper LCA, then the smaller taxid, then the smaller k-mer.  A window without a valid
+ * k-mer and a sequence shorter than w select nothing; w <= c selects every valid k-mer.  The table M holds every selected k-mer
+ * with the value F holds for it; it is a function of the set of sequences, whatever the batches, their order and the sizes.
+ *   bns_build_minimize_begin  in an open, unfinished, unfailed session whose window is not beyond the comb (else BNS_ERR_STATE; a
+ *                             second begin too).  Refuses w > 1920 and w - c + 1 > 1024 (BNS_ERR_ARG).  Freezes F -- bns_build_add
+ *                             and bns_build_seed return BNS_ERR_STATE from here on --, computes the depth of every taxonomy node on
+ *                             the device and allocates M with max(4, n_buckets_hint rounded up to a power of two) buckets.
+ *   bns_build_minimize_add    bns_build_add's inputs without taxids.  One lookup in F per valid position and 2048-base chunk; M
+ *                             doubles as the session table does, and the same batch is applied again (idempotent).  A k-mer that F
+ *                             does not hold fails the call with BNS_ERR_TABLE ("not part of the scored build") and faults nothing.
+ *                             Returns when the device is done with the batch.  After a failed call only bns_build_end is accepted.
+ *   bns_build_minimize_stats  out6 = {batches, grows of M, keys in F, keys in M, positions looked up, microseconds inside add}.
+ * After bns_build_minimize_begin, bns_build_finish / bns_build_export act on M (khash's own size, flags, empty slots zeroed) and
+ * bns_build_stats' "keys in the table" counts M's; F is freed by bns_build_end.  Memory: 12 bytes a bucket for F and for M, 4 bytes a
+ * taxonomy node for the depths; a grow of M holds two copies of M beside F.  minimize_add before minimize_begin, and either after
+ * bns_build_finish or without a session, return BNS_ERR_STATE. */
+int bns_build_minimize_begin(bns_ctx *ctx, uint32_t w, uint64_t n_buckets_hint);
+int bns_build_minimize_add(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bases,
+                           void *stream);
+int bns_build_minimize_stats(const bns_ctx *ctx, uint64_t *out6);
+
 /* ---- window session (version 110): every window of L bases of every sequence, called as a read (`bonsai distrib`) -------------
  * With L = window_len, sequence s of n bases has max(0, n - L + 1) windows; window p is its bases [p, p + L).  The CALL of a window is
  * the taxon bns_classify_batch returns for that substring as a single unpaired read on this context -- its table layout, encoder
