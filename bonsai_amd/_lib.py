@@ -137,6 +137,7 @@ def load():
         "bns_build_minimize_add": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint64, vp]),
         "bns_build_minimize_stats": (C.c_int, [vp, u64p]),
         "bns_windows_begin": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
+        "bns_windows_begin_conf": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]),
         "bns_windows_add": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp, vp]),
         "bns_windows_read": (C.c_int, [vp, u32p, u32p, u64p, C.c_uint64, u64p, u64p, C.c_int]),
         "bns_windows_timing": (C.c_int, [vp, C.POINTER(C.c_double), u64p]),

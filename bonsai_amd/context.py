@@ -583,9 +583,12 @@ class Context:
         return d
 
     # ---- window session: every window of window_len bases of every sequence, called as classify calls a read
-    def windows_begin(self, window_len, pair_cap=1 << 20):
-        """opens a session; needs table, encoder and taxonomy, and no confidence threshold"""
-        self._chk(self.L.bns_windows_begin(self.h, int(window_len), int(pair_cap)), "bns_windows_begin")
+    def windows_begin(self, window_len, pair_cap=1 << 20, confidence=0):
+        """opens a session; needs table, encoder and taxonomy, and no confidence threshold on the context.  confidence (what
+        set_confidence takes) is the session's own threshold: every window is called as classify calls it as a read under
+        set_confidence(confidence); 0: none"""
+        num, den = confidence_fraction(confidence)
+        self._chk(self.L.bns_windows_begin_conf(self.h, int(window_len), int(pair_cap), num, den), "bns_windows_begin_conf")
 
     def windows_add(self, d_bases, d_offsets, n_seqs, total_bases, d_taxid, d_taxon=None, stream=None):
         """one batch of whole sequences (device arrays, as build_add takes them).  d_taxon (total_bases uint32, or None): the call of
@@ -611,8 +614,9 @@ class Context:
     def windows_end(self):
         self._chk(self.L.bns_windows_end(self.h), "bns_windows_end")
 
-    def classify_windows(self, bases, offsets, taxids, window_len, pair_cap=1 << 20):
-        """host arrays through one session of its own -> (d_taxon image uint32[total_bases], (seq_taxid, called, count, n_dropped))"""
+    def classify_windows(self, bases, offsets, taxids, window_len, pair_cap=1 << 20, confidence=0):
+        """host arrays through one session of its own (confidence: the session's threshold, as windows_begin takes it)
+        -> (d_taxon image uint32[total_bases], (seq_taxid, called, count, n_dropped))"""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         taxids = np.ascontiguousarray(taxids, dtype=np.uint32)
@@ -621,7 +625,7 @@ class Context:
             raise ValueError("one taxid per sequence, and the bases the offsets name")
         taxon = np.zeros(total, dtype=np.uint32)
         bufs = []
-        self.windows_begin(window_len, pair_cap)
+        self.windows_begin(window_len, pair_cap, confidence)
         try:
             for a in (bases[:total], offsets, taxids):
                 bufs.append(self.dev_alloc(a.nbytes + 8))           # (the bases are read up to 8 bytes past the end)

@@ -250,7 +250,7 @@ int ready(bns_ctx *ctx, bool need_table, bool need_tax)
 
 extern "C" {
 
-int bns_version(void) { return 111; }
+int bns_version(void) { return 112; }
 
 int bns_device_pci_bus_id(int device, char *out, int cap)
 {
@@ -1465,6 +1465,10 @@ int bns_build_end(bns_ctx *ctx)
 }
 
 int bns_windows_begin(bns_ctx *ctx, uint32_t window_len, uint32_t pair_cap) { return windows_begin(ctx, window_len, pair_cap); }
+int bns_windows_begin_conf(bns_ctx *ctx, uint32_t window_len, uint32_t pair_cap, uint64_t num, uint64_t den)
+{
+    return windows_begin(ctx, window_len, pair_cap, num, den);
+}
 int bns_windows_add(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bases,
                     const uint32_t *d_taxid, uint32_t *d_taxon, void *stream)
 {

@@ -23,6 +23,11 @@
 //                          Pair counts: the lanes of a step that carry the same call are counted with a ballot, equal calls of
 //                          consecutive steps are added up in scalars, and one atomicAdd of the sum goes to the pair table when the call
 //                          changes or the sequence's part of the tile ends.
+//                          CONF (a session opened by bns_windows_begin_conf with theta > 0): a second bitmap with running counts, of the
+//                          looked-up-and-missing k-mers, is staged beside the hits', so a window's Q = hits + missing is two more prefix
+//                          counts.  Two consecutive windows are one vote only when the hit range AND Q are equal (an N entering or leaving
+//                          among missing k-mers changes Q and nothing else), and a vote's call then walks up as confidence_kernel's does:
+//                          the first of T, parent(T), ... whose clade holds ceil(theta Q) of the hits hl[lo, hi), by Euler interval.
 //
 // The pair table: open addressing, linear probing, key = taxid << 32 | call claimed with a compare-and-swap, EMPTY = ~0 (taxid
 // 0xFFFFFFFF is BNS_TAX_ABSENT, no sequence's taxon: such a pair with call 0xFFFFFFFF counts as dropped).  A pair that meets no free
@@ -32,6 +37,7 @@
 #pragma once
 #include "bns_device.hpp"
 #include "bns_kernels.hpp"
+#include "bns_confidence.hpp"
 
 namespace bns {
 
@@ -41,6 +47,7 @@ constexpr u32 WIN_NONE = 0xFFFFFFFFu;               // d_taxon of a base that st
 constexpr u64 WIN_PAIR_EMPTY = ~0ULL;
 constexpr u32 WIN_CLS_MISSING = 1, WIN_CLS_HIT = 2;
 constexpr u32 WIN_LDS_LIST_MAX = 11264;             // entries of a tile + halo whose hit list is staged in LDS (45 KiB); longer: global
+constexpr u32 WIN_CONF_CACHED = 2;                  // blocks of 64 hits whose tin stays in registers across the steps of a window's walk
 // k-mer starts a lookup piece owns.  A piece starts anywhere in a sequence and reads the packed image from the 32-base word in front of
 // it: up to 31 k-mers it does not own, the ones it owns, c - 1 more bases -- within the 2048 bases one register image holds.
 __host__ __device__ constexpr u32 win_rounds_per_chunk(u32 c) { return (2048u - (c - 1u)) / 64u; }
@@ -231,24 +238,61 @@ __device__ __forceinline__ u32 win_resolve_range(const u32 *hl, u32 lo, u32 hi, 
     return resolve_wave(keys, cnt, tin, tout, D, nodes, n_nodes);
 }
 
+// The confidence walk of one vote (all arguments wave-uniform): t = the call of the hits hl[lo, hi), need = ceil(theta Q) of the window.
+// confidence_kernel's rules on the window's own hits: t stays when need = 0, t = 0 or t is no node whose chain reaches a root; 0 when
+// the window has fewer hits than need or the walk passes a root; else the first of t, parent(t), ... whose clade holds need hits.
+__device__ __forceinline__ u32 win_confidence(const u32 *hl, u32 lo, u32 hi, u64 need, u32 t, const TaxNode *__restrict__ nodes, u32 n_nodes)
+{
+    if (need == 0 || t == 0u) return t;
+    const TaxNode nt = load_node(nodes, n_nodes, t);
+    if (!(nt.flags & NODE_CHAIN_OK)) return t;
+    if ((u64)(hi - lo) < need) return 0u;                          // no clade can hold more hits than there are
+    const u32 lane = (u32)lane_id();
+    u32 ct[WIN_CONF_CACHED];
+#pragma unroll
+    for (u32 c = 0; c < WIN_CONF_CACHED; ++c) {
+        const u32 i = lo + c * 64u + lane;
+        ct[c] = i < hi ? load_node(nodes, n_nodes, hl[i]).tin : 0u;
+    }
+    u32 a = t, tin_a = nt.tin, tout_a = nt.tout, par_a = nt.parent;
+    for (u32 step = 0; step < n_nodes; ++step) {                   // (a chain that reaches a root is shorter than the taxonomy)
+        u64 cnt = 0;
+#pragma unroll
+        for (u32 c = 0; c < WIN_CONF_CACHED; ++c) cnt += (u64)__popcll(ballot64(conf_in_clade(ct[c], tin_a, tout_a)));
+        for (u32 i0 = lo + WIN_CONF_CACHED * 64u; i0 < hi && cnt < need; i0 += 64u) {
+            const u32 i = i0 + lane;
+            const u32 th = i < hi ? load_node(nodes, n_nodes, hl[i]).tin : 0u;
+            cnt += (u64)__popcll(ballot64(conf_in_clade(th, tin_a, tout_a)));
+        }
+        if (cnt >= need) return a;
+        if (par_a == 0u) return 0u;                                // passed the root: unclassified
+        const TaxNode np = load_node(nodes, n_nodes, par_a);
+        a = par_a; tin_a = np.tin; tout_a = np.tout; par_a = np.parent;
+    }
+    return 0u;
+}
+
 // hits in front of tile position x: the running count of its 64-position word plus the bits below it
 __device__ __forceinline__ u32 win_rank(const u64 *bits, const u32 *wpre, u32 x)
 {
     return wpre[x >> 6] + (u32)__popcll(bits[x >> 6] & ((1ULL << (x & 63u)) - 1ULL));
 }
 
-template <bool GL>
-__global__ __launch_bounds__(64) void windows_vote_kernel(WindowParams wp, const TaxNode *__restrict__ nodes, u32 n_nodes, u32 c)
+// CONF: the session has a threshold theta = num / den > 0 of its own (the form without one is the code it was before there was one)
+template <bool GL, bool CONF = false>
+__global__ __launch_bounds__(64) void windows_vote_kernel(WindowParams wp, const TaxNode *__restrict__ nodes, u32 n_nodes, u32 c, u64 num, u64 den)
 {
     extern __shared__ __attribute__((aligned(16))) u64 s_dyn[];
     const u32 lane = (u32)lane_id();
     const u32 L = wp.L, H = L - c;                                 // a window holds the k-mers at its start .. start + H
     const u32 n_bw = (wp.list_cap >> 6) + 2u;                      // bitmap words: one past the last position's, for rank(np)
     u64 *bits = s_dyn;
-    u32 *wpre = reinterpret_cast<u32 *>(s_dyn + n_bw);
+    u64 *mbits = s_dyn + n_bw;                                     // CONF: the missing k-mers' bitmap and running counts
+    u32 *wpre = reinterpret_cast<u32 *>(s_dyn + (CONF ? 2u : 1u) * n_bw);
+    u32 *mpre = wpre + n_bw;
     u32 *scr = wp.scratch + (u64)blockIdx.x * wp.scratch_stride;
     u32 *keys = scr, *cnt = scr + wp.counter_cap, *tin = scr + 2u * (u64)wp.counter_cap, *tout = scr + 3u * (u64)wp.counter_cap;
-    u32 *hl = GL ? scr + 4u * (u64)wp.counter_cap : wpre + n_bw;
+    u32 *hl = GL ? scr + 4u * (u64)wp.counter_cap : wpre + (CONF ? 2u : 1u) * n_bw;
     const u64 n_tiles = (wp.total_bases + WIN_TILE - 1) / WIN_TILE;
     for (u64 g = blockIdx.x; g < n_tiles; g += gridDim.x) {
         const u64 g0 = g * WIN_TILE, g1 = g0 + WIN_TILE < wp.total_bases ? g0 + WIN_TILE : wp.total_bases;
@@ -263,10 +307,17 @@ __global__ __launch_bounds__(64) void windows_vote_kernel(WindowParams wp, const
             const u32 n_win = p_hi - p_lo, np = n_win + H;         // np <= WIN_TILE + H = list_cap stream positions, all of them k-mer starts
             const u64 at = o + p_lo;
             __builtin_amdgcn_wave_barrier();                       // (the previous part's readers are done)
-            u32 n_hits = 0;
+            u32 n_hits = 0, n_miss = 0;
             for (u32 base = 0; base < np + 1u; base += 64u) {      // (+ 1: the word rank(np) reads exists and is complete)
                 const u32 i = base + lane;
-                const bool hit = i < np && wp.cls[at + i] == WIN_CLS_HIT;
+                bool hit;
+                if constexpr (CONF) {
+                    const u32 cl = i < np ? (u32)wp.cls[at + i] : 0u;
+                    hit = cl == WIN_CLS_HIT;
+                    const u64 mm = ballot64(cl == WIN_CLS_MISSING);
+                    if (lane == 0) { mbits[base >> 6] = mm; mpre[base >> 6] = n_miss; }
+                    n_miss += (u32)__popcll(mm);
+                } else hit = i < np && wp.cls[at + i] == WIN_CLS_HIT;
                 const u64 hm = ballot64(hit);
                 if (lane == 0) { bits[base >> 6] = hm; wpre[base >> 6] = n_hits; }
                 if (hit) hl[n_hits + (u32)__popcll(hm & lanemask_lt())] = wp.vals[at + i];
@@ -276,7 +327,7 @@ __global__ __launch_bounds__(64) void windows_vote_kernel(WindowParams wp, const
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             const u32 taxid = wp.taxid[s];
-            u32 c_lo = 0, c_hi = 0, c_tax = 0;                     // the range and call of the window in front of the step
+            u32 c_lo = 0, c_hi = 0, c_tax = 0, c_q = 0;            // the range, call (and Q) of the window in front of the step
             bool c_have = false;
             u32 pend_call = 0, pend_n = 0;                         // windows counted and not yet in the pair table
             for (u32 base = 0; base < n_win; base += 64u) {
@@ -286,16 +337,26 @@ __global__ __launch_bounds__(64) void windows_vote_kernel(WindowParams wp, const
                 u32 plo = (u32)__shfl_up((int)lo, 1, 64), phi = (u32)__shfl_up((int)hi, 1, 64);
                 bool head = act && (lo != plo || hi != phi);
                 if (lane == 0) head = !c_have || lo != c_lo || hi != c_hi;
+                u32 q = 0;                                         // CONF: the window's Q = hits + missing, and R = ceil(theta Q)
+                u64 need = 0;
+                if constexpr (CONF) {
+                    q = act ? (hi - lo) + win_rank(mbits, mpre, i + H + 1u) - win_rank(mbits, mpre, i) : 0u;
+                    const u32 pq = (u32)__shfl_up((int)q, 1, 64);
+                    head = head || (act && q != (lane == 0 ? c_q : pq));
+                    need = act ? conf_required(num, den, (u64)q) : 0ULL;
+                }
                 u64 heads = ballot64(head);
                 u32 tx = c_tax;
                 while (heads) {
                     const int l = __builtin_ctzll(heads);
                     heads &= heads - 1;
-                    const u32 t = win_resolve_range(hl, readlane(lo, l), readlane(hi, l), keys, cnt, tin, tout, wp.counter_cap, nodes, n_nodes);
+                    u32 t = win_resolve_range(hl, readlane(lo, l), readlane(hi, l), keys, cnt, tin, tout, wp.counter_cap, nodes, n_nodes);
+                    if constexpr (CONF) t = win_confidence(hl, readlane(lo, l), readlane(hi, l), readlane64(need, l), t, nodes, n_nodes);
                     tx = lane >= (u32)l ? t : tx;                  // (the lanes from the next head on are overwritten by it)
                 }
                 const int last = (int)((n_win - base < 64u ? n_win - base : 64u) - 1u);
                 c_lo = readlane(lo, last); c_hi = readlane(hi, last); c_tax = readlane(tx, last); c_have = true;
+                if constexpr (CONF) c_q = readlane(q, last);
                 if (act && wp.taxon) wp.taxon[at + i] = tx;
                 u64 rem = ballot64(act);
                 while (rem) {
@@ -324,6 +385,7 @@ __global__ __launch_bounds__(256) void windows_pair_clear_kernel(u64 *__restrict
 // The session: window length, the pair table, and the positional stream of the batch in flight (grow-only).
 struct WindowSession {
     u32 L = 0;
+    u64 conf_num = 0, conf_den = 1;                  // the session's own threshold (bns_windows_begin_conf); 0: none
     u64 pair_cap = 0;
     u64 *pair_keys = nullptr, *pair_counts = nullptr;
     unsigned long long *dropped = nullptr;
@@ -375,16 +437,17 @@ int windows_ready(bns_ctx *ctx, u32 L)
 {
     int rc = ready(ctx, true, true);
     if (rc != BNS_OK) return rc;
-    if (ctx->conf_num) return fail(ctx, BNS_ERR_STATE, "window session: a confidence threshold is set (bns_set_confidence); windows are called without one");
+    if (ctx->conf_num) return fail(ctx, BNS_ERR_STATE, "window session: a confidence threshold is set on the context (bns_set_confidence); a session takes its own (bns_windows_begin_conf)");
     if (win_rounds_per_chunk(ctx->c) < 2u) return fail(ctx, BNS_ERR_ARG, "window session: the seed spans more than 1921 bases");
     if (L < ctx->c) return fail(ctx, BNS_ERR_ARG, "window_len is shorter than the seed (" + std::to_string(ctx->c) + " bases)");
     if ((u64)L - ctx->c + 1 > 65535) return fail(ctx, BNS_ERR_ARG, "window_len - seed span + 1 exceeds 65535 k-mers (the vote's counts are 16 bits wide)");
     return BNS_OK;
 }
 
-int windows_begin(bns_ctx *ctx, u32 window_len, u32 pair_cap)
+int windows_begin(bns_ctx *ctx, u32 window_len, u32 pair_cap, u64 num = 0, u64 den = 1)
 {
     if (!ctx) return BNS_ERR_ARG;
+    if (den == 0 || num > den) return fail(ctx, BNS_ERR_ARG, "confidence num / den: den > 0 and num <= den");
     if (ctx->windows) return fail(ctx, BNS_ERR_STATE, "a window session is already open (bns_windows_end)");
     int rc = windows_ready(ctx, window_len);
     if (rc != BNS_OK) return rc;
@@ -394,6 +457,8 @@ int windows_begin(bns_ctx *ctx, u32 window_len, u32 pair_cap)
     if (!w) return BNS_ERR_NOMEM;
     ctx->windows = w;
     w->L = window_len;
+    const u64 g = num ? std::gcd(num, den) : 1;      // (bns_set_confidence's lowest terms; the session's theta, never the context's)
+    w->conf_num = num / g; w->conf_den = num ? den / g : 1;
     w->pair_cap = 1;
     while (w->pair_cap < pair_cap) w->pair_cap <<= 1;
     hipError_t e = hipMalloc((void **)&w->pair_keys, (size_t)w->pair_cap * 8);
@@ -473,9 +538,14 @@ int windows_add(bns_ctx *ctx, const char *d_bases, const u64 *d_offsets, u64 n_s
     HIPCHK(ctx, hipGetLastError());
     if (timed) HIPCHK(ctx, hipEventRecord(w->ev[2], st));
     const u32 n_bw = (wp.list_cap >> 6) + 2u;
-    const size_t lds = (size_t)n_bw * 12 + (gl ? 0 : (size_t)wp.list_cap * 4);
-    if (gl) hipLaunchKernelGGL((windows_vote_kernel<true>), dim3((unsigned)vgrid), dim3(64), lds, st, wp, (const TaxNode *)ctx->nodes, ctx->n_nodes, ctx->c);
-    else    hipLaunchKernelGGL((windows_vote_kernel<false>), dim3((unsigned)vgrid), dim3(64), lds, st, wp, (const TaxNode *)ctx->nodes, ctx->n_nodes, ctx->c);
+    const bool conf = w->conf_num != 0;                      // (a second bitmap with its running counts)
+    const size_t lds = (size_t)n_bw * (conf ? 24 : 12) + (gl ? 0 : (size_t)wp.list_cap * 4);
+    const TaxNode *nodes = (const TaxNode *)ctx->nodes;
+    const u64 num = w->conf_num, den = w->conf_den;
+    if (conf && gl) hipLaunchKernelGGL((windows_vote_kernel<true, true>), dim3((unsigned)vgrid), dim3(64), lds, st, wp, nodes, ctx->n_nodes, ctx->c, num, den);
+    else if (conf)  hipLaunchKernelGGL((windows_vote_kernel<false, true>), dim3((unsigned)vgrid), dim3(64), lds, st, wp, nodes, ctx->n_nodes, ctx->c, num, den);
+    else if (gl)    hipLaunchKernelGGL((windows_vote_kernel<true>), dim3((unsigned)vgrid), dim3(64), lds, st, wp, nodes, ctx->n_nodes, ctx->c, num, den);
+    else            hipLaunchKernelGGL((windows_vote_kernel<false>), dim3((unsigned)vgrid), dim3(64), lds, st, wp, nodes, ctx->n_nodes, ctx->c, num, den);
     HIPCHK(ctx, hipGetLastError());
     if (timed) {                                             // (a timed add waits for its batch)
         HIPCHK(ctx, hipEventRecord(w->ev[3], st));

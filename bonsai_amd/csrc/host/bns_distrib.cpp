@@ -1,5 +1,5 @@
 // bns_distrib.cpp -- `bonsai distrib`: every window of read length of every genome, called by the loaded db on the device (the window
-// session of the device library, bns_windows_begin ..), and the per-genome distribution of those calls as a text file.
+// session of the device library, bns_windows_begin_conf ..: `-t` is the session's threshold), and the per-genome distribution of those calls as a text file.
 #include "bns_host_internal.hpp"
 
 namespace bns {
@@ -29,7 +29,7 @@ void write_distrib(ClassifierGeneric &c, const std::vector<std::string> &paths, 
 {
     const auto names = build_name_hash(seq2tax_path);
     bns_ctx *ctx = c.ctx_;
-    chk(ctx, bns_windows_begin(ctx, opt.window_len, opt.pair_cap), "bns_windows_begin");
+    chk(ctx, bns_windows_begin_conf(ctx, opt.window_len, opt.pair_cap, opt.conf_num, opt.conf_den), "bns_windows_begin_conf");
     struct End { bns_ctx *c; ~End() { bns_windows_end(c); } } end{ctx};
 
     BatchQueue q;

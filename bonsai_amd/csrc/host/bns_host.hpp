@@ -84,6 +84,9 @@ std::vector<u32> build_parent_map(const char *nodes_dmp);
 // nodes.dmp's third field ("rank") per taxid, indexed like build_parent_map's array; "no rank" where a line has no such field, "" for
 // an id without a line
 std::vector<std::string> read_node_ranks(const char *nodes_dmp);
+// Kraken 2's rank letters (the report's rank-to-letter rule): superkingdom / domain D, kingdom K, phylum P, class C, order O, family F,
+// genus G, species S; "" for a rank without one
+const char *rank_letter(const std::string &rank);
 // names.dmp's "scientific name" rows: taxid -> name (the first row of a taxid)
 std::unordered_map<u32, std::string> read_scientific_names(const char *names_dmp);
 // Kraken 2's standard report layout from the device tally (bns_tally_read): direct / clade have n + 1 entries -- bin 0 unclassified, bin n
@@ -462,12 +465,39 @@ Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &
 std::string format_distrib(const u32 *seq_taxid, const u32 *called, const u64 *count, u64 n_pairs);
 struct DistribOptions {
     unsigned window_len = 150;      // -l
+    u64 conf_num = 0, conf_den = 1; // -t: the session's confidence threshold, exactly as `classify -t` parses it (0: none)
     u32 pair_cap = 1u << 20;        // -P: slots of the session's pair table
     u64 batch_bases = 1ULL << 30;   // -B: as BuildOptions::batch_bases (windows never span sequences: the output does not depend on it)
 };
 // The genome files (taxids by get_taxid, as `bonsai build` maps them) through one window session on the classifier's first context:
 // this thread uploads and adds batch n while a second one reads batch n + 1.  Pairs that found no slot are an error.
 void write_distrib(ClassifierGeneric &c, const std::vector<std::string> &paths, const char *seq2tax_path, const DistribOptions &opt, std::FILE *out);
+
+// ---- `bonsai abundance` (bns_abundance.cpp): the reads of a `classify -R` report re-estimated at one level; no device ----------
+// The project's own definition (DESIGN "Defined behaviour"), after Bracken's re-estimation as recalled, not checked against Bracken.
+//   report   what `classify -R` writes, 6, 7 or 9 tab-separated fields a line, read from the right: name, taxid, rank code; the direct
+//            count is the third field.  Taxid 0 is "unclassified", taxid 4294967295 "(not in taxonomy)": neither is distributed.
+//   distrib  format_distrib's text; ancestry from parent[] (build_parent_map), levels from ranks[] (read_node_ranks) through rank_letter:
+//            a node is AT the level when its own rank maps to the letter (a strain, code S1, is below the level S).
+// lvl(t) = the first of t, parent(t), ... at the level, or none.  S ranges over lvl(t) of the taxa t with direct reads;
+// base[S] = the sum of direct[t] over t with lvl(t) = S; S is kept iff base[S] >= min_reads, else its reads are discarded.  Every
+// other taxon N with direct reads (lvl(N) = none) takes its distrib line's entries g:w:W: weight[S] += (w / W) base[S] for S = lvl(g)
+// kept; without a line or with a weight sum of 0 its reads are not distributed; else added[S] += direct[N] weight[S] / sum.
+// new_est[S] = base[S] + added[S].  Doubles; genomes in ascending taxid, then N in ascending taxid.
+// Text: "name\ttaxonomy_id\ttaxonomy_lvl\tkraken_assigned_reads\tadded_reads\tnew_est_reads\tfraction_total_reads\n", then a line per kept
+// S ascending: name (names, else the decimal id), id, the level letter, base, added and new_est as %.3f, new_est / sum of new_est as
+// %.6f (0.000000 when the sum is 0).  totals[5] = all reads, unclassified + not in taxonomy, discarded below min_reads, not distributed,
+// sum of new_est (the first is the sum of the other four).  A malformed line of either file is an Error that names the line.
+struct AbundanceOptions {
+    char level = 'S';               // -l: one of D K P C O F G S
+    u64 min_reads = 10;             // -T
+};
+std::string estimate_abundance(const std::string &distrib_text, const std::string &report_text, const std::vector<u32> &parent,
+                               const std::vector<std::string> &ranks, const std::unordered_map<u32, std::string> &names,
+                               const AbundanceOptions &opt, double totals[5]);
+// ... from the files (names_dmp may be null)
+std::string estimate_abundance_files(const char *distrib_path, const char *report_path, const char *nodes_dmp, const char *names_dmp,
+                                     const AbundanceOptions &opt, double totals[5]);
 
 // ---- Encoder API surface (encoder.h:415-442, 448-530) -----------------------------------------------------
 // Synchronous, in sequence order, on the calling thread -- like the reference; the k-mers come from the GPU encoder.

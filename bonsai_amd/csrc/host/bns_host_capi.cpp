@@ -296,6 +296,20 @@ int bnsh_write_distrib(const uint32_t *seq_taxid, const uint32_t *called, const 
     });
 }
 
+// estimate_abundance_files: the text of `bonsai abundance`, malloc'd in *out (*out_bytes bytes, NUL-terminated), and its five totals
+int bnsh_estimate_abundance(const char *distrib_path, const char *report_path, const char *nodes_dmp, const char *names_dmp, char level,
+                            uint64_t min_reads, char **out, uint64_t *out_bytes, double *totals5)
+{
+    return guard([&] {
+        AbundanceOptions opt;
+        opt.level = level; opt.min_reads = min_reads;
+        const std::string s = estimate_abundance_files(distrib_path, report_path, nodes_dmp, names_dmp, opt, totals5);
+        *out = static_cast<char *>(std::malloc(s.size() + 1));
+        std::memcpy(*out, s.c_str(), s.size() + 1);
+        *out_bytes = s.size();
+    });
+}
+
 // hll_estimate of 4096 one-byte registers
 uint64_t bnsh_hll_estimate(const uint8_t *reg) { return reg ? hll_estimate(reg) : 0; }
 

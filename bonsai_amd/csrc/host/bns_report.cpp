@@ -32,7 +32,8 @@ std::vector<std::string_view> dmp_fields(std::string_view line)
     return f;
 }
 
-// Kraken 2's rank letters; "" for a rank without one
+}  // namespace
+
 const char *rank_letter(const std::string &r)
 {
     if (r == "superkingdom" || r == "domain") return "D";
@@ -45,6 +46,8 @@ const char *rank_letter(const std::string &r)
     if (r == "species") return "S";
     return "";
 }
+
+namespace {
 
 // distinct: the extra column of the `-u` report (nullptr: the seven-column line); db_keys: the two columns `-d` puts behind it, the
 // clade's key count in the db and distinct / db_keys (not clamped: the numerator is an estimate), 0.000000 where the db holds none

@@ -364,11 +364,14 @@ int inspect_main(int argc, char *argv[])
 int distrib_main(int argc, char *argv[])
 {
     auto distrib_usage = [&]() {
-        std::fprintf(stderr, "Usage: %s distrib [-l window length: 150] [-g device] [-L minbucket|bucket|khash] [-C: do not canonicalize]\n"
+        std::fprintf(stderr, "Usage: %s distrib [-l window length: 150] [-t confidence threshold: 0] [-g device] [-L minbucket|bucket|khash]\n"
+                             "       [-C: do not canonicalize]\n"
                              "       [-B bases per batch] [-P pairs: slots of the (genome taxid, called taxid) table: 1048576] -M seq2tax [-F paths file]\n"
                              "       [-o file] <dbpath> <tax_path> <genome paths...>\n"
                              "Writes 'mapped_taxid<TAB>genome_taxids:kmers_mapped:total_genome_kmers', then a line per called taxid: the genomes with\n"
-                             "windows called there, as <genome taxid>:<windows called here>:<all windows of the genome>.\n", argv[0]);
+                             "windows called there, as <genome taxid>:<windows called here>:<all windows of the genome>.\n"
+                             "-t: every window is called as `classify -t` calls it as a read: a decimal in [0, 1] with at most 9 digits after the\n"
+                             "    point.  Give the -t (and as -l the read length) of the classify run whose report is to be re-estimated.\n", argv[0]);
         return EXIT_FAILURE;
     };
     int co, device = 0, layout = BNS_LAYOUT_MINBUCKET;
@@ -376,8 +379,17 @@ int distrib_main(int argc, char *argv[])
     bns::DistribOptions opt;
     std::string seq2taxpath, paths_file;
     const char *out_path = nullptr;
-    while ((co = getopt(argc, argv, "l:g:L:CB:P:M:F:o:h?")) >= 0) {
+    while ((co = getopt(argc, argv, "l:t:g:L:CB:P:M:F:o:h?")) >= 0) {
         switch (co) {
+            case 't': {
+                unsigned long long num = 0, den = 1;
+                if (!parse_confidence(optarg, num, den)) {
+                    std::fprintf(stderr, "[E] -t: the confidence threshold must be a decimal in [0, 1] with at most 9 digits after the point, not '%s'\n", optarg);
+                    return distrib_usage();
+                }
+                opt.conf_num = num; opt.conf_den = den;
+                break;
+            }
             case 'l': { const long long v = std::atoll(optarg); if (v < 1 || v > 0xFFFFFFFFLL) return distrib_usage(); opt.window_len = (unsigned)v; } break;
             case 'g': device = std::atoi(optarg); break;
             case 'C': canon = false; break;
@@ -430,6 +442,57 @@ int distrib_main(int argc, char *argv[])
         return EXIT_FAILURE;
     }
     if (ofp != stdout && std::fclose(ofp) != 0) { std::fprintf(stderr, "[E] Could not write the window distribution\n"); return EXIT_FAILURE; }
+    return EXIT_SUCCESS;
+}
+
+// `bonsai abundance`: a `classify -R` report re-estimated at one level with the `distrib` file of the same db, read length and -t.
+// Host code only: no device is opened.
+int abundance_main(int argc, char *argv[])
+{
+    auto abundance_usage = [&]() {
+        std::fprintf(stderr, "Usage: bonsai abundance [-l D|K|P|C|O|F|G|S: S] [-T min reads: 10] [-n names.dmp] [-o file] <distrib_file> <report_file> <nodes.dmp>\n"
+                             "Re-estimates the reads of a `classify -R` report at one level: a taxon at the level (or below it) keeps its reads, the\n"
+                             "reads of a taxon above it go to the level's taxa in proportion to how the db calls their genomes' windows there\n"
+                             "(`distrib`, run with the -l read length and the -t of the classify run) times the reads those taxa already have.\n"
+                             "-T: a taxon at the level with fewer reads is dropped and its reads are discarded.\n"
+                             "Writes name, taxonomy_id, taxonomy_lvl, kraken_assigned_reads, added_reads, new_est_reads, fraction_total_reads;\n"
+                             "five totals go to stderr.\n");
+        return EXIT_FAILURE;
+    };
+    int co;
+    bns::AbundanceOptions opt;
+    const char *names_path = nullptr, *out_path = nullptr;
+    while ((co = getopt(argc, argv, "l:T:n:o:h?")) >= 0) {
+        switch (co) {
+            case 'l': if (std::strlen(optarg) != 1 || !std::strchr("DKPCOFGS", optarg[0])) return abundance_usage(); opt.level = optarg[0]; break;
+            case 'T': {
+                char *end = nullptr;
+                const long long v = std::strtoll(optarg, &end, 10);
+                if (!*optarg || *end || v < 0) return abundance_usage();
+                opt.min_reads = (bns::u64)v;
+                break;
+            }
+            case 'n': names_path = optarg; break;
+            case 'o': out_path = optarg; break;
+            default: return abundance_usage();
+        }
+    }
+    if (argc - optind != 3) return abundance_usage();
+    std::FILE *ofp = nullptr;
+    try {
+        double totals[5];
+        const std::string text = bns::estimate_abundance_files(argv[optind], argv[optind + 1], argv[optind + 2], names_path, opt, totals);
+        ofp = out_path ? std::fopen(out_path, "w") : stdout;
+        if (!ofp) throw bns::Error("Could not open output file");
+        if (std::fwrite(text.data(), 1, text.size(), ofp) != text.size()) throw bns::Error("Could not write the abundance table");
+        std::fprintf(stderr, "reads: %.0f\nunclassified or not in the taxonomy: %.0f\ndiscarded below -T: %.0f\nnot distributed: %.0f\n"
+                             "estimated at level %c: %.3f\n", totals[0], totals[1], totals[2], totals[3], opt.level, totals[4]);
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "[E] %s\n", e.what());
+        if (ofp && ofp != stdout) { std::fclose(ofp); std::remove(out_path); }
+        return EXIT_FAILURE;
+    }
+    if (ofp != stdout && std::fclose(ofp) != 0) { std::fprintf(stderr, "[E] Could not write the abundance table\n"); return EXIT_FAILURE; }
     return EXIT_SUCCESS;
 }
 
@@ -580,12 +643,14 @@ int main(int argc, char *argv[])
     if (argc > 1 && std::strcmp(argv[1], "pack") == 0) return leave(pack_main(argc - 1, argv + 1));
     if (argc > 1 && std::strcmp(argv[1], "inspect") == 0) return leave(inspect_main(argc - 1, argv + 1));
     if (argc > 1 && std::strcmp(argv[1], "distrib") == 0) return leave(distrib_main(argc - 1, argv + 1));
-    std::fprintf(stderr, "Usage: %s <classify|build|pack|inspect|distrib> ...\n"
+    if (argc > 1 && std::strcmp(argv[1], "abundance") == 0) return leave(abundance_main(argc - 1, argv + 1));
+    std::fprintf(stderr, "Usage: %s <classify|build|pack|inspect|distrib|abundance> ...\n"
                          "  classify <opts> <dbpath> <tax_path> <inr1.fq> [<inr2.fq>]\n"
                          "  build    <opts> <out.path> <ignored> <genome paths>\n"
                          "  pack     -o <out.bnsp> <in1.fq> [<in2.fq>]      (reads -> 2-bit container for classify)\n"
                          "  inspect  <opts> <dbpath> <tax_path>             (the db's keys per taxon, in the layout of classify -R)\n"
                          "  distrib  <opts> <dbpath> <tax_path> <genome paths>  (how the db calls every read-length window of every genome)\n"
+                         "  abundance <opts> <distrib_file> <report_file> <nodes.dmp>  (a classify -R report re-estimated at one level)\n"
                          "Other reference subcommands (prebuild, hist, metatree) are out of scope (DESIGN.md).\n", argv[0]);
     return EXIT_FAILURE;
 }

@@ -67,6 +67,9 @@ def lib():
         L.bnsh_format_distrib.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.bnsh_write_distrib.restype = C.c_int
         L.bnsh_write_distrib.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p]
+        L.bnsh_estimate_abundance.restype = C.c_int
+        L.bnsh_estimate_abundance.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char, C.c_uint64, C.POINTER(C.c_void_p),
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -121,6 +124,23 @@ def format_distrib(seq_taxid, called, count, path=None):
     if lib().bnsh_format_distrib(s.ctypes.data, t.ctypes.data, n.ctypes.data, s.size, C.byref(out), C.byref(ob)) != 0:
         raise HostIOError(lib().bnsh_last_error().decode())
     return _take_blob(out, ob.value).decode()
+
+
+ABUNDANCE_TOTALS = ("all", "unclassified", "discarded", "not_distributed", "estimated")
+
+
+def estimate_abundance(distrib_path, report_path, nodes_dmp, names_dmp=None, level="S", min_reads=10):
+    """`bonsai abundance` (bns::estimate_abundance_files): the reads of a `classify -R` report re-estimated at `level` (one of D K P C
+    O F G S) with the `bonsai distrib` file of the same db, read length and threshold -> (text, totals): the table and a dict of the
+    five totals (all reads, unclassified + not in taxonomy, discarded below min_reads, not distributed, the sum of new_est_reads)"""
+    if not (isinstance(level, str) and len(level) == 1):
+        raise ValueError("level is one letter")
+    out, ob, totals = C.c_void_p(), C.c_uint64(), (C.c_double * 5)()
+    if lib().bnsh_estimate_abundance(str(distrib_path).encode(), str(report_path).encode(), str(nodes_dmp).encode(),
+                                     str(names_dmp).encode() if names_dmp else None, level.encode(), int(min_reads), C.byref(out),
+                                     C.byref(ob), totals) != 0:
+        raise HostIOError(lib().bnsh_last_error().decode())
+    return _take_blob(out, ob.value).decode(), dict(zip(ABUNDANCE_TOTALS, (float(x) for x in totals)))
 
 
 def format_report(direct, clade, parent, ranks=None, names=None, sketch_bins=None, sketch_registers=None, db_keys=None):

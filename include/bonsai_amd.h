@@ -474,6 +474,16 @@ int bns_build_minimize_stats(const bns_ctx *ctx, uint64_t *out6);
  *                      window_len - c + 1 <= 65535 (the vote's counts are 16 bits wide, as the reference's: inside the bound none can
  *                      wrap), else BNS_ERR_ARG.  pair_cap slots of the pair table, rounded up to a power of two; 0: BNS_ERR_ARG.  The
  *                      table starts empty.
+ *   bns_windows_begin_conf (version 112)  bns_windows_begin with a confidence threshold theta = num / den that belongs to the SESSION
+ *                      (argument rules of bns_set_confidence: den == 0 or num > den is BNS_ERR_ARG; num == 0 opens exactly the
+ *                      session bns_windows_begin opens).  The call of a window is then the taxon bns_classify_batch returns for that
+ *                      substring with bns_set_confidence(num, den) on, bit for bit: Q = the window's hits + looked-up-and-missing
+ *                      k-mers (k-mers over an N do not enter, as `ambig` does not in classify), R = ceil(theta Q) exactly, and the
+ *                      call T becomes the first of T, parent(T), ... whose clade (Euler interval, counted exactly) holds >= R of the
+ *                      window's hits; 0 when hits < R or the walk passes a root; T stays when R = 0, T = 0 or T is no node whose chain
+ *                      reaches a root.  Pair table, d_taxon image, n_dropped and bns_windows_read are as without a threshold; the walk
+ *                      is part of the vote stage of bns_windows_timing.  The context's own threshold (bns_set_confidence) is never
+ *                      inherited and, while on, still makes begin, begin_conf and add return BNS_ERR_STATE.
  *   bns_windows_add    one batch of whole sequences, bns_build_add's inputs (device arrays; n_seqs + 1 offsets, the bases readable
  *                      8 bytes past the end, a taxid per sequence).  d_taxon may be NULL; else it has total_bases entries: the call of
  *                      window p of sequence s goes to d_taxon[offsets[s] + p] (the convention of `hits`), and every base that starts no
@@ -496,6 +506,7 @@ int bns_build_minimize_stats(const bns_ctx *ctx, uint64_t *out6);
  * bns_tally_enable tally and the sketches are not touched (as with bns_resolve_batch).  Without a session nothing is allocated or
  * launched. */
 int bns_windows_begin(bns_ctx *ctx, uint32_t window_len, uint32_t pair_cap);
+int bns_windows_begin_conf(bns_ctx *ctx, uint32_t window_len, uint32_t pair_cap, uint64_t num, uint64_t den);
 int bns_windows_add(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bases,
                     const uint32_t *d_taxid, uint32_t *d_taxon, void *stream);
 int bns_windows_read(bns_ctx *ctx, uint32_t *seq_taxid, uint32_t *called, uint64_t *count, uint64_t cap, uint64_t *n_pairs,
