@@ -516,6 +516,12 @@ class Context:
     def probe_device(self, d_kmers, n, d_vals, d_found=None, stream=None):
         self._chk(self.L.bns_probe_device(self.h, d_kmers, n, d_vals, d_found, stream), "bns_probe_device")
 
+    def encode_device(self, d_bases, d_offsets, n_reads, total_bases, d_kmers, d_n_kmers, stream=None):
+        """bns_encode_batch_device: read r's k-mers (minimizers under set_window) at d_kmers[offsets[r]:] (total_bases uint64), their
+        number in d_n_kmers[r] (uint32).  Queued on the stream: wait for it before reading."""
+        self._chk(self.L.bns_encode_batch_device(self.h, d_bases, d_offsets, n_reads, total_bases, d_kmers, d_n_kmers, stream),
+                  "bns_encode_batch_device")
+
     def build_table_device(self, d_bases, d_offsets, n_genomes, total_bases, d_taxid, n_buckets, d_flags, d_keys,
                            d_vals, stream=None):
         hdr = np.zeros(4, dtype=np.uint64)

@@ -96,6 +96,29 @@ int bns_set_window(bns_ctx *ctx, uint32_t w, int score);
  * chunks of 2^27 slots when they do not (an 8e9-key db: 210 GB of arrays, 200+ GB of table); BNS_LAYOUT_KHASH keeps them resident. */
 int bns_load_table(bns_ctx *ctx, uint64_t n_buckets, const uint32_t *flags, const uint64_t *keys,
                    const uint32_t *vals, int layout);
+/* ---- the `void *stream` argument of the _device entry points, bns_build_add, bns_build_minimize_add and bns_windows_add ----------
+ * `stream` is a hipStream_t of the context's device; NULL means the context's own stream (the one every host-buffer entry point
+ * works on).  For a non-NULL stream:
+ *   ORDER     everything the call enqueues -- kernels, memsets, the copies of its counters -- goes on `stream`, in order.  Inputs
+ *             written by work enqueued on `stream` before the call are seen (the caller need not wait for them); the results are
+ *             complete for work enqueued on `stream` after the call returns.  Nothing is ordered against any other stream.
+ *   RETURN    these return with their work still queued: bns_probe_device, bns_encode_batch_device, bns_windows_add (unless the
+ *             session began with timing on: a timed add waits for its batch), and bns_classify_batch_device /
+ *             bns_classify_batch_packed_device when max_read_len is given AND no unit can hold more than 128 k-mers
+ *             (mates * (max_read_len - seed span + 1) <= 128: no overflow list to read back).  Their inputs and outputs are the
+ *             device's until `stream` has been waited for.  These have synchronised `stream` when they return:
+ *             bns_load_table_device, bns_build_table_device, bns_build_add, bns_build_minimize_add, and the two classify calls
+ *             with max_read_len = 0 (the longest read is read back) or with units of more than 128 k-mers (the overflow count is).
+ *             bns_build_add, bns_build_minimize_add and bns_windows_add first wait for the context's own stream (begin, seed, a
+ *             reset or an earlier grow worked there).
+ *   WORKSPACE a context has ONE workspace (its counters, records, packed image, flag words, scratch, overflow list, tally and
+ *             sketches), shared by all its calls.  Two calls on one context on different streams must not overlap: ordering them
+ *             (an event, or waiting for the first) is the caller's job.  A call that has to enlarge a workspace buffer frees the old
+ *             one, which drains the device.
+ *   READERS   bns_tally_read, bns_sketch_read, bns_build_finish / bns_build_export and bns_dev_download work on the context's own
+ *             stream: `stream` must be complete before they are called.  bns_windows_read and bns_dev_sync drain the device
+ *             themselves.  The timing events (bns_set_timing) are recorded on `stream`, around the call's dominant kernel. */
+
 /* Same, arrays already resident in HBM (e.g. after an RCCL broadcast).  With BNS_LAYOUT_KHASH the
  * context BORROWS the arrays (caller keeps them alive); with BNS_LAYOUT_BUCKET they are only read
  * during the call's enqueued kernels. */
