@@ -7,6 +7,7 @@
 #include "bns_inspect.hpp"
 #include "bns_confidence.hpp"
 #include "bns_sketch.hpp"
+#include "bns_text_plan.hpp"
 
 #include <dlfcn.h>
 #if defined(__x86_64__)
@@ -51,13 +52,12 @@ static_assert(sizeof(SmallLayout) <= SMALL_BYTES, "ctx->small is allocated with 
 static_assert(offsetof(SmallLayout, load_cnt) >= SMALL_CLASSIFY_ZERO, "classify's memset must not reach the other entry points' words");
 
 // bns_debug_set bits (tests and profiling; 0 in production); the table load's -- 0x10, 0x20, 0x100, 0x200, 0x1000, bits 16-20 and
-// 24-28 -- are in bns_table_plan.hpp, the classify launch's -- 0x2000, 0x8000 -- in bns_classify_plan.hpp
+// 24-28 -- are in bns_table_plan.hpp, the classify launch's -- 0x2000, 0x8000 -- in bns_classify_plan.hpp, the text calls' -- 0x40,
+// 0x4000 -- in bns_text_plan.hpp
 constexpr int BNS_DBG_PEXT_OFF = 0x400;             // spaced seeds: gather run by run instead of through the compress network
 constexpr int BNS_DBG_FORCE_RCCL = 0x800;           // bns_load_table_multi with ONE context still broadcasts through RCCL (1-rank communicator)
-constexpr int BNS_DBG_BATCH_TINY = 0x40;            // bns_classify_text: a classify launch per >= 64 records (many batches on small texts)
 constexpr int BNS_DBG_INSPECT_TINY = 0x8;           // bns_table_tally: grids of at most 4 workgroups that flush their LDS counters every 3 rounds (tests: many rounds, a full LDS hash and the mid-walk flush on small tables; same counts)
 constexpr int BNS_DBG_INSPECT_WHOLE = 0x80;         // bns_table_tally: fetch whole 128-byte buckets instead of their upper halves (A/B; same counts)
-constexpr int BNS_DBG_SLICE_8K = 0x4000;            // bns_classify_batch uploads in 8 KiB slices (the slicing logic on small batches)
 
 // What the last classify dispatch launched (bns_debug_last_classify_form, a test aid): the template arguments of the
 // classify_kernel instantiation, of the classify_overflow_kernel one when units went there, and the launch geometry.  Written

@@ -46,28 +46,12 @@
 namespace bns {
 namespace ingest {
 
-constexpr u32 TILE = 16384;                     // text bytes per pass of a 256-thread block (64 per lane)
+// (TILE, the text bytes per pass of a 256-thread block, REC_BLOCK, StreamInfo and CallInfo: bns_text_plan.hpp -- the call's plan sizes by them)
 constexpr u32 SUB = 16;                         // lanes per record in pack_text_kernel (four records per wavefront)
 constexpr u32 REC_ITEMS = 8;                    // candidates / records per thread of a scan block (2048 per block)
-constexpr u32 REC_BLOCK = 256u * REC_ITEMS;
+static_assert(REC_BLOCK == 256u * REC_ITEMS, "a scan block is 256 threads");
 constexpr u32 MAX_REC_LINES = 4096;
 constexpr u32 WALK_INCOMPLETE = 0x80000000u;    // (c_flags) the walk ran into the end of a text that is not final
-
-struct StreamInfo {
-    u32 n_nl, n_lines, n_cand, n_hdr;           // n_cand: lines that start with '>' / '@'; n_hdr: those that are headers
-    u32 n_take, consumed, why, lo;
-    u32 hi, n_eff, n_real, any_inside;          // n_eff: headers that yield a record (a final text that ends in a bare '>' / '@' byte: that one does not)
-    u32 why_all, pad[3];                        // n_real: lines that may be looked at (not the unfinished last line of a text that goes on; not the nothing behind a final '\n')
-};                                              // any_inside: a walk found candidates inside its record; why_all: what the walks found wrong, all candidates
-struct CallInfo {
-    StreamInfo s[2];
-    u32 n_take;                                 // records per stream this call takes
-    u32 n_reads;                                // n_take * n_streams
-    u32 max_len, why;
-    u32 total_bases, names_bytes;
-    u32 ticket[6];                              // block tickets: lines_kernel [0..1], compact_kernel [2..3], offsets_kernel [4]; [5]: compact blocks that are done
-    u32 fast, pad;                              // every candidate of either stream is a header: record r is candidate r
-};
 
 // what one stream's kernels work on (buffer coordinates: text + lo .. text + hi)
 struct StreamArgs {
@@ -652,9 +636,8 @@ struct Upload {
     u64 bytes = 0, piece = 0;
     u32 n_pieces = 0;
     bool pending = false;                               // uploaded (or on its way) and not yet classified
-    hipEvent_t ev[64] = {};
+    hipEvent_t ev[MAX_PIECES] = {};
 };
-constexpr u32 MAX_PIECES = 64;
 
 struct TextWork {                                       // the context's workspace for bns_classify_text (grow-only)
     Upload up[2][2];                                    // [stream][buffer]
@@ -694,9 +677,31 @@ struct TextCall {
     int status = BNS_TEXT_OK;
     u32 why = 0, n_launches = 0, rounds = 0;
     float ms_parse = 0, ms_classify = 0;
+    // where each stream's text is: the (aligned) base of its buffer, the offset of the call's text in it, the upload it travels in (host text)
+    const u8 *text[2] = {nullptr, nullptr};
     u32 rel[2] = {0, 0};
     Upload *up[2] = {nullptr, nullptr};
 };
+
+// THE table of the workspace's device buffers, each with the bytes a call's plan asks for (0: not that call's, or sized where it is
+// filled: the line bytes by text_flush_batch, an upload by start_upload).  text_reserve and text_work_free both walk it.
+template <class F>
+void text_each_buffer(TextWork &tw, const TextBytes &b, F &&f)
+{
+    for (u32 s = 0; s < 2; ++s) {
+        f(tw.ls[s], b.ls[s]); f(tw.line_off[s], b.line_off[s]);
+        for (DevBuf &c : tw.cand[s]) f(c, b.cand[s]);
+    }
+    for (u32 q = 0; q < 2; ++q) { f(tw.seq_len[q], b.seq_len); f(tw.name_off[q], b.name_off); f(tw.pos64[q], b.pos64); f(tw.names[q], b.names); }
+    f(tw.offsets, b.offsets); f(tw.words, b.words); f(tw.nmask, b.nmask); f(tw.info, b.info);
+    for (u32 q = 0; q < 2; ++q) for (DevBuf &o : tw.out[q]) f(o, b.out);
+    for (u32 q = 0; q < 2; ++q) f(tw.lines_off[q], b.lines_off);
+    f(tw.lines_state, b.lines_state);
+    f(tw.hits, b.hits);
+    for (u32 q = 0; q < 2; ++q) for (u32 i = 0; i < 4; ++i) f(tw.runs[q][i], b.runs[i]);
+    for (u32 q = 0; q < 2; ++q) f(tw.lines[q], size_t(0));
+    for (auto &row : tw.up) for (Upload &u : row) f(u.buf, size_t(0));
+}
 
 void text_release_uploads(TextCall &tc) { for (u32 s = 0; s < tc.ns; ++s) if (tc.up[s]) { tc.up[s]->pending = false; tc.up[s] = nullptr; } }
 // an error exit: uploads in flight are waited for and given up, the three streams drained
@@ -709,41 +714,53 @@ int text_bail(bns_ctx *ctx, TextCall &tc, int code)
     tc.pending = false;
     return code;
 }
+// a HIP call of a text call in progress: its failure leaves through text_bail (`ctx` and the call's `tc` are in scope)
+#define TXCHK(expr)                                                                                                            \
+    do {                                                                                                                        \
+        hipError_t _e = (expr);                                                                                                 \
+        if (_e != hipSuccess) {                                                                                                 \
+            ctx->err = std::string(#expr) + ": " + hipGetErrorString(_e);                                                       \
+            return text_bail(ctx, tc, _e == hipErrorOutOfMemory ? BNS_ERR_NOMEM : BNS_ERR_HIP);                                 \
+        }                                                                                                                       \
+    } while (0)
 
 // (after a drain of the back stream) the runs of batch batch_no - 1 -> the caller's arrays, or the context's
 int text_flush_runs_of_prev(bns_ctx *ctx, TextWork &tw, TextCall &tc)
 {
     if (!tc.want_runs || tc.batch_no == 0) return BNS_OK;
-    hipStream_t bs = ctx->back_stream;
-    const bns_text_out *out = &tc.out;
-    u64 &runs_done = tc.runs_done;
     const u32 pq = (tc.batch_no - 1u) & 1u;
     const u64 n_tot = tw.h_cursor[pq];                      // runs so far, that batch's included
-    if (out->run_tax) {                                     // the caller's own arrays
-        if (n_tot > out->runs_cap) { tc.runs_overflow = true; return BNS_OK; }
-        if (n_tot > runs_done) {
-            HIPCHK(ctx, hipMemcpyAsync(out->run_tax + runs_done, tw.runs[pq][2].p, (size_t)(n_tot - runs_done) * 4, hipMemcpyDeviceToHost, bs));
-            HIPCHK(ctx, hipMemcpyAsync(out->run_len + runs_done, tw.runs[pq][3].p, (size_t)(n_tot - runs_done) * 4, hipMemcpyDeviceToHost, bs));
+    u32 *run_tax = tc.out.run_tax, *run_len = tc.out.run_len;
+    if (run_tax) {                                          // the caller's own arrays: they are as large as they are
+        if (n_tot > tc.out.runs_cap) { tc.runs_overflow = true; return BNS_OK; }
+    } else {                                                // the context's: they grow
+        if (ctx->h_run_cap < n_tot) {
+            const size_t want = (size_t)n_tot + (size_t)n_tot / 2 + 1024;
+            u32 *nt = nullptr, *nl = nullptr;
+            HIPCHK(ctx, hipHostMalloc((void **)&nt, want * 4, hipHostMallocDefault));
+            HIPCHK(ctx, hipHostMalloc((void **)&nl, want * 4, hipHostMallocDefault));
+            if (tc.runs_done) { std::memcpy(nt, ctx->h_run_tax, (size_t)tc.runs_done * 4); std::memcpy(nl, ctx->h_run_len, (size_t)tc.runs_done * 4); }
+            if (ctx->h_run_tax) (void)hipHostFree(ctx->h_run_tax);
+            if (ctx->h_run_len) (void)hipHostFree(ctx->h_run_len);
+            ctx->h_run_tax = nt; ctx->h_run_len = nl; ctx->h_run_cap = want;
         }
-        runs_done = n_tot;
-        return BNS_OK;
+        run_tax = ctx->h_run_tax; run_len = ctx->h_run_len;
     }
-    if (ctx->h_run_cap < n_tot) {
-        const size_t want = (size_t)n_tot + (size_t)n_tot / 2 + 1024;
-        u32 *nt = nullptr, *nl = nullptr;
-        HIPCHK(ctx, hipHostMalloc((void **)&nt, want * 4, hipHostMallocDefault));
-        HIPCHK(ctx, hipHostMalloc((void **)&nl, want * 4, hipHostMallocDefault));
-        if (runs_done) { std::memcpy(nt, ctx->h_run_tax, (size_t)runs_done * 4); std::memcpy(nl, ctx->h_run_len, (size_t)runs_done * 4); }
-        if (ctx->h_run_tax) (void)hipHostFree(ctx->h_run_tax);
-        if (ctx->h_run_len) (void)hipHostFree(ctx->h_run_len);
-        ctx->h_run_tax = nt; ctx->h_run_len = nl; ctx->h_run_cap = want;
+    if (n_tot > tc.runs_done) {
+        HIPCHK(ctx, hipMemcpyAsync(run_tax + tc.runs_done, tw.runs[pq][2].p, (size_t)(n_tot - tc.runs_done) * 4, hipMemcpyDeviceToHost, ctx->back_stream));
+        HIPCHK(ctx, hipMemcpyAsync(run_len + tc.runs_done, tw.runs[pq][3].p, (size_t)(n_tot - tc.runs_done) * 4, hipMemcpyDeviceToHost, ctx->back_stream));
     }
-    if (n_tot > runs_done) {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_run_tax + runs_done, tw.runs[pq][2].p, (size_t)(n_tot - runs_done) * 4, hipMemcpyDeviceToHost, bs));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_run_len + runs_done, tw.runs[pq][3].p, (size_t)(n_tot - runs_done) * 4, hipMemcpyDeviceToHost, bs));
-    }
-    runs_done = n_tot;
+    tc.runs_done = n_tot;
     return BNS_OK;
+}
+
+// (after a drain of the back stream) what the last classified batch -- the one in set q -- took joins the call's times
+void text_add_batch_times(bns_ctx *ctx, TextWork &tw, TextCall &tc, u32 q)
+{
+    if (!tc.batch_no || !ctx->timing) return;
+    float ms = 0;
+    if (!tc.parse_only && hipEventElapsedTime(&ms, tw.tc0[q], tw.tc1[q]) == hipSuccess) tc.ms_classify += ms;
+    if (tc.want_lines && !tc.parse_only && hipEventElapsedTime(&ms, tw.tl0, tw.tl1) == hipSuccess) tc.ms_lines += ms;   // (that batch recorded the events around its hit-run and line kernels)
 }
 
 // the last classified batch is not the caller's after all (its runs did not fit his arrays): nor is what came behind it.  (Nothing was
@@ -763,8 +780,41 @@ int text_roll_back(bns_ctx *ctx, TextWork &tw, TextCall &tc)
     return BNS_OK;
 }
 
-// (the last classified batch recorded the events around its hit-run and line kernels)
-static inline bool want_lines_prev(const TextCall &tc) { return tc.want_lines && !tc.parse_only; }
+// The Kraken lines of the open batch (classified, its hit runs made: set batch_no & 1).  Lengths and places first; the batch's byte
+// count comes back before a byte is written: the device buffer is sized by it (a bound from the batch's bases would be 22 bytes a
+// base), and a batch that does not fit the caller's buffer is known at once.
+int text_batch_lines(bns_ctx *ctx, TextWork &tw, TextCall &tc, u64 runs_base, u64 &lines_bytes, bool &lines_overflow)
+{
+    hipStream_t st = ctx->stream;
+    const u32 q = tc.batch_no & 1u;
+    const u64 n_units = tc.acc_reads / tc.ns;
+    unsigned long long *d_lcur = &((SmallLayout *)ctx->small.p)->lines_cursor;   // (zeroed at the start of the call, like runs_cursor)
+    LinesArgs la{};
+    la.taxon = (u32 *)tw.out[q][0].p; la.missing = (u32 *)tw.out[q][1].p; la.ambig = (u32 *)tw.out[q][2].p;
+    la.seq_len = (const u32 *)tw.seq_len[q].p; la.name_off = (const u32 *)tw.name_off[q].p;
+    la.names = (const char *)tw.names[q].p; la.name_base = (u32)tc.open_names0;
+    la.run_start = (const u64 *)tw.runs[q][0].p; la.n_runs = (const u32 *)tw.runs[q][1].p;
+    la.run_tax = (const u32 *)tw.runs[q][2].p - runs_base; la.run_len = (const u32 *)tw.runs[q][3].p - runs_base;
+    la.n_units = n_units; la.nmates = tc.ns; la.emit_all = (tc.out.lines_flags & BNS_LINES_ALL) ? 1u : 0u;
+    la.line_off = (u64 *)tw.lines_off[q].p; la.base = tc.lines_done;
+    la.ticket = (u32 *)tw.lines_state.p; la.state = (u64 *)tw.lines_state.p + 1; la.cursor = d_lcur;
+    const size_t n_blocks = (size_t)((n_units + 255) / 256);
+    HIPCHK(ctx, hipMemsetAsync(tw.lines_state.p, 0, (n_blocks + 2) * 8, st));
+    hipLaunchKernelGGL(lines_len_kernel, dim3(grid_for(ctx, n_units, 256)), dim3(256), 0, st, la);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(&tw.h_cursor[2], d_lcur, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    lines_bytes = tw.h_cursor[2] - tc.lines_done;
+    if (tw.h_cursor[2] > tc.out.lines_cap) lines_overflow = true;
+    else if (lines_bytes) {
+        BNS_RC(ensure(ctx, tw.lines[q], (size_t)lines_bytes + 64));
+        la.lines = (char *)tw.lines[q].p; la.cap = lines_bytes;
+        hipLaunchKernelGGL(lines_write_kernel, dim3(grid_for(ctx, (n_units + LINES_GROUP - 1) / LINES_GROUP, 4)), dim3(256), 0, st, la);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (ctx->timing) HIPCHK(ctx, hipEventRecord(tw.tl1, st));
+    return BNS_OK;
+}
 
 // ---- the open batch -> one classify launch; its results behind those of the batches in front.  Results leave on the back stream:
 // batch b's arrays (set b & 1) are copied out while batch b + 1 is parsed and classified into the other set.  Before a batch is
@@ -782,8 +832,7 @@ int text_flush_batch(bns_ctx *ctx, TextWork &tw, TextCall &tc)
     const u64 n_reads = tc.acc_reads, n_units = tc.acc_reads / ns, u_done = tc.open_reads0 / ns;
     // (the back stream drained: the out / runs arrays of set q are free, and the run count of the batch in front is on the host)
     HIPCHK(ctx, hipStreamSynchronize(bs));
-    if (tc.batch_no && ctx->timing && !parse_only) { float ms = 0; if (hipEventElapsedTime(&ms, tw.tc0[q ^ 1u], tw.tc1[q ^ 1u]) == hipSuccess) tc.ms_classify += ms; }
-    if (tc.batch_no && ctx->timing && want_lines_prev(tc)) { float ms = 0; if (hipEventElapsedTime(&ms, tw.tl0, tw.tl1) == hipSuccess) tc.ms_lines += ms; }
+    text_add_batch_times(ctx, tw, tc, q ^ 1u);
     int frc = text_flush_runs_of_prev(ctx, tw, tc);
     if (frc != BNS_OK) return frc;
     if (tc.runs_overflow) { tc.status = BNS_TEXT_CAP; return text_roll_back(ctx, tw, tc); }
@@ -811,35 +860,7 @@ int text_flush_batch(bns_ctx *ctx, TextWork &tw, TextCall &tc)
                                (u32 *)tw.runs[q][2].p - runs_base, (u32 *)tw.runs[q][3].p - runs_base, d_cur);
             HIPCHK(ctx, hipGetLastError());
         }
-        if (want_lines) {
-            // Lengths and places first; the batch's byte count comes back before a byte is written: the device buffer is sized by it (a
-            // bound from the batch's bases would be 22 bytes a base), and a batch that does not fit the caller's buffer is known at once.
-            unsigned long long *d_lcur = &((SmallLayout *)ctx->small.p)->lines_cursor;   // (zeroed at the start of the call, like runs_cursor)
-            LinesArgs la{};
-            la.taxon = o0; la.missing = o1; la.ambig = o2;
-            la.seq_len = (const u32 *)tw.seq_len[q].p; la.name_off = (const u32 *)tw.name_off[q].p;
-            la.names = (const char *)tw.names[q].p; la.name_base = (u32)tc.open_names0;
-            la.run_start = (const u64 *)tw.runs[q][0].p; la.n_runs = (const u32 *)tw.runs[q][1].p;
-            la.run_tax = (const u32 *)tw.runs[q][2].p - runs_base; la.run_len = (const u32 *)tw.runs[q][3].p - runs_base;
-            la.n_units = n_units; la.nmates = ns; la.emit_all = (out->lines_flags & BNS_LINES_ALL) ? 1u : 0u;
-            la.line_off = (u64 *)tw.lines_off[q].p; la.base = tc.lines_done;
-            la.ticket = (u32 *)tw.lines_state.p; la.state = (u64 *)tw.lines_state.p + 1; la.cursor = d_lcur;
-            const size_t n_blocks = (size_t)((n_units + 255) / 256);
-            HIPCHK(ctx, hipMemsetAsync(tw.lines_state.p, 0, (n_blocks + 2) * 8, st));
-            hipLaunchKernelGGL(lines_len_kernel, dim3(grid_for(ctx, n_units, 256)), dim3(256), 0, st, la);
-            HIPCHK(ctx, hipGetLastError());
-            HIPCHK(ctx, hipMemcpyAsync(&tw.h_cursor[2], d_lcur, 8, hipMemcpyDeviceToHost, st));
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            lines_bytes = tw.h_cursor[2] - tc.lines_done;
-            if (tw.h_cursor[2] > out->lines_cap) lines_overflow = true;
-            else if (lines_bytes) {
-                if ((frc = ensure(ctx, tw.lines[q], (size_t)lines_bytes + 64)) != BNS_OK) return frc;
-                la.lines = (char *)tw.lines[q].p; la.cap = lines_bytes;
-                hipLaunchKernelGGL(lines_write_kernel, dim3(grid_for(ctx, (n_units + LINES_GROUP - 1) / LINES_GROUP, 4)), dim3(256), 0, st, la);
-                HIPCHK(ctx, hipGetLastError());
-            }
-            if (ctx->timing) HIPCHK(ctx, hipEventRecord(tw.tl1, st));
-        }
+        if (want_lines && (frc = text_batch_lines(ctx, tw, tc, runs_base, lines_bytes, lines_overflow)) != BNS_OK) return frc;
     }
     // the copies, on the back stream behind this batch's kernels; the next batch is parsed and classified meanwhile
     HIPCHK(ctx, hipEventRecord(tw.ev_done[q], st));
@@ -910,20 +931,173 @@ int text_wrap_up(bns_ctx *ctx, TextWork &tw, TextCall &tc, bns_text_info *info)
     hipStream_t st = ctx->stream, bs = ctx->back_stream;
     int rc = text_flush_batch(ctx, tw, tc);
     if (rc != BNS_OK) return text_bail(ctx, tc, rc);
-#define WUCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { ctx->err = std::string(#expr) + ": " + hipGetErrorString(_e); return text_bail(ctx, tc, _e == hipErrorOutOfMemory ? BNS_ERR_NOMEM : BNS_ERR_HIP); } } while (0)
-    WUCHK(hipStreamSynchronize(st));
-    WUCHK(hipStreamSynchronize(bs));
-    if (tc.batch_no && ctx->timing && !tc.parse_only) { float ms = 0; if (hipEventElapsedTime(&ms, tw.tc0[(tc.batch_no - 1u) & 1u], tw.tc1[(tc.batch_no - 1u) & 1u]) == hipSuccess) tc.ms_classify += ms; }
-    if (tc.batch_no && ctx->timing && want_lines_prev(tc)) { float ms = 0; if (hipEventElapsedTime(&ms, tw.tl0, tw.tl1) == hipSuccess) tc.ms_lines += ms; }
+    TXCHK(hipStreamSynchronize(st));
+    TXCHK(hipStreamSynchronize(bs));
+    text_add_batch_times(ctx, tw, tc, (tc.batch_no - 1u) & 1u);
     if (!tc.rolled_back) {
         if ((rc = text_flush_runs_of_prev(ctx, tw, tc)) != BNS_OK) return text_bail(ctx, tc, rc);
         if (tc.runs_overflow) { tc.status = BNS_TEXT_CAP; if ((rc = text_roll_back(ctx, tw, tc)) != BNS_OK) return text_bail(ctx, tc, rc); }
     }
-    WUCHK(hipStreamSynchronize(bs));
-#undef WUCHK
+    TXCHK(hipStreamSynchronize(bs));
     if ((rc = text_give_back_uploads(ctx, tw, tc)) != BNS_OK) return text_bail(ctx, tc, rc);
     tc.pending = false;
     text_fill_info(ctx, tc, info);
+    return BNS_OK;
+}
+
+// ---- the measurement overrides, read from the environment on every call (what the numbers mean: TextPlanIn)
+long long text_piece_mb_env()
+{
+    const char *e = std::getenv("BNS_TEXT_PIECE_MB");
+    if (!e) return 0;
+    const long v = std::atol(e);
+    return v > 0 ? v : -1;
+}
+long long text_batch_reads_env() { const char *e = std::getenv("BNS_TEXT_BATCH_READS"); return e ? std::atoll(e) : 0; }
+
+// host[0, bytes) -> u.buf, piece by piece on the copy stream
+int start_upload(bns_ctx *ctx, Upload &u, const char *host, u64 bytes)
+{
+    int rc = ensure(ctx, u.buf, (size_t)bytes + 256);
+    if (rc != BNS_OK) return rc;
+    if (!ctx->copy_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    u.host = host; u.bytes = bytes; u.piece = text_piece_bytes(ctx->dbg, text_piece_mb_env(), bytes);
+    u.n_pieces = (u32)std::max<u64>(1, (bytes + u.piece - 1) / u.piece);
+    for (u32 j = 0; j < u.n_pieces; ++j) {
+        const u64 a = (u64)j * u.piece, b = std::min<u64>(bytes, a + u.piece);
+        if (b > a) HIPCHK(ctx, hipMemcpyAsync((char *)u.buf.p + a, host + a, (size_t)(b - a), hipMemcpyHostToDevice, ctx->copy_stream));
+        if (!u.ev[j]) HIPCHK(ctx, hipEventCreateWithFlags(&u.ev[j], hipEventDisableTiming));
+        HIPCHK(ctx, hipEventRecord(u.ev[j], ctx->copy_stream));
+    }
+    u.pending = true;
+    return BNS_OK;
+}
+
+// ---- bns_classify_text, step by step
+// the argument rules, in the order they are tested: the first one that fails decides the code
+int text_check_args(bns_ctx *ctx, const char *const *text, const uint64_t *text_bytes, int n_streams, int flags, const bns_text_out *out, const bns_text_info *info)
+{
+    if (!ctx || !text || !text_bytes || !out || !info || (n_streams != 1 && n_streams != 2)) return BNS_ERR_ARG;
+    const bool parse_only = (flags & BNS_TEXT_PARSE_ONLY) != 0;
+    if ((flags & BNS_TEXT_DEFER) && (out->words || out->nmask)) return BNS_ERR_ARG;
+    BNS_RC(ready(ctx, !parse_only, !parse_only));
+    if (!parse_only && !out->taxon) return BNS_ERR_ARG;
+    if ((out->run_start != nullptr) != (out->n_runs != nullptr)) return BNS_ERR_ARG;
+    if (out->name_off && !out->names) return BNS_ERR_ARG;
+    if (out->lines && parse_only) return BNS_ERR_ARG;
+    if (out->line_off && !out->lines) return BNS_ERR_ARG;
+    if ((out->run_tax != nullptr) != (out->run_len != nullptr) || (out->run_tax && !out->run_start)) return BNS_ERR_ARG;
+    for (int s = 0; s < n_streams; ++s) {
+        if (text_bytes[s] && !text[s]) return BNS_ERR_ARG;
+        // (every 32-bit offset of the text path rests on this bound: bns_text_plan.hpp)
+        if (text_bytes[s] >= (1ULL << 31)) return fail(ctx, BNS_ERR_ARG, "bns_classify_text: at most 2^31 - 1 bytes of text per stream and call");
+    }
+    return BNS_OK;
+}
+
+// the workspace's events and page-locked words: made by the context's first text call
+int text_work_init(bns_ctx *ctx, TextWork &tw)
+{
+    if (tw.h_info) return BNS_OK;
+    HIPCHK(ctx, hipHostMalloc((void **)&tw.h_info, sizeof(CallInfo), hipHostMallocDefault));
+    HIPCHK(ctx, hipHostMalloc((void **)&tw.h_cursor, 32, hipHostMallocDefault));
+    HIPCHK(ctx, hipEventCreate(&tw.t0)); HIPCHK(ctx, hipEventCreate(&tw.t1));
+    HIPCHK(ctx, hipEventCreate(&tw.tl0)); HIPCHK(ctx, hipEventCreate(&tw.tl1));
+    for (int q = 0; q < 2; ++q) {
+        HIPCHK(ctx, hipEventCreateWithFlags(&tw.ev_done[q], hipEventDisableTiming));
+        HIPCHK(ctx, hipEventCreate(&tw.tc0[q])); HIPCHK(ctx, hipEventCreate(&tw.tc1[q]));
+    }
+    return BNS_OK;
+}
+
+// where the text is: inside an upload that bns_text_prefetch started (at any offset `rel` of it), in one started now, or in the
+// caller's device memory -- into tc; and with that, what the call's plan is made from
+int text_sources(bns_ctx *ctx, TextWork &tw, TextCall &tc, const char *const *text, const uint64_t *text_bytes, TextPlanIn &in)
+{
+    in.ns = tc.ns; in.on_device = tc.on_device; in.parse_only = tc.parse_only; in.want_runs = tc.want_runs; in.want_lines = tc.want_lines;
+    in.want_words = tc.out.words || tc.out.nmask;
+    in.dbg = ctx->dbg; in.piece_mb = text_piece_mb_env(); in.batch_reads = text_batch_reads_env();
+    for (u32 s = 0; s < tc.ns; ++s) {
+        in.bytes[s] = text_bytes[s];
+        if (tc.on_device) {
+            // (the kernels want an aligned base: the 64-byte boundary in front of the text, the text at offset rel of it)
+            tc.rel[s] = (u32)((uintptr_t)text[s] & 63u);
+            tc.text[s] = (const u8 *)text[s] - tc.rel[s];
+        } else {
+            Upload *u = nullptr;
+            for (Upload &c : tw.up[s])
+                if (c.pending && c.host && text[s] >= c.host && text[s] + text_bytes[s] <= c.host + c.bytes) u = &c;     // (an empty text at its end included)
+            if (!u) {
+                u = !tw.up[s][0].pending ? &tw.up[s][0] : (!tw.up[s][1].pending ? &tw.up[s][1] : nullptr);
+                if (!u) return fail(ctx, BNS_ERR_STATE, "bns_classify_text: two prefetched texts are waiting and this call's text is neither");
+                BNS_RC(start_upload(ctx, *u, text[s], text_bytes[s]));
+            }
+            tc.up[s] = u; tc.text[s] = (const u8 *)u->buf.p;
+            tc.rel[s] = (u32)(text[s] - u->host);               // (inside an upload, and that holds less than 2^31 bytes)
+            in.upload_piece[s] = u->piece;
+        }
+        in.rel[s] = tc.rel[s];
+    }
+    return BNS_OK;
+}
+
+// every workspace buffer as large as the plan says (grow-only)
+int text_reserve(bns_ctx *ctx, TextWork &tw, const TextPlan &plan)
+{
+    int rc = BNS_OK;
+    text_each_buffer(tw, plan.bytes, [&](DevBuf &b, size_t bytes) { if (rc == BNS_OK) rc = ensure(ctx, b, bytes); });
+    return rc;
+}
+
+// One parse over [tc.cons[s], hi[s]) of every stream, hi = what piece k has brought up: the info words zeroed, the six launches --
+// the stretch's records are packed behind those the open batch holds -- and the CallInfo back on the host (the stream is drained).
+int text_parse_round(bns_ctx *ctx, TextWork &tw, TextCall &tc, const TextPlan &plan, u32 k, const u32 (&hi)[2], int fin, int flags, u32 lim, CallInfo &ci)
+{
+    hipStream_t st = ctx->stream;
+    const u32 ns = tc.ns, q = tc.batch_no & 1u;                 // q: the set of result arrays the open batch writes
+    const unsigned pgrid = (unsigned)ctx->n_cu * 8;
+    CallInfo *d_ci = (CallInfo *)tw.info.p;
+    if (ctx->timing) TXCHK(hipEventRecord(tw.t0, st));
+    TXCHK(hipMemsetAsync(d_ci, 0, plan.info_bytes, st));
+    ParseArgs pa{};
+    pa.ci = d_ci; pa.n_streams = ns; pa.final_text = fin; pa.trim_readno = (flags & BNS_TEXT_TRIM_READNO) ? 1 : 0;
+    char *info = (char *)tw.info.p;
+    u32 max_tiles = 1;
+    for (u32 s = 0; s < ns; ++s) {
+        // (the piece that ends this slice -- and with it every piece in front of it: the copy stream is in order)
+        if (tc.up[s]) TXCHK(hipStreamWaitEvent(st, tc.up[s]->ev[plan.piece_of(s, k)], 0));
+        StreamArgs &a = pa.s[s];
+        a.text = tc.text[s]; a.lo = tc.cons[s]; a.hi = hi[s];
+        a.tile0 = tile0(a.lo); a.n_tiles = n_tiles(a.lo, a.hi);
+        a.cap_lines = plan.cap_lines; a.cap_rec = plan.cap_rec;
+        a.ls = (u32 *)tw.ls[s].p; a.line_off = (u32 *)tw.line_off[s].p;
+        u32 **cp[10] = {&a.cand, &a.c_next, &a.c_seq, &a.c_name, &a.c_line1, &a.c_single, &a.c_flags, &a.c_inside, &a.c_pos, &a.rec_cand};
+        for (int i = 0; i < 10; ++i) *cp[i] = (u32 *)tw.cand[s][i].p;
+        a.st_lines = (u64 *)(info + plan.off_lines) + s * plan.st_tiles;
+        a.st_groups = (u64 *)(info + plan.off_groups) + s * plan.st_groups;
+        a.st_compact = (u64 *)(info + plan.off_compact) + s * plan.st_cand;
+        max_tiles = std::max(max_tiles, a.n_tiles);
+    }
+    pa.st_offsets = (u64 *)(info + plan.off_offsets);
+    const u32 R0 = (u32)tc.acc_reads;
+    // the slice's records go behind those the open batch holds: offsets from acc_bases on, names from names_done on
+    OffsetsOut oo{(u32 *)tw.seq_len[q].p + R0, (u64 *)tw.offsets.p + R0, tc.acc_bases, (u32 *)tw.name_off[q].p + R0, (u32)tc.names_done};
+    PackOut po{(const u64 *)tw.offsets.p + R0, R0, (u64 *)tw.words.p, (u32 *)tw.nmask.p, (const u32 *)tw.name_off[q].p + R0, (u32)(tc.names_done - tc.acc_names),
+               (char *)tw.names[q].p, (u64 *)tw.pos64[q].p + R0, {tc.rel[0], tc.rel[1]}};
+    const unsigned cgrid = (unsigned)std::min<u64>(pgrid, (u64)plan.cap_rec / REC_BLOCK + 1), ogrid = (unsigned)std::min<u64>(256, plan.slice_reads_cap / REC_BLOCK + 1);
+    hipLaunchKernelGGL(count_kernel, dim3(std::min<u32>(max_tiles, pgrid * 2), ns), dim3(256), 0, st, pa);
+    hipLaunchKernelGGL(write_kernel, dim3(std::min<u32>(max_tiles, pgrid * 2), ns), dim3(256), 0, st, pa);
+    hipLaunchKernelGGL(walk_kernel, dim3(pgrid, ns), dim3(256), 0, st, pa);
+    hipLaunchKernelGGL(compact_kernel, dim3(cgrid, ns), dim3(256), 0, st, pa, lim);
+    hipLaunchKernelGGL(offsets_kernel, dim3(ogrid), dim3(256), 0, st, pa, oo);
+    if (tw.min_qual) hipLaunchKernelGGL(pack_text_minq_kernel, dim3(pgrid), dim3(256), 0, st, pa, po, 33u + tw.min_qual);
+    else hipLaunchKernelGGL(pack_text_kernel, dim3(pgrid), dim3(256), 0, st, pa, po);
+    TXCHK(hipGetLastError());
+    if (ctx->timing) TXCHK(hipEventRecord(tw.t1, st));
+    TXCHK(hipMemcpyAsync(tw.h_info, d_ci, sizeof(CallInfo), hipMemcpyDeviceToHost, st));
+    TXCHK(hipStreamSynchronize(st));
+    ci = *tw.h_info;
+    if (ctx->timing) { float ms = 0; if (hipEventElapsedTime(&ms, tw.t0, tw.t1) == hipSuccess) tc.ms_parse += ms; }
     return BNS_OK;
 }
 
@@ -935,18 +1109,7 @@ void text_work_free(bns_ctx *ctx)
 {
     bns_text_work *tw = ctx->text_work;
     if (!tw) return;
-    std::vector<DevBuf *> bufs = {&tw->up[0][0].buf, &tw->up[0][1].buf, &tw->up[1][0].buf, &tw->up[1][1].buf, &tw->ls[0], &tw->ls[1],
-                                  &tw->line_off[0], &tw->line_off[1], &tw->info, &tw->offsets, &tw->words, &tw->nmask, &tw->hits};
-    for (auto &row : tw->cand) for (DevBuf &b : row) bufs.push_back(&b);
-    for (int q = 0; q < 2; ++q) {
-        bufs.push_back(&tw->seq_len[q]);
-        for (DevBuf &b : tw->out[q]) bufs.push_back(&b);
-        for (DevBuf &b : tw->runs[q]) bufs.push_back(&b);
-        bufs.push_back(&tw->lines[q]); bufs.push_back(&tw->lines_off[q]);
-        bufs.push_back(&tw->name_off[q]); bufs.push_back(&tw->names[q]); bufs.push_back(&tw->pos64[q]);
-    }
-    bufs.push_back(&tw->lines_state);
-    for (DevBuf *b : bufs) release(*b);
+    text_each_buffer(*tw, TextBytes{}, [](DevBuf &b, size_t) { release(b); });
     for (auto &row : tw->up) for (Upload &u : row) for (hipEvent_t e : u.ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : {tw->t0, tw->t1, tw->tl0, tw->tl1, tw->ev_done[0], tw->ev_done[1], tw->tc0[0], tw->tc0[1], tw->tc1[0], tw->tc1[1]}) if (e) (void)hipEventDestroy(e);
     if (tw->h_info) (void)hipHostFree(tw->h_info);
@@ -1005,33 +1168,6 @@ int bns_dev_copy_peer(bns_ctx *dst_ctx, void *dst, bns_ctx *src_ctx, const void 
     return BNS_OK;
 }
 
-static size_t text_piece_bytes(const bns_ctx *ctx, u64 bytes)
-{
-    size_t piece = (size_t)64 << 20;
-    if (const char *e = std::getenv("BNS_TEXT_PIECE_MB")) { const long v = std::atol(e); if (v > 0) piece = (size_t)v << 20; }   // (measurements)
-    if (ctx->dbg & BNS_DBG_SLICE_8K) piece = (size_t)8 << 10;
-    const u64 least = ((bytes + MAX_PIECES - 1) / MAX_PIECES + 63) & ~63ULL;
-    return (size_t)std::max<u64>(piece, least);
-}
-
-// host[0, bytes) -> u.buf, piece by piece on the copy stream
-static int start_upload(bns_ctx *ctx, Upload &u, const char *host, u64 bytes)
-{
-    int rc = ensure(ctx, u.buf, (size_t)bytes + 256);
-    if (rc != BNS_OK) return rc;
-    if (!ctx->copy_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    u.host = host; u.bytes = bytes; u.piece = text_piece_bytes(ctx, bytes);
-    u.n_pieces = (u32)std::max<u64>(1, (bytes + u.piece - 1) / u.piece);
-    for (u32 j = 0; j < u.n_pieces; ++j) {
-        const u64 a = (u64)j * u.piece, b = std::min<u64>(bytes, a + u.piece);
-        if (b > a) HIPCHK(ctx, hipMemcpyAsync((char *)u.buf.p + a, host + a, (size_t)(b - a), hipMemcpyHostToDevice, ctx->copy_stream));
-        if (!u.ev[j]) HIPCHK(ctx, hipEventCreateWithFlags(&u.ev[j], hipEventDisableTiming));
-        HIPCHK(ctx, hipEventRecord(u.ev[j], ctx->copy_stream));
-    }
-    u.pending = true;
-    return BNS_OK;
-}
-
 int bns_set_min_base_quality(bns_ctx *ctx, uint32_t q)
 {
     if (!ctx || q > 93u) return BNS_ERR_ARG;
@@ -1070,25 +1206,10 @@ int bns_text_prefetch(bns_ctx *ctx, const char *const *text, const uint64_t *tex
 int bns_classify_text(bns_ctx *ctx, const char *const *text, const uint64_t *text_bytes, int n_streams, uint64_t limit, int flags,
                       uint64_t cap_records, const bns_text_out *out, bns_text_info *info)
 {
-    if (!ctx || !text || !text_bytes || !out || !info || (n_streams != 1 && n_streams != 2)) return BNS_ERR_ARG;
     auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_enter = now_s();
-    const bool parse_only = (flags & BNS_TEXT_PARSE_ONLY) != 0, on_device = (flags & BNS_TEXT_DEVICE) != 0;
-    const bool final_text = (flags & BNS_TEXT_FINAL) != 0;
-    if ((flags & BNS_TEXT_DEFER) && (out->words || out->nmask)) return BNS_ERR_ARG;
-    int rc = ready(ctx, !parse_only, !parse_only);
+    int rc = text_check_args(ctx, text, text_bytes, n_streams, flags, out, info);
     if (rc != BNS_OK) return rc;
-    if (!parse_only && !out->taxon) return BNS_ERR_ARG;
-    if ((out->run_start != nullptr) != (out->n_runs != nullptr)) return BNS_ERR_ARG;
-    if (out->name_off && !out->names) return BNS_ERR_ARG;
-    if (out->lines && parse_only) return BNS_ERR_ARG;
-    if (out->line_off && !out->lines) return BNS_ERR_ARG;
-    if ((out->run_tax != nullptr) != (out->run_len != nullptr) || (out->run_tax && !out->run_start)) return BNS_ERR_ARG;
-    const u32 ns = (u32)n_streams;
-    for (u32 s = 0; s < ns; ++s) {
-        if (text_bytes[s] && !text[s]) return BNS_ERR_ARG;
-        if (text_bytes[s] >= (1ULL << 31)) return fail(ctx, BNS_ERR_ARG, "bns_classify_text: at most 2^31 - 1 bytes of text per stream and call");
-    }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::memset(info, 0, sizeof(*info));
     if (!ctx->text_work) ctx->text_work = new (std::nothrow) bns_text_work();
@@ -1098,249 +1219,90 @@ int bns_classify_text(bns_ctx *ctx, const char *const *text, const uint64_t *tex
     if (!tw.call) return BNS_ERR_NOMEM;
     TextCall &tc = *tw.call;
     if (tc.pending) return fail(ctx, BNS_ERR_STATE, "bns_classify_text: a deferred call waits for bns_text_finish");
+    if ((rc = text_work_init(ctx, tw)) != BNS_OK) return rc;
+    // ---- the call's state (it outlives the call behind BNS_TEXT_DEFER), where its text is, and what follows from that: the plan
+    tc = TextCall{};
+    tc.out = *out; tc.ns = (u32)n_streams;
+    tc.parse_only = (flags & BNS_TEXT_PARSE_ONLY) != 0; tc.on_device = (flags & BNS_TEXT_DEVICE) != 0;
+    tc.want_runs = out->run_start != nullptr && !tc.parse_only; tc.want_lines = out->lines != nullptr;
+    const u32 ns = tc.ns;
+    TextPlanIn in;
+    if ((rc = text_sources(ctx, tw, tc, text, text_bytes, in)) != BNS_OK) return rc;
+    // every error exit from here on goes through text_bail: uploads in flight are waited for and given up, the three streams drained
+    TextPlan plan;
+    const char *refusal = "";
+    if ((rc = plan_text(in, plan, refusal)) != BNS_OK) return text_bail(ctx, tc, fail(ctx, rc, std::string("bns_classify_text: ") + refusal));
+    if ((rc = text_reserve(ctx, tw, plan)) != BNS_OK) return text_bail(ctx, tc, rc);
+    for (u32 s = 0; s < ns; ++s) tc.cons[s] = tc.open_cons0[s] = tc.cons_before_prev[s] = tc.rel[s];
     hipStream_t st = ctx->stream;
-    if (!tw.h_info) {
-        HIPCHK(ctx, hipHostMalloc((void **)&tw.h_info, sizeof(CallInfo), hipHostMallocDefault));
-        HIPCHK(ctx, hipHostMalloc((void **)&tw.h_cursor, 32, hipHostMallocDefault));
-        HIPCHK(ctx, hipEventCreate(&tw.t0)); HIPCHK(ctx, hipEventCreate(&tw.t1));
-        HIPCHK(ctx, hipEventCreate(&tw.tl0)); HIPCHK(ctx, hipEventCreate(&tw.tl1));
-        for (int q = 0; q < 2; ++q) {
-            HIPCHK(ctx, hipEventCreateWithFlags(&tw.ev_done[q], hipEventDisableTiming));
-            HIPCHK(ctx, hipEventCreate(&tw.tc0[q])); HIPCHK(ctx, hipEventCreate(&tw.tc1[q]));
-        }
-    }
-    // ---- where the text is: inside an upload that bns_text_prefetch started (at any offset `rel` of it), in one started now, or in
-    // the caller's device memory.  Everything below works in the coordinates of that buffer -- whose base is aligned -- and the call's
-    // own offsets come back as buffer offset - rel.  Piece k of the upload ends slice k: it is parsed -- together with what the
-    // pieces in front of it left unfinished, which simply lies in front of it in the same buffer -- and classified while k + 1 ... travel.
-    struct Src { const u8 *base = nullptr; u32 rel = 0, end = 0, j0 = 0, n = 1; u64 piece = 0; Upload *up = nullptr; } src[2];
-    for (u32 s = 0; s < ns; ++s) {
-        Src &q = src[s];
-        if (on_device) {
-            // (the kernels want an aligned base: the 64-byte boundary in front of the text, the text at offset rel of it)
-            q.rel = (u32)((uintptr_t)text[s] & 63u);
-            q.base = (const u8 *)text[s] - q.rel; q.end = q.rel + (u32)text_bytes[s];
-            // text that is all there already is ONE slice (nothing travels that a second slice's parse could hide), unless pieces are asked for
-            // -- or the text is large: a slice's workspaces are sized by its bytes (4.6 bytes per byte of text), and a call of 1.35 GB -- what one
-            // call on a gzip stream inflates -- allocated 6 GB of them, again whenever a call was a little larger than every one before it (a
-            // hipFree each, the device drained each time: one call in eight took 4 s).  Slices of 128 MiB beyond that: the same 1.2 GB for every call
-            const bool pieces_forced = (ctx->dbg & BNS_DBG_SLICE_8K) || std::getenv("BNS_TEXT_PIECE_MB");
-            const u64 big_piece = 128ull << 20;
-            q.piece = pieces_forced ? text_piece_bytes(ctx, text_bytes[s]) : (q.end > big_piece ? big_piece : std::max<u64>(64, ((u64)q.end + 63) & ~63ULL));
-        } else {
-            Upload *u = nullptr;
-            for (Upload &c : tw.up[s])
-                if (c.pending && c.host && text[s] >= c.host && text[s] + text_bytes[s] <= c.host + c.bytes) u = &c;     // (an empty text at its end included)
-            if (!u) {
-                u = !tw.up[s][0].pending ? &tw.up[s][0] : (!tw.up[s][1].pending ? &tw.up[s][1] : nullptr);
-                if (!u) return fail(ctx, BNS_ERR_STATE, "bns_classify_text: two prefetched texts are waiting and this call's text is neither");
-                if ((rc = start_upload(ctx, *u, text[s], text_bytes[s])) != BNS_OK) return rc;
-            }
-            q.up = u; q.base = (const u8 *)u->buf.p; q.rel = (u32)(text[s] - u->host); q.end = q.rel + (u32)text_bytes[s]; q.piece = u->piece;
-        }
-        q.j0 = (u32)(q.rel / q.piece);
-        q.n = q.end > q.rel ? (u32)((q.end - 1) / q.piece) - q.j0 + 1 : 1;
-    }
-    const u32 n_slices = std::max(src[0].n, ns == 2 ? src[1].n : 1u);
-    auto up_to = [&](u32 s, u32 k) -> u32 {                      // where stream s's text ends after slice k (buffer coordinates)
-        const Src &q = src[s];
-        return k + 1 >= q.n ? q.end : (u32)std::min<u64>(q.end, (u64)(q.j0 + k + 1) * q.piece);
-    };
-    auto bail = [&](int code) { for (u32 s = 0; s < ns; ++s) tc.up[s] = src[s].up; tc.on_device = on_device; tc.ns = ns; return text_bail(ctx, tc, code); };
-    // every error exit from here on goes through bail(): uploads in flight are waited for and given up, the three streams drained
-#define TXCHK(expr)                                                                                                            \
-    do {                                                                                                                        \
-        hipError_t _e = (expr);                                                                                                 \
-        if (_e != hipSuccess) {                                                                                                 \
-            ctx->err = std::string(#expr) + ": " + hipGetErrorString(_e);                                                       \
-            return bail(_e == hipErrorOutOfMemory ? BNS_ERR_NOMEM : BNS_ERR_HIP);                                               \
-        }                                                                                                                       \
-    } while (0)
-    if ((out->words || out->nmask) && n_slices > 1) return bail(fail(ctx, BNS_ERR_ARG, "bns_classify_text: the packed words come back for one-slice calls only (<= 64 MiB of text)"));
-    // the largest stretch one parse may cover: two slices' worth (a record longer than a slice is the host parser's)
-    u64 range_cap = 0, call_text = 0;
-    for (u32 s = 0; s < ns; ++s) { range_cap = std::max<u64>(range_cap, n_slices == 1 ? text_bytes[s] : 2 * src[s].piece + 64); call_text += text_bytes[s]; }
-    const u32 cap_lines = (u32)(range_cap / 8 + 1024);          // (more lines than one per 8 bytes: BNS_TEXT_WHY_LINES)
-    const u32 cap_rec = (u32)(range_cap / 16 + 512);            // (more records than one per 16 bytes: BNS_TEXT_WHY_LINES as well)
-    // ---- batches.  A slice is what one parse covers (one upload piece and what the pieces in front left unfinished); a BATCH is what one
-    // classify launch covers: the records of consecutive slices, appended to ONE packed image (offsets, words, flag words, the result
-    // rows of the batch's set) until it holds `batch_reads` records (or batch_bases / batch_names), or the call ends.  The fused kernel
-    // at 210 k records a launch -- one 64 MiB slice -- ran at a fifth of its rate (26 records per wavefront slot: launch, the first
-    // fetches of a cold table and the tail are most of the 430 us); classifier.h:307-318 hands classify_seqs its batch whole, too.
-    // Capacities are "what a batch may hold when it is flushed" + one slice's worst case: a slice is packed before its counts are known.
-    u64 batch_reads = 2u << 20;
-    if (const char *e = std::getenv("BNS_TEXT_BATCH_READS")) { const long long v = std::atoll(e); if (v > 0) batch_reads = (u64)v; }   // (measurements)
-    if (ctx->dbg & BNS_DBG_BATCH_TINY) batch_reads = 64;         // (tests: many batches on small texts)
-    const u64 batch_bases = 320u << 20, batch_names = 64u << 20;
-    const u64 slice_reads_cap = (u64)cap_rec * ns, slice_bases_cap = range_cap * ns;
-    // (by the call's text rounded UP to a power of two: the calls of one input differ by a few per cent -- batches of a BGZF file, the first
-    // and the later calls of a gzip stream -- and a workspace that grows by a hair is freed and allocated again, every one of them, a hipFree
-    // each: with another thread's kernels queueing up all the while one such call was seen to take 4 s instead of 20 ms)
-    u64 sized_for = 64u << 20;
-    while (sized_for < call_text) sized_for <<= 1;
-    const u64 carry_reads = n_slices == 1 ? 0 : std::min<u64>(batch_reads, sized_for / 64 + 64);
-    const u64 carry_bases = n_slices == 1 ? 0 : std::min<u64>(batch_bases, sized_for);
-    const u64 carry_names = n_slices == 1 ? 0 : std::min<u64>(batch_names, sized_for);
-    const u64 cap_reads = slice_reads_cap + carry_reads, cap_bases = slice_bases_cap + carry_bases, cap_names = slice_bases_cap + carry_names;
-    if (cap_reads >= (1ULL << 31) || cap_bases >= (1ULL << 32) - (1ULL << 20)) return bail(fail(ctx, BNS_ERR_ARG, "bns_classify_text: text too large for one batch"));
-    for (u32 s = 0; s < ns; ++s) {
-        if ((rc = ensure(ctx, tw.ls[s], (size_t)cap_lines * 4 + 64)) != BNS_OK) return bail(rc);
-        if ((rc = ensure(ctx, tw.line_off[s], (size_t)cap_lines * 4 + 64)) != BNS_OK) return bail(rc);
-        for (DevBuf &b : tw.cand[s]) if ((rc = ensure(ctx, b, (size_t)cap_rec * 4 + 64)) != BNS_OK) return bail(rc);
-    }
-    // CallInfo and, behind it, the look-back words of the slice's scans (tiles of either stream, candidate blocks of either stream, record
-    // blocks): zeroed together in front of every parse
-    const size_t st_tiles = (size_t)(range_cap / TILE + 8), st_cand = (size_t)cap_rec / REC_BLOCK + 2, st_recs = (size_t)slice_reads_cap / REC_BLOCK + 2;
-    const size_t st_groups = st_tiles / 64 + 2;
-    const size_t info_bytes = ((sizeof(CallInfo) + 63) & ~size_t(63)) + (2 * st_tiles + 2 * st_groups + 2 * st_cand + st_recs) * 8;
-    for (int q = 0; q < 2; ++q) {
-        if ((rc = ensure(ctx, tw.seq_len[q], (size_t)cap_reads * 4 + 64)) != BNS_OK) return bail(rc);
-        if ((rc = ensure(ctx, tw.name_off[q], (size_t)(cap_reads + 1) * 4)) != BNS_OK) return bail(rc);
-        if ((rc = ensure(ctx, tw.pos64[q], (size_t)cap_reads * 8)) != BNS_OK) return bail(rc);
-        if ((rc = ensure(ctx, tw.names[q], (size_t)cap_names + 64)) != BNS_OK) return bail(rc);
-    }
-    if ((rc = ensure(ctx, tw.offsets, (size_t)(cap_reads + 1) * 8)) != BNS_OK) return bail(rc);
-    if ((rc = ensure(ctx, tw.words, ((size_t)cap_bases / 32 + cap_reads + 2) * 8)) != BNS_OK) return bail(rc);
-    if ((rc = ensure(ctx, tw.nmask, ((size_t)cap_bases / 32 + cap_reads + 2) * 4)) != BNS_OK) return bail(rc);
-    if ((rc = ensure(ctx, tw.info, info_bytes)) != BNS_OK) return bail(rc);
-    const bool want_runs = out->run_start != nullptr && !parse_only, want_lines = out->lines != nullptr;
-    if (!parse_only) {
-        for (int q = 0; q < 2; ++q) for (int i = 0; i < 4; ++i) if ((rc = ensure(ctx, tw.out[q][i], (size_t)cap_reads * 4 + 64)) != BNS_OK) return bail(rc);
-        if (want_lines) {                                       // (the line bytes themselves: sized batch by batch, text_flush_batch)
-            for (int q = 0; q < 2; ++q) if ((rc = ensure(ctx, tw.lines_off[q], (size_t)(cap_reads + 1) * 8 + 64)) != BNS_OK) return bail(rc);
-            if ((rc = ensure(ctx, tw.lines_state, ((size_t)cap_reads / 256 + 4) * 8)) != BNS_OK) return bail(rc);
-        }
-        if (want_runs || want_lines) {
-            if ((rc = ensure(ctx, tw.hits, (size_t)cap_bases * 4 + 64)) != BNS_OK) return bail(rc);
-            for (int q = 0; q < 2; ++q) {
-                if ((rc = ensure(ctx, tw.runs[q][0], (size_t)cap_reads * 8 + 64)) != BNS_OK) return bail(rc);
-                if ((rc = ensure(ctx, tw.runs[q][1], (size_t)cap_reads * 4 + 64)) != BNS_OK) return bail(rc);
-                if ((rc = ensure(ctx, tw.runs[q][2], (size_t)cap_bases * 4 + 64)) != BNS_OK) return bail(rc);
-                if ((rc = ensure(ctx, tw.runs[q][3], (size_t)cap_bases * 4 + 64)) != BNS_OK) return bail(rc);
-            }
-        }
-    }
     const double t_alloc0 = now_s();
     TXCHK(hipStreamSynchronize(st));                            // (workspaces of an earlier call on this stream are free now)
     if (getenv("BNS_CLI_TIMING") && now_s() - t_enter > 0.2)
         fprintf(stderr, "[timing] bns_classify_text: %.3f s until its workspaces stood (%.3f of it draining the stream)\n", now_s() - t_enter, now_s() - t_alloc0);
-    const u8 *d_text[2] = {src[0].base, src[1].base};
-
-    if (want_runs) TXCHK(hipMemsetAsync(&((SmallLayout *)ctx->small.p)->runs_cursor, 0, 8, st));
-    if (want_lines) { TXCHK(hipMemsetAsync(&((SmallLayout *)ctx->small.p)->lines_cursor, 0, 8, st)); if (out->line_off) out->line_off[0] = 0; }
-    CallInfo *d_ci = (CallInfo *)tw.info.p;
+    if (tc.want_runs) TXCHK(hipMemsetAsync(&((SmallLayout *)ctx->small.p)->runs_cursor, 0, 8, st));
+    if (tc.want_lines) { TXCHK(hipMemsetAsync(&((SmallLayout *)ctx->small.p)->lines_cursor, 0, 8, st)); if (out->line_off) out->line_off[0] = 0; }
     if (!ctx->back_stream) TXCHK(hipStreamCreateWithFlags(&ctx->back_stream, hipStreamNonBlocking));
-    // ---- the call's state (struct TextCall: it outlives the call behind BNS_TEXT_DEFER), under the names the rounds below use
-    tc = TextCall{};
-    tc.out = *out; tc.parse_only = parse_only; tc.want_runs = want_runs; tc.want_lines = want_lines; tc.on_device = on_device; tc.ns = ns;
-    for (u32 s = 0; s < ns; ++s) { tc.cons[s] = tc.open_cons0[s] = tc.cons_before_prev[s] = tc.rel[s] = src[s].rel; tc.up[s] = src[s].up; }
-    u32 &batch_no = tc.batch_no, (&cons)[2] = tc.cons, &acc_max_len = tc.acc_max_len, (&open_cons0)[2] = tc.open_cons0, &why = tc.why, &rounds = tc.rounds;
-    u64 &done_reads = tc.done_reads, &names_done = tc.names_done, &bases_done = tc.bases_done, &acc_reads = tc.acc_reads, &acc_bases = tc.acc_bases, &acc_names = tc.acc_names;
-    u64 &open_reads0 = tc.open_reads0, &open_names0 = tc.open_names0, &open_bases0 = tc.open_bases0;
-    int &status = tc.status;
-    float &ms_parse = tc.ms_parse;
-    const bool &rolled_back = tc.rolled_back;
-    auto flush_batch = [&]() -> int { return text_flush_batch(ctx, tw, tc); };
-    const u32 lim = limit >= text_bytes[0] ? 0xFFFFFFFFu : (u32)limit + src[0].rel;
-    const unsigned pgrid = (unsigned)ctx->n_cu * 8;
-    const u32 min_qual = tw.min_qual;
+    const bool final_text = (flags & BNS_TEXT_FINAL) != 0;
+    const u32 lim = limit >= text_bytes[0] ? 0xFFFFFFFFu : (u32)limit + tc.rel[0];      // (limit < bytes[0]: below 2^31, like rel + bytes)
     // One round = one parse over [cons, hi) of every stream, hi = what piece k has brought up -- cut to the window one parse may
-    // cover (of a pair of files the denser one is ahead of what its mate lets it hand over: its unparsed text waits, it does not grow
-    // the window) -- whose records are appended to the open batch.  k moves on with the uploads; when they are all up the rounds go on
+    // cover -- whose records are appended to the open batch.  k moves on with the uploads; when they are all up the rounds go on
     // until the text is used up.
-    const u32 window = (u32)std::min<u64>(range_cap - 64, 0x7FFFFFFFu);
     u32 k = 0;
-    for (;; ++rounds) {
+    for (;; ++tc.rounds) {
         // room for one more slice's worst case?  (else the open batch goes first)
-        if (acc_reads + slice_reads_cap > cap_reads || acc_bases + slice_bases_cap > cap_bases || acc_names + slice_bases_cap > cap_names) {
-            if ((rc = flush_batch()) != BNS_OK) return bail(rc);
-            if (rolled_back) break;
+        if (tc.acc_reads + plan.slice_reads_cap > plan.cap_reads || tc.acc_bases + plan.slice_bases_cap > plan.cap_bases || tc.acc_names + plan.slice_bases_cap > plan.cap_names) {
+            if ((rc = text_flush_batch(ctx, tw, tc)) != BNS_OK) return text_bail(ctx, tc, rc);
+            if (tc.rolled_back) break;
         }
         u32 hi[2] = {0, 0};
         bool last = true, capped = false;
         for (u32 s = 0; s < ns; ++s) {
-            hi[s] = up_to(s, k);
-            if (n_slices > 1 && hi[s] - cons[s] > window) { hi[s] = cons[s] + window; capped = true; }
-            if (hi[s] != src[s].end) last = false;
+            hi[s] = plan.up_to(s, k);
+            if (plan.n_slices > 1 && hi[s] - tc.cons[s] > plan.window) { hi[s] = tc.cons[s] + plan.window; capped = true; }
+            if (hi[s] != plan.s[s].end) last = false;
         }
         const int fin = (last && final_text) ? 1 : 0;
-        const u32 q = batch_no & 1u;                            // the set of result arrays the open batch writes
-        if (ctx->timing) TXCHK(hipEventRecord(tw.t0, st));
-        TXCHK(hipMemsetAsync(d_ci, 0, info_bytes, st));
-        ParseArgs pa{};
-        pa.ci = d_ci; pa.n_streams = ns; pa.final_text = fin; pa.trim_readno = (flags & BNS_TEXT_TRIM_READNO) ? 1 : 0;
-        u64 *st_words = (u64 *)((char *)tw.info.p + ((sizeof(CallInfo) + 63) & ~size_t(63)));
-        u32 max_tiles = 1;
-        for (u32 s = 0; s < ns; ++s) {
-            // (the piece that ends this slice -- and with it every piece in front of it: the copy stream is in order)
-            if (src[s].up) TXCHK(hipStreamWaitEvent(st, src[s].up->ev[std::min(src[s].j0 + k, src[s].j0 + src[s].n - 1)], 0));
-            StreamArgs &a = pa.s[s];
-            a.text = d_text[s]; a.lo = cons[s]; a.hi = hi[s];
-            a.tile0 = a.lo / TILE; a.n_tiles = a.hi > a.lo ? (a.hi - 1) / TILE - a.tile0 + 1 : 1;
-            a.cap_lines = cap_lines; a.cap_rec = cap_rec;
-            a.ls = (u32 *)tw.ls[s].p; a.line_off = (u32 *)tw.line_off[s].p;
-            u32 **cp[10] = {&a.cand, &a.c_next, &a.c_seq, &a.c_name, &a.c_line1, &a.c_single, &a.c_flags, &a.c_inside, &a.c_pos, &a.rec_cand};
-            for (int i = 0; i < 10; ++i) *cp[i] = (u32 *)tw.cand[s][i].p;
-            a.st_lines = st_words + s * st_tiles; a.st_groups = st_words + 2 * st_tiles + s * st_groups; a.st_compact = st_words + 2 * st_tiles + 2 * st_groups + s * st_cand;
-            max_tiles = std::max(max_tiles, a.n_tiles);
-        }
-        pa.st_offsets = st_words + 2 * st_tiles + 2 * st_groups + 2 * st_cand;
-        const u32 R0 = (u32)acc_reads;
-        // the slice's records go behind those the open batch holds: offsets from acc_bases on, names from names_done on
-        OffsetsOut oo{(u32 *)tw.seq_len[q].p + R0, (u64 *)tw.offsets.p + R0, acc_bases, (u32 *)tw.name_off[q].p + R0, (u32)names_done};
-        PackOut po{(const u64 *)tw.offsets.p + R0, R0, (u64 *)tw.words.p, (u32 *)tw.nmask.p, (const u32 *)tw.name_off[q].p + R0, (u32)(names_done - acc_names),
-                   (char *)tw.names[q].p, (u64 *)tw.pos64[q].p + R0, {src[0].rel, src[1].rel}};
-        const unsigned cgrid = (unsigned)std::min<u64>(pgrid, (u64)cap_rec / REC_BLOCK + 1), ogrid = (unsigned)std::min<u64>(256, slice_reads_cap / REC_BLOCK + 1);
-        hipLaunchKernelGGL(count_kernel, dim3(std::min<u32>(max_tiles, pgrid * 2), ns), dim3(256), 0, st, pa);
-        hipLaunchKernelGGL(write_kernel, dim3(std::min<u32>(max_tiles, pgrid * 2), ns), dim3(256), 0, st, pa);
-        hipLaunchKernelGGL(walk_kernel, dim3(pgrid, ns), dim3(256), 0, st, pa);
-        hipLaunchKernelGGL(compact_kernel, dim3(cgrid, ns), dim3(256), 0, st, pa, lim);
-        hipLaunchKernelGGL(offsets_kernel, dim3(ogrid), dim3(256), 0, st, pa, oo);
-        if (min_qual) hipLaunchKernelGGL(pack_text_minq_kernel, dim3(pgrid), dim3(256), 0, st, pa, po, 33u + min_qual);
-        else hipLaunchKernelGGL(pack_text_kernel, dim3(pgrid), dim3(256), 0, st, pa, po);
-        TXCHK(hipGetLastError());
-        if (ctx->timing) TXCHK(hipEventRecord(tw.t1, st));
-        TXCHK(hipMemcpyAsync(tw.h_info, d_ci, sizeof(CallInfo), hipMemcpyDeviceToHost, st));
-        TXCHK(hipStreamSynchronize(st));
-        const CallInfo ci = *tw.h_info;
-        if (ctx->timing) { float ms = 0; if (hipEventElapsedTime(&ms, tw.t0, tw.t1) == hipSuccess) ms_parse += ms; }
-        if (ci.why) { status = BNS_TEXT_IRREGULAR; why = ci.why; break; }
+        CallInfo ci;
+        if ((rc = text_parse_round(ctx, tw, tc, plan, k, hi, fin, flags, lim, ci)) != BNS_OK) return rc;      // (it has bailed)
+        if (ci.why) { tc.status = BNS_TEXT_IRREGULAR; tc.why = ci.why; break; }
         const u64 n_reads = ci.n_reads;
         if (n_reads == 0) {
             // nothing complete in this stretch: more text may complete it (the next slice is parsed together with this one).  At the
             // end of the text: a final text is done (blank lines; a pair whose one file has run out; headers behind the limit only);
             // otherwise the caller has handed over less than one record
-            if (!last && k + 1 < n_slices) { ++k; continue; }
-            if (!last && capped) { status = BNS_TEXT_NO_RECORD; break; }      // (a whole window without one complete record)
-            for (u32 s = 0; s < ns; ++s) cons[s] = ci.s[s].consumed;
-            const bool behind_limit = lim != 0xFFFFFFFFu && ci.s[0].n_hdr && cons[0] >= lim;
-            if (!fin && !behind_limit) status = BNS_TEXT_NO_RECORD;
+            if (!last && k + 1 < plan.n_slices) { ++k; continue; }
+            if (!last && capped) { tc.status = BNS_TEXT_NO_RECORD; break; }      // (a whole window without one complete record)
+            for (u32 s = 0; s < ns; ++s) tc.cons[s] = ci.s[s].consumed;
+            const bool behind_limit = lim != 0xFFFFFFFFu && ci.s[0].n_hdr && tc.cons[0] >= lim;
+            if (!fin && !behind_limit) tc.status = BNS_TEXT_NO_RECORD;
             break;
         }
-        if (done_reads + n_reads > cap_records || (out->names && names_done + ci.names_bytes > out->names_cap)) { status = BNS_TEXT_CAP; break; }
+        if (tc.done_reads + n_reads > cap_records || (out->names && tc.names_done + ci.names_bytes > out->names_cap)) { tc.status = BNS_TEXT_CAP; break; }
         // ---- the slice is the open batch's (a batch opens with its first slice)
-        if (acc_reads == 0) { open_reads0 = done_reads; open_names0 = names_done; open_bases0 = bases_done; for (u32 s = 0; s < ns; ++s) open_cons0[s] = cons[s]; }
-        acc_reads += n_reads; acc_bases += ci.total_bases; acc_names += ci.names_bytes; acc_max_len = std::max(acc_max_len, ci.max_len);
-        done_reads += n_reads; names_done += ci.names_bytes; bases_done += ci.total_bases;
-        for (u32 s = 0; s < ns; ++s) cons[s] = ci.s[s].consumed;
-        if (acc_reads >= batch_reads || acc_bases >= batch_bases || acc_names >= batch_names) {
-            if ((rc = flush_batch()) != BNS_OK) return bail(rc);
-            if (rolled_back) break;
+        if (tc.acc_reads == 0) {
+            tc.open_reads0 = tc.done_reads; tc.open_names0 = tc.names_done; tc.open_bases0 = tc.bases_done;
+            for (u32 s = 0; s < ns; ++s) tc.open_cons0[s] = tc.cons[s];
+        }
+        tc.acc_reads += n_reads; tc.acc_bases += ci.total_bases; tc.acc_names += ci.names_bytes; tc.acc_max_len = std::max(tc.acc_max_len, ci.max_len);
+        tc.done_reads += n_reads; tc.names_done += ci.names_bytes; tc.bases_done += ci.total_bases;
+        for (u32 s = 0; s < ns; ++s) tc.cons[s] = ci.s[s].consumed;
+        if (tc.acc_reads >= plan.batch_reads || tc.acc_bases >= plan.batch_bases || tc.acc_names >= plan.batch_names) {
+            if ((rc = text_flush_batch(ctx, tw, tc)) != BNS_OK) return text_bail(ctx, tc, rc);
+            if (tc.rolled_back) break;
         }
         // a stream that has handed over everything in front of the limit is done (the rest is the next stretch's)
-        if (lim != 0xFFFFFFFFu && cons[0] >= lim) break;
+        if (lim != 0xFFFFFFFFu && tc.cons[0] >= lim) break;
         if (last) break;
-        if (k + 1 < n_slices) ++k;
+        if (k + 1 < plan.n_slices) ++k;
     }
     if (flags & BNS_TEXT_DEFER) {
         // parsed and packed: the caller's host buffers are his again, the records are known; classify, the hit runs and every result
         // array wait for bns_text_finish (what a full batch made necessary on the way has been classified already)
-        if ((rc = text_give_back_uploads(ctx, tw, tc)) != BNS_OK) return bail(rc);
+        if ((rc = text_give_back_uploads(ctx, tw, tc)) != BNS_OK) return text_bail(ctx, tc, rc);
         tc.pending = true;
         text_fill_info(ctx, tc, info);
         return BNS_OK;
     }
-#undef TXCHK
     return text_wrap_up(ctx, tw, tc, info);
 }
 
@@ -1354,3 +1316,4 @@ int bns_text_finish(bns_ctx *ctx, bns_text_info *info)
 }
 
 }  // extern "C"
+#undef TXCHK
