@@ -433,59 +433,37 @@ class Context:
                                           _p(n_k, u32p)), "bns_encode_batch")
         return [kmers[int(offsets[r]):int(offsets[r]) + int(n_k[r])].copy() for r in range(n_reads)]
 
+    def _hashes(self, name, bases, offsets, args, tables, n_tables, words=1, per=1):
+        """The hashers' call `name`(h, bases, offsets, n, *args, *tables, out, counts): one array per sequence, (n,) uint64 or
+        (n, words).  words = u64 per value and per table entry, per = entries per base of the output buffer, tables = n_tables
+        character tables of 256 entries, or None."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        out = np.zeros(max(1, words * per * int(offsets[-1])), dtype=np.uint64)
+        cnt = np.zeros(n, dtype=np.uint32)
+        tabs = [] if tables is None else [np.ascontiguousarray(t, dtype=np.uint64).reshape(-1) for t in tables]
+        assert len(tabs) in (0, n_tables) and all(t.size == 256 * words for t in tabs)
+        self._chk(getattr(self.L, name)(self.h, bases.ctypes.data, _p(offsets, u64p), n, *args, *([_p(t, u64p) for t in tabs] or [None] * n_tables),
+                                        _p(out, u64p), _p(cnt, u32p)), name)
+        vals = (out[words * per * int(offsets[r]):words * (per * int(offsets[r]) + int(cnt[r]))] for r in range(n))
+        return [(v if words == 1 else v.reshape(-1, words)).copy() for v in vals]
+
     def rolling_hash(self, bases, offsets, k, canon=False, tables=None, w=0):
         """RollingHasher<u64>::for_each_hash over a batch (encoder.h:644-865): list of uint64 arrays.  w > k: with a window
         (minimizers of the hash stream by lex_score; the canonical path queues both strands' hashes).
         tables = (fwd[256], rc[256]) character tables, None = the default-seed tables (parity unpinned)."""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n = offsets.size - 1
-        per = 2 if (w > k and canon) else 1
-        out = np.zeros(max(1, per * int(offsets[-1])), dtype=np.uint64)
-        cnt = np.zeros(n, dtype=np.uint32)
-        tf = tr = None
-        if tables is not None:
-            tf = np.ascontiguousarray(tables[0], dtype=np.uint64); tr = np.ascontiguousarray(tables[1], dtype=np.uint64)
-            assert tf.size == 256 and tr.size == 256
-        self._chk(self.L.bns_rolling_hash_windowed_batch(self.h, bases.ctypes.data, _p(offsets, u64p), n, k, int(canon), int(w),
-                                                         _p(tf, u64p) if tf is not None else None, _p(tr, u64p) if tr is not None else None,
-                                                         _p(out, u64p), _p(cnt, u32p)), "bns_rolling_hash_windowed_batch")
-        return [out[per * int(offsets[r]):per * int(offsets[r]) + int(cnt[r])].copy() for r in range(n)]
+        return self._hashes("bns_rolling_hash_windowed_batch", bases, offsets, (k, int(canon), int(w)), tables, 2, 1, 2 if (w > k and canon) else 1)
 
     def rolling_hash128(self, bases, offsets, k, canon=False, tables=None, w=0):
         """RollingHasher<__uint128_t>::for_each_hash (w > k: with a window of w - k + 1 values): list of (n, 2) uint64 arrays
         [lo, hi], one per sequence.  tables = (fwd, rc), each 256 x (lo, hi) u64; None = the default-seed tables."""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n = offsets.size - 1
-        per = 2 if (w > k and canon) else 1
-        out = np.zeros(max(1, 2 * per * int(offsets[-1])), dtype=np.uint64)
-        cnt = np.zeros(n, dtype=np.uint32)
-        tf = tr = None
-        if tables is not None:
-            tf = np.ascontiguousarray(tables[0], dtype=np.uint64).reshape(-1); tr = np.ascontiguousarray(tables[1], dtype=np.uint64).reshape(-1)
-            assert tf.size == 512 and tr.size == 512
-        self._chk(self.L.bns_rolling_hash128_windowed_batch(self.h, bases.ctypes.data, _p(offsets, u64p), n, k, int(canon), int(w),
-                                                            _p(tf, u64p) if tf is not None else None, _p(tr, u64p) if tr is not None else None,
-                                                            _p(out, u64p), _p(cnt, u32p)), "bns_rolling_hash128_windowed_batch")
-        return [out[2 * per * int(offsets[r]):2 * (per * int(offsets[r]) + int(cnt[r]))].reshape(-1, 2).copy() for r in range(n)]
+        return self._hashes("bns_rolling_hash128_windowed_batch", bases, offsets, (k, int(canon), int(w)), tables, 2, 2, 2 if (w > k and canon) else 1)
 
     def for_each_hash(self, bases, offsets, k=0, canon=-1, table=None):
         """Encoder::for_each_hash over a batch (encoder.h:355-394, ntHash): list of uint64 arrays, one per sequence.
         k = 0: the encoder's k; canon = -1: the encoder's flag; table = 256 seeds in make_nthash_lut's geometry (None: published)."""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n = offsets.size - 1
-        out = np.zeros(max(1, int(offsets[-1])), dtype=np.uint64)
-        cnt = np.zeros(n, dtype=np.uint32)
-        t = None
-        if table is not None:
-            t = np.ascontiguousarray(table, dtype=np.uint64)
-            assert t.size == 256
-        self._chk(self.L.bns_for_each_hash_batch(self.h, bases.ctypes.data, _p(offsets, u64p), n, int(k), int(canon),
-                                                 _p(t, u64p) if t is not None else None, _p(out, u64p), _p(cnt, u32p)),
-                  "bns_for_each_hash_batch")
-        return [out[int(offsets[r]):int(offsets[r]) + int(cnt[r])].copy() for r in range(n)]
+        return self._hashes("bns_for_each_hash_batch", bases, offsets, (int(k), int(canon)), None if table is None else (table,), 1)
 
     def probe(self, kmers):
         """kh_get over a batch (khash64.h:250-263): (vals, found)."""

@@ -1,5 +1,6 @@
 // bns_api.hip -- the C ABI of include/bonsai_amd.h: context, HBM residency, and the entry points; classify, table load, build and
-// window sessions are thin forwards into bns_classify.hpp, bns_table_load.hpp, bns_build.hpp (+ bns_minimize.hpp) and bns_windows.hpp.
+// window sessions and the hash feeders (RollingHasher, ntHash) are thin forwards into bns_classify.hpp, bns_table_load.hpp, bns_build.hpp
+// (+ bns_minimize.hpp), bns_windows.hpp and bns_hashers.hpp.
 // Single translation unit for the device library: the kernels are included so their templates are visible.
 #include "../../include/bonsai_amd.h"
 #include "bns_kernels.hip"
@@ -247,6 +248,7 @@ int ready(bns_ctx *ctx, bool need_table, bool need_tax)
 #include "bns_minimize.hpp"
 #include "bns_table_load.hpp"
 #include "bns_windows.hpp"
+#include "bns_hashers.hpp"
 
 extern "C" {
 
@@ -1097,205 +1099,48 @@ int bns_encode_batch(bns_ctx *ctx, const char *bases, const uint64_t *offsets, u
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (n_reads == 0) return BNS_OK;
     const u64 total = offsets[n_reads];
-    if ((rc = ensure(ctx, ctx->st_bases, (size_t)total + 8)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_offsets, (size_t)(n_reads + 1) * 8)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_kmers, (size_t)total * 8 + 8)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_out[0], (size_t)n_reads * 4)) != BNS_OK) return rc;
-    hipStream_t st = ctx->stream;
-    if (total) HIPCHK(ctx, hipMemcpyAsync(ctx->st_bases.p, bases, (size_t)total, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->st_offsets.p, offsets, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-    rc = bns_encode_batch_device(ctx, (const char *)ctx->st_bases.p, (const u64 *)ctx->st_offsets.p, n_reads, total,
-                                 (u64 *)ctx->st_kmers.p, (u32 *)ctx->st_out[0].p, st);
-    if (rc != BNS_OK) return rc;
-    if (total && kmers) HIPCHK(ctx, hipMemcpyAsync(kmers, ctx->st_kmers.p, (size_t)total * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(n_kmers, ctx->st_out[0].p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return BNS_OK;
+    BNS_RC(ensure(ctx, ctx->st_kmers, (size_t)total * 8 + 8));
+    BNS_RC(ensure(ctx, ctx->st_out[0], (size_t)n_reads * 4));
+    BNS_RC(stage_batch(ctx, bases, offsets, n_reads));
+    BNS_RC(bns_encode_batch_device(ctx, (const char *)ctx->st_bases.p, (const u64 *)ctx->st_offsets.p, n_reads, total,
+                                   (u64 *)ctx->st_kmers.p, (u32 *)ctx->st_out[0].p, ctx->stream));
+    return fetch_values(ctx, kmers, ctx->st_kmers.p, (size_t)total * 8, n_kmers, ctx->st_out[0].p, n_reads);
 }
 
-// wy::WyRand stand-in for the default character tables: Lemire's wyhash64 (state += 0x60bee2bee120fc15, two 64x64->128
-// multiply folds), seeded as encoder.h:682-683 seeds the two hashers.  PARITY UNPINNED: pass real tables instead.
-static u64 wyhash64_next(u64 &state)
+// the hash feeders: bns_hashers.hpp
+int bns_rolling_tables(uint64_t seed1, uint64_t seed2, uint64_t *fwd, uint64_t *rc) { return rolling_tables<u64>(seed1, seed2, fwd, rc); }
+int bns_rolling_tables128(uint64_t seed1, uint64_t seed2, uint64_t *fwd_lohi, uint64_t *rc_lohi)
 {
-    state += 0x60bee2bee120fc15ULL;
-    unsigned __int128 t = (unsigned __int128)state * 0xa3b195354a39b70dULL;
-    const u64 m1 = (u64)(t >> 64) ^ (u64)t;
-    t = (unsigned __int128)m1 * 0x1b03738712fad5c9ULL;
-    return (u64)(t >> 64) ^ (u64)t;
+    return rolling_tables<W128>(seed1, seed2, fwd_lohi, rc_lohi);
 }
-
-int bns_rolling_tables(uint64_t seed1, uint64_t seed2, uint64_t *fwd, uint64_t *rc)
+int bns_nthash_tables(uint64_t seed_a, uint64_t seed_c, uint64_t seed_g, uint64_t seed_t, uint64_t *table256)
 {
-    if (!fwd || !rc) return BNS_ERR_ARG;
-    u64 sf = (u32)(seed1 ^ seed2), sr = (u32)((seed2 * seed1) ^ (seed2 ^ seed1));
-    for (int i = 0; i < 256; ++i) fwd[i] = wyhash64_next(sf);
-    for (int i = 0; i < 256; ++i) rc[i] = wyhash64_next(sr);
-    return BNS_OK;
+    return nthash_tables(seed_a, seed_c, seed_g, seed_t, table256);
 }
-
 int bns_rolling_hash_batch(bns_ctx *ctx, const char *bases, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, int canon,
                            const uint64_t *fwd_table, const uint64_t *rc_table, uint64_t *hashes, uint32_t *n_hashes)
 {
-    return bns_rolling_hash_windowed_batch(ctx, bases, offsets, n_seqs, k, canon, 0, fwd_table, rc_table, hashes, n_hashes);
+    return rolling_batch<u64>(ctx, bases, offsets, n_seqs, k, canon, 0, fwd_table, rc_table, hashes, n_hashes);
 }
-
 int bns_rolling_hash_windowed_batch(bns_ctx *ctx, const char *bases, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, int canon,
                                     uint32_t w, const uint64_t *fwd_table, const uint64_t *rc_table, uint64_t *hashes, uint32_t *n_hashes)
 {
-    if (!ctx || !offsets || !n_hashes) return BNS_ERR_ARG;
-    const bool windowed = w > k;                                          // RollingHasher::window(): w <= k_ means none (encoder.h:664-665)
-    const u32 per = (windowed && canon) ? 2u : 1u;                        // entries per base the buffers are laid out with
-    if (k == 0) return fail(ctx, BNS_ERR_ARG, "k must be positive");
-    if ((fwd_table == nullptr) != (rc_table == nullptr)) return fail(ctx, BNS_ERR_ARG, "pass both character tables or neither");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (n_seqs == 0) return BNS_OK;
-    const u64 total = offsets[n_seqs];
-    u64 tabs[512];
-    if (fwd_table) { std::memcpy(tabs, fwd_table, 2048); std::memcpy(tabs + 256, rc_table, 2048); }
-    else bns_rolling_tables(1337, 137, tabs, tabs + 256);                 // RollingHasher's default seeds (encoder.h:673)
-    int rc;
-    if ((rc = ensure(ctx, ctx->st_bases, (size_t)total + 8)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_offsets, (size_t)(n_seqs + 1) * 8)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_kmers, (size_t)total * 8 * per + 8)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_out[0], (size_t)n_seqs * 4)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_aux, sizeof(tabs))) != BNS_OK) return rc;
-    if (windowed) {
-        if ((rc = ensure(ctx, ctx->st_hits, (size_t)total * 8 * per + 8)) != BNS_OK) return rc;
-        if ((rc = ensure(ctx, ctx->st_out[1], (size_t)n_seqs * 4)) != BNS_OK) return rc;
-    }
-    hipStream_t st = ctx->stream;
-    if (total) HIPCHK(ctx, hipMemcpyAsync(ctx->st_bases.p, bases, (size_t)total, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->st_offsets.p, offsets, (size_t)(n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->st_aux.p, tabs, sizeof(tabs), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(rolling_hash_kernel, dim3(grid_for(ctx, n_seqs, 4)), dim3(256), 0, st, (const u8 *)ctx->st_bases.p,
-                       (const u64 *)ctx->st_offsets.p, (u64)n_seqs, (u32)k, canon ? 1 : 0, windowed ? 1 : 0, (const u64 *)ctx->st_aux.p,
-                       (const u64 *)ctx->st_aux.p + 256, (u64 *)ctx->st_kmers.p, (u32 *)ctx->st_out[0].p);
-    HIPCHK(ctx, hipGetLastError());
-    const void *d_res = ctx->st_kmers.p, *d_cnt = ctx->st_out[0].p;
-    if (windowed) {
-        hipLaunchKernelGGL(stream_window_kernel, dim3(grid_for(ctx, n_seqs, 4)), dim3(256), 0, st, (const u64 *)ctx->st_kmers.p,
-                           (const u32 *)ctx->st_out[0].p, (const u64 *)ctx->st_offsets.p, (u64)n_seqs, per, (u32)(w - k + 1),
-                           (u64 *)ctx->st_hits.p, (u32 *)ctx->st_out[1].p);
-        HIPCHK(ctx, hipGetLastError());
-        d_res = ctx->st_hits.p; d_cnt = ctx->st_out[1].p;
-    }
-    if (total && hashes) HIPCHK(ctx, hipMemcpyAsync(hashes, d_res, (size_t)total * 8 * per, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(n_hashes, d_cnt, (size_t)n_seqs * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return BNS_OK;
+    return rolling_batch<u64>(ctx, bases, offsets, n_seqs, k, canon, w, fwd_table, rc_table, hashes, n_hashes);
 }
-
-// make_nthash_lut's geometry (encoder.h:93-103): the base's seed at the letter (both cases), its complement's seed at
-// index (letter & 7), everything else 0.
-int bns_nthash_tables(uint64_t seed_a, uint64_t seed_c, uint64_t seed_g, uint64_t seed_t, uint64_t *table256)
-{
-    if (!table256) return BNS_ERR_ARG;
-    std::memset(table256, 0, 256 * sizeof(uint64_t));
-    table256[4] = table256['a'] = table256['A'] = seed_a;      // 'T' & 7 == 4: T's complement
-    table256[7] = table256['c'] = table256['C'] = seed_c;      // 'G' & 7 == 7
-    table256[3] = table256['g'] = table256['G'] = seed_g;      // 'C' & 7 == 3
-    table256[1] = table256['t'] = table256['T'] = seed_t;      // 'A' & 7 == 1
-    return BNS_OK;
-}
-
-int bns_for_each_hash_batch(bns_ctx *ctx, const char *bases, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, int canon,
-                            const uint64_t *table256, uint64_t *hashes, uint32_t *n_hashes)
-{
-    if (!ctx || !offsets || !n_hashes) return BNS_ERR_ARG;
-    if (k == 0) {                                             // encoder.h:357,362: k = 0 means the Spacer's k
-        if (!ctx->enc_set) return fail(ctx, BNS_ERR_STATE, "k = 0 takes the encoder's k: configure the encoder first (bns_set_encoder)");
-        k = ctx->k;
-    }
-    if (ctx->enc_set && ctx->spaced) return fail(ctx, BNS_ERR_ARG, "Can't for_each_hash for a spaced spacer");       // encoder.h:364
-    if (ctx->enc_set && ctx->win > ctx->c) return fail(ctx, BNS_ERR_ARG, "Can't for_each_hash for a windowed spacer"); // encoder.h:363
-    if (canon < 0) canon = (ctx->enc_set && ctx->canon) ? 1 : 0;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (n_seqs == 0) return BNS_OK;
-    const u64 total = offsets[n_seqs];
-    u64 tab[256];
-    if (table256) std::memcpy(tab, table256, sizeof(tab));
-    else bns_nthash_tables(0x3c8bfbb395c60474ULL, 0x3193c18562a02b4cULL, 0x20323ed082572324ULL, 0x295549f54be24456ULL, tab);   // ntHash's published seeds
-    int rc;
-    if ((rc = ensure(ctx, ctx->st_bases, (size_t)total + 8)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_offsets, (size_t)(n_seqs + 1) * 8)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_kmers, (size_t)total * 8 + 8)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_out[0], (size_t)n_seqs * 4)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_aux, sizeof(tab))) != BNS_OK) return rc;
-    hipStream_t st = ctx->stream;
-    if (total) HIPCHK(ctx, hipMemcpyAsync(ctx->st_bases.p, bases, (size_t)total, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->st_offsets.p, offsets, (size_t)(n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->st_aux.p, tab, sizeof(tab), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(nthash_kernel, dim3(grid_for(ctx, n_seqs, 4)), dim3(256), 0, st, (const u8 *)ctx->st_bases.p,
-                       (const u64 *)ctx->st_offsets.p, (u64)n_seqs, (u32)k, canon ? 1 : 0, (const u64 *)ctx->st_aux.p,
-                       (u64 *)ctx->st_kmers.p, (u32 *)ctx->st_out[0].p);
-    HIPCHK(ctx, hipGetLastError());
-    if (total && hashes) HIPCHK(ctx, hipMemcpyAsync(hashes, ctx->st_kmers.p, (size_t)total * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(n_hashes, ctx->st_out[0].p, (size_t)n_seqs * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return BNS_OK;
-}
-
-// CharacterHash<__uint128_t>'s default tables: two draws per entry, of which only the second survives (its 128-bit mask is
-// truncated to 64 bits on the way into the uint64_t member maxval_, characterhash.h:82-97) -- hi = 0 in every entry.
-int bns_rolling_tables128(uint64_t seed1, uint64_t seed2, uint64_t *fwd_lohi, uint64_t *rc_lohi)
-{
-    if (!fwd_lohi || !rc_lohi) return BNS_ERR_ARG;
-    u64 sf = (u32)(seed1 ^ seed2), sr = (u32)((seed2 * seed1) ^ (seed2 ^ seed1));
-    for (int i = 0; i < 256; ++i) { (void)wyhash64_next(sf); fwd_lohi[2 * i] = wyhash64_next(sf); fwd_lohi[2 * i + 1] = 0; }
-    for (int i = 0; i < 256; ++i) { (void)wyhash64_next(sr); rc_lohi[2 * i] = wyhash64_next(sr); rc_lohi[2 * i + 1] = 0; }
-    return BNS_OK;
-}
-
 int bns_rolling_hash128_batch(bns_ctx *ctx, const char *bases, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, int canon,
                               const uint64_t *fwd_lohi, const uint64_t *rc_lohi, uint64_t *hashes_lohi, uint32_t *n_hashes)
 {
-    return bns_rolling_hash128_windowed_batch(ctx, bases, offsets, n_seqs, k, canon, 0, fwd_lohi, rc_lohi, hashes_lohi, n_hashes);
+    return rolling_batch<W128>(ctx, bases, offsets, n_seqs, k, canon, 0, fwd_lohi, rc_lohi, hashes_lohi, n_hashes);
 }
-
 int bns_rolling_hash128_windowed_batch(bns_ctx *ctx, const char *bases, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, int canon,
                                        uint32_t w, const uint64_t *fwd_lohi, const uint64_t *rc_lohi, uint64_t *hashes_lohi, uint32_t *n_hashes)
 {
-    if (!ctx || !offsets || !n_hashes) return BNS_ERR_ARG;
-    const bool windowed = w > k;                                          // RollingHasher::window(): w <= k_ means none (encoder.h:664-665)
-    const u32 per = (windowed && canon) ? 2u : 1u;
-    if (k == 0) return fail(ctx, BNS_ERR_ARG, "k must be positive");
-    if ((fwd_lohi == nullptr) != (rc_lohi == nullptr)) return fail(ctx, BNS_ERR_ARG, "pass both character tables or neither");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (n_seqs == 0) return BNS_OK;
-    const u64 total = offsets[n_seqs];
-    std::vector<u64> tabs(1024);
-    if (fwd_lohi) { std::memcpy(tabs.data(), fwd_lohi, 4096); std::memcpy(tabs.data() + 512, rc_lohi, 4096); }
-    else bns_rolling_tables128(1337, 137, tabs.data(), tabs.data() + 512);
-    int rc;
-    if ((rc = ensure(ctx, ctx->st_bases, (size_t)total + 8)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_offsets, (size_t)(n_seqs + 1) * 8)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_kmers, (size_t)total * 16 * per + 16)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_out[0], (size_t)n_seqs * 4)) != BNS_OK) return rc;
-    if ((rc = ensure(ctx, ctx->st_aux, 8192)) != BNS_OK) return rc;
-    if (windowed) {
-        if ((rc = ensure(ctx, ctx->st_hits, (size_t)total * 16 * per + 16)) != BNS_OK) return rc;
-        if ((rc = ensure(ctx, ctx->st_out[1], (size_t)n_seqs * 4)) != BNS_OK) return rc;
-    }
-    hipStream_t st = ctx->stream;
-    if (total) HIPCHK(ctx, hipMemcpyAsync(ctx->st_bases.p, bases, (size_t)total, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->st_offsets.p, offsets, (size_t)(n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->st_aux.p, tabs.data(), 8192, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(rolling_hash128_kernel, dim3(grid_for(ctx, n_seqs, 4)), dim3(256), 0, st, (const u8 *)ctx->st_bases.p,
-                       (const u64 *)ctx->st_offsets.p, (u64)n_seqs, (u32)k, canon ? 1 : 0, windowed ? 1 : 0, (const u64 *)ctx->st_aux.p,
-                       (const u64 *)ctx->st_aux.p + 512, (u64 *)ctx->st_kmers.p, (u32 *)ctx->st_out[0].p);
-    HIPCHK(ctx, hipGetLastError());
-    const void *d_res = ctx->st_kmers.p, *d_cnt = ctx->st_out[0].p;
-    if (windowed) {
-        hipLaunchKernelGGL(stream_window128_kernel, dim3(grid_for(ctx, n_seqs, 4)), dim3(256), 0, st, (const u64 *)ctx->st_kmers.p,
-                           (const u32 *)ctx->st_out[0].p, (const u64 *)ctx->st_offsets.p, (u64)n_seqs, per, (u32)(w - k + 1),
-                           (u64 *)ctx->st_hits.p, (u32 *)ctx->st_out[1].p);
-        HIPCHK(ctx, hipGetLastError());
-        d_res = ctx->st_hits.p; d_cnt = ctx->st_out[1].p;
-    }
-    if (total && hashes_lohi) HIPCHK(ctx, hipMemcpyAsync(hashes_lohi, d_res, (size_t)total * 16 * per, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(n_hashes, d_cnt, (size_t)n_seqs * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return BNS_OK;
+    return rolling_batch<W128>(ctx, bases, offsets, n_seqs, k, canon, w, fwd_lohi, rc_lohi, hashes_lohi, n_hashes);
+}
+int bns_for_each_hash_batch(bns_ctx *ctx, const char *bases, const uint64_t *offsets, uint64_t n_seqs, uint32_t k, int canon,
+                            const uint64_t *table256, uint64_t *hashes, uint32_t *n_hashes)
+{
+    return nthash_batch(ctx, bases, offsets, n_seqs, k, canon, table256, hashes, n_hashes);
 }
 
 int bns_probe_device(bns_ctx *ctx, const uint64_t *d_kmers, uint64_t n, uint32_t *d_vals, uint8_t *d_found, void *stream)

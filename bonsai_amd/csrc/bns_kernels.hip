@@ -7,6 +7,7 @@
 //   probe_kernel      kh_get over a batch of keys                                (khash64.h:250-263)
 //   rebucket_kernel   khash arrays -> 64-byte bucket layout (same key->value map)
 //   build_*           update_lca_map on device                                   (feature_min.h:205-228)
+// The hash feeders (RollingHasher<u64 | u128> with and without a window, Encoder::for_each_hash) are not here: bns_hashers.hpp.
 //
 // HBM-bound integer work: no MFMA.  The levers are one 64-byte sector per lookup (bucket layout, quad-
 // cooperative loads), coalesced 2-bit read words, wave ballots for the vote, and an Euler-interval
@@ -2068,371 +2069,6 @@ __global__ __launch_bounds__(256) void hit_runs_kernel(const u32 *__restrict__ h
                 if (i0 == 0) break;
             }
         }
-    }
-}
-
-// =====================================================================================================
-// RollingHasher<u64, CyclicHash<u64>> without a window (encoder.h:644-865, rollinghash/cyclichash.h):
-//   forward   H_j = rotl1(H_{j-1}) ^ rotl_{k%64}(T[s_{j-k}]) ^ T[s_j]
-//   reverse   R_j = rotr1(R_{j-1} ^ rotl_{k%64}(Trc[rc s_j]) ^ Trc[rc s_{j-k}])        (canonical path: emits min(H, R))
-// Both recurrences are linear over GF(2) up to a rotation, so rotating position j's term by -j (forward) / +(j-1)
-// (reverse) turns them into plain prefix XORs: one wavefront per sequence scans 64 positions per step.  The start
-// values per segment (a segment = the run of valid characters the reference restarts on, k + 1 characters after an
-// invalid one) are a k-term XOR for H and, for R, the reference's fill that eats the window's LAST base's complement
-// k times (encoder.h:721).  The 256-entry character tables are an argument (parity unpinned).
-// =====================================================================================================
-__device__ __forceinline__ u64 rotl64v(u64 x, u32 r) { r &= 63u; return r ? (x << r) | (x >> (64u - r)) : x; }
-__device__ __forceinline__ u64 rotr64v(u64 x, u32 r) { r &= 63u; return r ? (x >> r) | (x << (64u - r)) : x; }
-__device__ __forceinline__ u64 wave_xor_scan(u64 v)                     // inclusive prefix XOR over the wavefront
-{
-    const int lane = lane_id();
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const u32 lo = (u32)__shfl_up((int)(u32)v, off), hi = (u32)__shfl_up((int)(u32)(v >> 32), off);
-        if (lane >= off) v ^= ((u64)hi << 32) | lo;
-    }
-    return v;
-}
-__device__ __forceinline__ u64 wave_xor_all(u64 v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-        v ^= ((u64)(u32)__shfl_xor((int)(u32)(v >> 32), off) << 32) | (u32)__shfl_xor((int)(u32)v, off);
-    return v;
-}
-
-__global__ __launch_bounds__(256) void rolling_hash_kernel(const u8 *__restrict__ bases, const u64 *__restrict__ offsets, u64 n_seqs,
-                                                           u32 k, int canon, int raw, const u64 *__restrict__ tf, const u64 *__restrict__ tr,
-                                                           u64 *__restrict__ out, u32 *__restrict__ n_out)
-{
-    // raw (the input of stream_window_kernel): the canonical path stores BOTH strands' hashes, forward then reverse, two
-    // entries per position (what the windowed RollingHasher queues, encoder.h:724-725,730-731) instead of their minimum
-    const u32 lane = threadIdx.x & 63u;
-    const u64 n_waves = (u64)gridDim.x * 4;
-    const u32 myr = k & 63u;
-    const bool both = raw && canon;
-    const u64 per = both ? 2 : 1;
-    for (u64 q = (u64)blockIdx.x * 4 + (threadIdx.x >> 6); q < n_seqs; q += n_waves) {
-        const u8 *s = bases + offsets[q];
-        const u64 l = offsets[q + 1] - offsets[q];
-        u64 *o = out + per * offsets[q];
-        u64 n = 0;                                                       // values emitted so far (wave-uniform)
-        auto code_at = [&](u64 i, u32 &bad) -> u32 { return base_code(s[i], bad); };
-        u64 r = 0;                                                       // segment start
-        while (l >= k && r + k <= l) {
-            // first invalid character at or after r
-            u64 inv = l;
-            for (u64 c0 = r; c0 < l && inv == l; c0 += 64) {
-                u32 bad = 0;
-                if (c0 + lane < l) (void)code_at(c0 + lane, bad);
-                const u64 m = __builtin_amdgcn_ballot_w64(bad != 0);
-                if (m) inv = c0 + (u64)__builtin_ctzll(m);
-            }
-            if (inv >= r + k) {                                          // the fill completes: values for j = r+k-1 .. inv-1
-                const u64 j0 = r + k - 1;
-                // H_{j0} = XOR_t rotl^{k-1-t}(T[s_{r+t}]);  R_{j0} = XOR_t rotl^{t}(Trc[rc s_{j0}])
-                u64 h0 = 0, g0 = 0;
-                u32 bad;
-                const u64 tlast = canon ? tr[3u - code_at(j0, bad)] : 0ULL;
-                for (u32 t = lane; t < k; t += 64) {
-                    h0 ^= rotl64v(tf[code_at(r + t, bad)], k - 1u - t);
-                    g0 ^= rotl64v(tlast, t);
-                }
-                h0 = wave_xor_all(h0); g0 = wave_xor_all(g0);
-                if (lane == 0) { if (both) { o[2 * n] = h0; o[2 * n + 1] = g0; } else o[n] = canon ? (h0 < g0 ? h0 : g0) : h0; }
-                // normalised running values: P = rotr^{j}(H_j), Q = rotl^{j}(R_j)
-                u64 P = rotr64v(h0, (u32)j0), Q = rotl64v(g0, (u32)j0);
-                for (u64 c0 = j0 + 1; c0 < inv; c0 += 64) {
-                    const u64 j = c0 + lane;
-                    u64 ef = 0, er = 0;
-                    if (j < inv) {
-                        const u32 cin = code_at(j, bad), cout = code_at(j - k, bad);
-                        ef = rotr64v(rotl64v(tf[cout], myr) ^ tf[cin], (u32)j);
-                        if (canon) er = rotl64v(rotl64v(tr[3u - cin], myr) ^ tr[3u - cout], (u32)(j - 1));
-                    }
-                    const u64 pf = P ^ wave_xor_scan(ef), qr = Q ^ wave_xor_scan(er);
-                    if (j < inv) {
-                        const u64 hj = rotl64v(pf, (u32)j), gj = rotr64v(qr, (u32)j);
-                        const u64 at = n + 1 + (j - (j0 + 1));
-                        if (both) { o[2 * at] = hj; o[2 * at + 1] = gj; } else o[at] = canon ? (hj < gj ? hj : gj) : hj;
-                    }
-                    P = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(pf >> 32), 63) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)pf, 63);
-                    Q = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(qr >> 32), 63) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)qr, 63);
-                }
-                n += inv - j0;
-            }
-            if (inv >= l) break;
-            if (canon && inv + 2 * (u64)k >= l) break;                   // encoder.h:714
-            r = inv + (u64)k + 1;                                        // i += k_, then the loop's ++i
-        }
-        if (lane == 0) n_out[q] = (u32)(per * n);
-    }
-}
-
-// RollingHasher<__uint128_t, CyclicHash<__uint128_t>> without a window (the instantiation test/encoding.cpp:152 constructs): the
-// same two recurrences over a 128-bit word.  A value is a (lo, hi) pair of u64; rotations are 128-bit, myr = k % 128; the prefix
-// XOR runs over both halves.  Tables: 256 entries x (lo, hi).  Same segment rules as rolling_hash_kernel.
-struct W128 { u64 lo, hi; };
-__device__ __forceinline__ W128 operator^(W128 a, W128 b) { return W128{a.lo ^ b.lo, a.hi ^ b.hi}; }
-__device__ __forceinline__ bool less128(W128 a, W128 b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
-__device__ __forceinline__ W128 rotl128v(W128 x, u32 r)
-{
-    r &= 127u;
-    if (r >= 64u) { const u64 t = x.lo; x.lo = x.hi; x.hi = t; r -= 64u; }
-    if (r == 0u) return x;
-    return W128{(x.lo << r) | (x.hi >> (64u - r)), (x.hi << r) | (x.lo >> (64u - r))};
-}
-__device__ __forceinline__ W128 rotr128v(W128 x, u32 r) { return rotl128v(x, 128u - (r & 127u)); }
-__device__ __forceinline__ W128 ld128(const u64 *t, u32 i) { return W128{t[2u * i], t[2u * i + 1u]}; }
-__device__ __forceinline__ u64 bcast63(u64 v)
-{
-    return ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(v >> 32), 63) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)v, 63);
-}
-// raw (the input of stream_window128_kernel): the canonical path stores BOTH strands' values, forward then reverse, as separate
-// entries (the windowed hasher queues them one after the other, encoder.h:724-725); n_out counts entries.
-__global__ __launch_bounds__(256) void rolling_hash128_kernel(const u8 *__restrict__ bases, const u64 *__restrict__ offsets, u64 n_seqs,
-                                                              u32 k, int canon, int raw, const u64 *__restrict__ tf, const u64 *__restrict__ tr,
-                                                              u64 *__restrict__ out, u32 *__restrict__ n_out)
-{
-    const u32 lane = threadIdx.x & 63u;
-    const u64 n_waves = (u64)gridDim.x * 4;
-    const u32 myr = k & 127u;
-    const bool both = raw && canon;
-    for (u64 q = (u64)blockIdx.x * 4 + (threadIdx.x >> 6); q < n_seqs; q += n_waves) {
-        const u8 *s = bases + offsets[q];
-        const u64 l = offsets[q + 1] - offsets[q];
-        u64 *o = out + (both ? 4 : 2) * offsets[q];
-        u64 n = 0;
-        auto code_at = [&](u64 i, u32 &bad) -> u32 { return base_code(s[i], bad); };
-        auto put = [&](u64 at, W128 h, W128 g) {
-            if (both) { o[4 * at] = h.lo; o[4 * at + 1] = h.hi; o[4 * at + 2] = g.lo; o[4 * at + 3] = g.hi; return; }
-            const W128 v = canon ? (less128(h, g) ? h : g) : h; o[2 * at] = v.lo; o[2 * at + 1] = v.hi;
-        };
-        u64 r = 0;
-        while (l >= k && r + k <= l) {
-            u64 inv = l;
-            for (u64 c0 = r; c0 < l && inv == l; c0 += 64) {
-                u32 bad = 0;
-                if (c0 + lane < l) (void)code_at(c0 + lane, bad);
-                const u64 m = __builtin_amdgcn_ballot_w64(bad != 0);
-                if (m) inv = c0 + (u64)__builtin_ctzll(m);
-            }
-            if (inv >= r + k) {
-                const u64 j0 = r + k - 1;
-                W128 h0{0, 0}, g0{0, 0};
-                u32 bad;
-                const W128 tlast = canon ? ld128(tr, 3u - code_at(j0, bad)) : W128{0, 0};
-                for (u32 t = lane; t < k; t += 64) {
-                    h0 = h0 ^ rotl128v(ld128(tf, code_at(r + t, bad)), k - 1u - t);
-                    g0 = g0 ^ rotl128v(tlast, t);
-                }
-                h0 = W128{wave_xor_all(h0.lo), wave_xor_all(h0.hi)}; g0 = W128{wave_xor_all(g0.lo), wave_xor_all(g0.hi)};
-                if (lane == 0) put(n, h0, g0);
-                W128 P = rotr128v(h0, (u32)j0), Q = rotl128v(g0, (u32)j0);
-                for (u64 c0 = j0 + 1; c0 < inv; c0 += 64) {
-                    const u64 j = c0 + lane;
-                    W128 ef{0, 0}, er{0, 0};
-                    if (j < inv) {
-                        const u32 cin = code_at(j, bad), cout = code_at(j - k, bad);
-                        ef = rotr128v(rotl128v(ld128(tf, cout), myr) ^ ld128(tf, cin), (u32)j);
-                        if (canon) er = rotl128v(rotl128v(ld128(tr, 3u - cin), myr) ^ ld128(tr, 3u - cout), (u32)(j - 1));
-                    }
-                    const W128 pf = P ^ W128{wave_xor_scan(ef.lo), wave_xor_scan(ef.hi)}, qr = Q ^ W128{wave_xor_scan(er.lo), wave_xor_scan(er.hi)};
-                    if (j < inv) put(n + 1 + (j - (j0 + 1)), rotl128v(pf, (u32)j), rotr128v(qr, (u32)j));
-                    P = W128{bcast63(pf.lo), bcast63(pf.hi)};
-                    Q = W128{bcast63(qr.lo), bcast63(qr.hi)};
-                }
-                n += inv - j0;
-            }
-            if (inv >= l) break;
-            if (canon && inv + 2 * (u64)k >= l) break;                   // encoder.h:714
-            r = inv + (u64)k + 1;
-        }
-        if (lane == 0) n_out[q] = (u32)(both ? 2 * n : n);
-    }
-}
-
-// QueueMap over a finished stream of 128-bit values ((lo, hi) pairs): stream_window_kernel for RollingHasher<__uint128_t> with a
-// window.  score = lex_score128 (the reference's is sketch's CEHasher, un-vendored: restated, parity unpinned -- the number of
-// values, which is what test/encoding.cpp:152-156 pins, does not depend on it).  `per` = entries per base of the buffer layout.
-__device__ __forceinline__ u64 lex_score128(u64 lo, u64 hi) { return kmer_score(lo ^ kmer_score(hi, 0), 0); }
-__global__ __launch_bounds__(256) void stream_window128_kernel(const u64 *__restrict__ in, const u32 *__restrict__ n_in, const u64 *__restrict__ offsets,
-                                                               u64 n_seqs, u32 per, u32 ws, u64 *__restrict__ out, u32 *__restrict__ n_out)
-{
-    const u32 lane = threadIdx.x & 63u;
-    const u64 n_waves = (u64)gridDim.x * 4;
-    for (u64 q = (u64)blockIdx.x * 4 + (threadIdx.x >> 6); q < n_seqs; q += n_waves) {
-        const u64 *v = in + 2ULL * per * offsets[q];
-        u64 *o = out + 2ULL * per * offsets[q];
-        const u32 n = n_in[q];
-        u32 emitted = 0;
-        auto less = [](u64 sa, u64 alo, u64 ahi, u64 sb, u64 blo, u64 bhi) { return sa < sb || (sa == sb && (ahi < bhi || (ahi == bhi && alo < blo))); };
-        if (n >= ws) {
-            const u32 nw = n - ws + 1u;
-            for (u32 i0 = 0; i0 < nw; i0 += 64u) {
-                const u32 i = i0 + lane;
-                u64 blo = ~0ULL, bhi = ~0ULL, bs = ~0ULL;
-                if (i < nw) {
-                    blo = v[2 * i]; bhi = v[2 * i + 1]; bs = lex_score128(blo, bhi);
-                    for (u32 j = 1; j < ws; ++j) {
-                        const u64 elo = v[2 * (i + j)], ehi = v[2 * (i + j) + 1], sc = lex_score128(elo, ehi);
-                        if (less(sc, elo, ehi, bs, blo, bhi)) { bs = sc; blo = elo; bhi = ehi; }
-                    }
-                }
-                const bool on = i < nw && !(blo == ~0ULL && bhi == ~0ULL);
-                const u64 vm = ballot64(on);
-                if (on) { const u32 at = emitted + (u32)__popcll(vm & lanemask_lt()); o[2 * at] = blo; o[2 * at + 1] = bhi; }
-                emitted += (u32)__popcll(vm);
-            }
-        } else if (n) {
-            if (lane == 0) {                                   // (a stream shorter than its window: rare and short -- one lane)
-                u64 blo = v[0], bhi = v[1], bs = lex_score128(blo, bhi);
-                for (u32 i = 1; i < n; ++i) {
-                    const u64 elo = v[2 * i], ehi = v[2 * i + 1], sc = lex_score128(elo, ehi);
-                    if (less(sc, elo, ehi, bs, blo, bhi)) { bs = sc; blo = elo; bhi = ehi; }
-                }
-                o[0] = blo; o[1] = bhi;                        // (max_in_queue().el_ is emitted as is)
-            }
-            emitted = 1;
-        }
-        if (lane == 0) n_out[q] = emitted;
-    }
-}
-
-// =====================================================================================================
-// Encoder::for_each_hash (encoder.h:355-394): ntHash of every k-window the reference's loop visits.  One wavefront per
-// sequence.  The loop, in closed form: for every maximal run [a, b) of A/C/G/T (either case; a NUL byte ends the string,
-// encoder.h:371-377) with b - a >= k, the windows a .. b-k in order -- except that a run whose FIRST window ends exactly at
-// the end of the string emits nothing (`if(*p2 == 0) return;` is tested before `p2 - p == k`, encoder.h:378-379).
-// NTC64 (bcgsc/ntHash, un-vendored: restated from the published definition, Mohamadi et al. 2016, as ntHash 1.0.x ships it):
-//   forward  fh(w) = XOR_j rol^{k-1-j}(T[s_j])      rolling  fh' = rol1(fh) ^ rol^k(T[out]) ^ T[in]
-//   reverse  rh(w) = XOR_j rol^{j}(T[s_j & 7])      rolling  rh' = ror1(rh ^ T[out & 7] ^ rol^k(T[in & 7]))
-//   (the complement's seed sits at index c & 7 of the same table: A&7 = 1 holds T's seed, C&7 = 3 G's, G&7 = 7 C's,
-//    T&7 = 4 A's -- the geometry make_nthash_lut builds in-tree, encoder.h:93-103);  canonical value = min(fh, rh).
-// Both rolling forms are prefix XORs after rotating window i's term by -i / +i, as in rolling_hash_kernel.
-// The 256-entry table is an argument (parity unpinned: SURVEY F10).
-// =====================================================================================================
-__global__ __launch_bounds__(256) void nthash_kernel(const u8 *__restrict__ bases, const u64 *__restrict__ offsets, u64 n_seqs,
-                                                     u32 k, int canon, const u64 *__restrict__ T, u64 *__restrict__ out, u32 *__restrict__ n_out)
-{
-    const u32 lane = threadIdx.x & 63u;
-    const u64 n_waves = (u64)gridDim.x * 4;
-    const u32 kr = k & 63u;
-    for (u64 q = (u64)blockIdx.x * 4 + (threadIdx.x >> 6); q < n_seqs; q += n_waves) {
-        const u8 *s = bases + offsets[q];
-        u64 l = offsets[q + 1] - offsets[q];
-        u64 *o = out + offsets[q];
-        u64 n = 0;
-        auto invalid = [&](u64 i) -> bool { u32 bad; (void)base_code(s[i], bad); return bad != 0; };
-        u64 a = 0;                                                       // scan position
-        while (a + k <= l) {
-            // first valid character at or after a (a NUL ends the string), then the end of its run
-            u64 b = l;
-            bool found_start = false;
-            for (u64 c0 = a; c0 < l; c0 += 64) {
-                const bool in = c0 + lane < l;
-                const u8 ch = in ? s[c0 + lane] : (u8)1;
-                const u64 nul = __builtin_amdgcn_ballot_w64(in && ch == 0);
-                u64 inv = __builtin_amdgcn_ballot_w64(in && invalid(c0 + lane));
-                if (nul) { const int z = __builtin_ctzll(nul); l = c0 + (u64)z; inv &= (1ULL << z) - 1ULL; }
-                const u64 within = (l - c0 >= 64) ? ~0ULL : ((1ULL << (l - c0)) - 1ULL);
-                if (!found_start) {
-                    const u64 ok = ~inv & within;
-                    if (!ok) { if (nul) break; continue; }
-                    const int f = __builtin_ctzll(ok);
-                    a = c0 + (u64)f; found_start = true;
-                    inv &= ~((2ULL << f) - 1ULL);                        // invalid characters after the start only
-                }
-                if (inv & within) { b = c0 + (u64)__builtin_ctzll(inv & within); break; }
-                if (nul) break;
-            }
-            if (!found_start) break;
-            if (b > l) b = l;
-            if (b - a >= (u64)k && !(a + k == l)) {
-                u64 fh = 0, rh = 0;
-                for (u32 t = lane; t < k; t += 64) {
-                    const u8 ch = s[a + t];
-                    fh ^= rotl64v(T[ch], k - 1u - t);
-                    rh ^= rotl64v(T[ch & 7u], t);
-                }
-                fh = wave_xor_all(fh); rh = wave_xor_all(rh);
-                if (lane == 0) o[n] = canon ? (rh < fh ? rh : fh) : fh;
-                u64 P = rotr64v(fh, (u32)a), Q = rotl64v(rh, (u32)a);
-                const u64 last = b - k;                                  // last window of the run
-                for (u64 c0 = a + 1; c0 <= last; c0 += 64) {
-                    const u64 i = c0 + lane;
-                    u64 ef = 0, er = 0;
-                    if (i <= last) {
-                        const u8 cout = s[i - 1], cin = s[i + k - 1];
-                        ef = rotr64v(rotl64v(T[cout], kr) ^ T[cin], (u32)i);
-                        er = rotl64v(T[cout & 7u] ^ rotl64v(T[cin & 7u], kr), (u32)(i - 1));
-                    }
-                    const u64 pf = P ^ wave_xor_scan(ef), qr = Q ^ wave_xor_scan(er);
-                    if (i <= last) {
-                        const u64 f = rotl64v(pf, (u32)i), r = rotr64v(qr, (u32)i);
-                        o[n + (i - a)] = canon ? (r < f ? r : f) : f;
-                    }
-                    P = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(pf >> 32), 63) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)pf, 63);
-                    Q = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(qr >> 32), 63) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)qr, 63);
-                }
-                n += last - a + 1;
-            }
-            if (b >= l) break;
-            a = b + 1;
-        }
-        if (lane == 0) n_out[q] = (u32)n;
-    }
-}
-
-// QueueMap over a finished stream (qmap.h:79-87 as RollingHasher uses it, encoder.h:706-710,771-776,735-736,794-795): window i
-// = entries i .. i+ws-1 of sequence q's stream, its value the entry with the smallest (lex_score(v), v); a value equal to
-// ENCODE_OVERFLOW is not emitted; a stream shorter than the window gives one value, its minimum.  `per` = entries per base
-// the stream buffers are laid out with (sequence q starts at per * offsets[q]).  One wavefront per sequence.
-__global__ __launch_bounds__(256) void stream_window_kernel(const u64 *__restrict__ in, const u32 *__restrict__ n_in, const u64 *__restrict__ offsets,
-                                                            u64 n_seqs, u32 per, u32 ws, u64 *__restrict__ out, u32 *__restrict__ n_out)
-{
-    const u32 lane = threadIdx.x & 63u;
-    const u64 n_waves = (u64)gridDim.x * 4;
-    for (u64 q = (u64)blockIdx.x * 4 + (threadIdx.x >> 6); q < n_seqs; q += n_waves) {
-        const u64 *v = in + (u64)per * offsets[q];
-        u64 *o = out + (u64)per * offsets[q];
-        const u32 n = n_in[q];
-        u32 emitted = 0;
-        auto less = [](u64 sa, u64 a, u64 sb, u64 b) { return sa < sb || (sa == sb && a < b); };
-        if (n >= ws) {
-            const u32 nw = n - ws + 1u;
-            for (u32 i0 = 0; i0 < nw; i0 += 64u) {
-                const u32 i = i0 + lane;
-                u64 be = ~0ULL, bs = ~0ULL;
-                if (i < nw) {
-                    be = v[i]; bs = kmer_score(be, 0);
-                    for (u32 j = 1; j < ws; ++j) {
-                        const u64 e = v[i + j], sc = kmer_score(e, 0);
-                        if (less(sc, e, bs, be)) { bs = sc; be = e; }
-                    }
-                }
-                const bool on = i < nw && be != ~0ULL;
-                const u64 vm = ballot64(on);
-                if (on) o[emitted + (u32)__popcll(vm & lanemask_lt())] = be;
-                emitted += (u32)__popcll(vm);
-            }
-        } else if (n) {
-            u64 be = ~0ULL, bs = ~0ULL;
-            bool have = false;
-            for (u32 i = lane; i < n; i += 64u) {
-                const u64 e = v[i], sc = kmer_score(e, 0);
-                if (!have || less(sc, e, bs, be)) { bs = sc; be = e; have = true; }
-            }
-            for (int off = 32; off >= 1; off >>= 1) {
-                const u64 oe = ((u64)(u32)__shfl_xor((int)(u32)(be >> 32), off) << 32) | (u32)__shfl_xor((int)(u32)be, off);
-                const u64 os = ((u64)(u32)__shfl_xor((int)(u32)(bs >> 32), off) << 32) | (u32)__shfl_xor((int)(u32)bs, off);
-                const bool oh = __shfl_xor((int)have, off) != 0;
-                if (oh && (!have || less(os, oe, bs, be))) { bs = os; be = oe; have = true; }
-            }
-            if (lane == 0) o[0] = be;                          // (max_in_queue().el_ is emitted as is, even ~0)
-            emitted = 1;
-        }
-        if (lane == 0) n_out[q] = emitted;
     }
 }
 
