@@ -154,6 +154,8 @@ def load():
         "bns_dev_sync": (C.c_int, [vp]),
         "bns_classify_text": (C.c_int, [vp, C.POINTER(vp), u64p, C.c_int, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(TextOut), C.POINTER(TextInfo)]),
         "bns_set_min_base_quality": (C.c_int, [vp, C.c_uint32]),
+        "bns_set_dust": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
+        "bns_dust_mask": (C.c_int, [vp, vp, u64p, C.c_uint64, u32p]),
         "bns_text_prefetch": (C.c_int, [vp, C.POINTER(vp), u64p, C.c_int]),
         "bns_text_finish": (C.c_int, [vp, C.POINTER(TextInfo)]),
         "bns_dev_copy_peer": (C.c_int, [vp, vp, vp, vp, C.c_size_t]),

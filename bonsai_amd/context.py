@@ -263,6 +263,26 @@ class Context:
         (q in [0, 93]; 0 turns it off).  FASTA records are untouched."""
         self._chk(self.L.bns_set_min_base_quality(self.h, int(q)), "bns_set_min_base_quality")
 
+    def set_dust(self, window=64, level=20):
+        """bns_set_dust: every classify and build call masks low-complexity sequence (symmetric DUST over the packed image: window in
+        [8, 64] bases, level in [1, 1000]) before it looks anything up; a masked base counts like an 'N'.  window 0 turns it off."""
+        self._chk(self.L.bns_set_dust(self.h, int(window), int(level)), "bns_set_dust")
+
+    def dust_mask(self, bases, offsets):
+        """bns_dust_mask -> one bool array per sequence: the bases the current set_dust() masks (those of N's are not set)"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        flags = np.zeros(int(self.L.bns_packed_words(int(offsets[-1]), n)), dtype=np.uint32)
+        self._chk(self.L.bns_dust_mask(self.h, bases.ctypes.data if bases.size else None, _p(offsets, u64p), n, _p(flags, u32p)), "bns_dust_mask")
+        out = []
+        for s in range(n):
+            o = int(offsets[s]); ln = int(offsets[s + 1]) - o
+            w = flags[(o >> 5) + s:(o >> 5) + s + ((ln + 31) >> 5)]
+            bits = np.unpackbits(w.astype(">u4").view(np.uint8)) if w.size else np.zeros(0, dtype=np.uint8)
+            out.append(bits[:ln].astype(bool))
+        return out
+
     # ---- hot path (host buffers)
     def classify(self, bases, offsets, paired=False, want_hits=False):
         """classify_seqs (classifier.h:269-287) over one batch; returns dict of per-unit arrays."""

@@ -143,6 +143,9 @@ struct bns_ctx {
     // the hit stream of a launch whose caller wants none goes to conf_hits as well
     u32 sketch_cap = 0;
     DevBuf sk_regs, sk_slot_of, sk_slot_bin, sk_seen, sk_state;
+    // bns_set_dust: window and level of the low-complexity mask (dust_w 0: off); dust_flags: one flag word per packed word (bns_dust.hpp)
+    u32 dust_w = 0, dust_t = 0;
+    DevBuf dust_flags;
     // workspace (grow-only)
     DevBuf words, nmask, ovf_list, scratch, small, records;      // small: ovf_count + misc counters
     DevBuf st_bases, st_offsets, st_out[4], st_hits, st_kmers, st_aux, st_runs[4], st_words, st_nmask, st_bad;   // st_words..: packed host batches   // st_runs: run_start, n_runs, run_tax, run_len
@@ -244,6 +247,7 @@ int ready(bns_ctx *ctx, bool need_table, bool need_tax)
 }  // namespace
 
 #include "bns_classify.hpp"
+#include "bns_dust.hpp"
 #include "bns_build.hpp"
 #include "bns_minimize.hpp"
 #include "bns_table_load.hpp"
@@ -252,7 +256,7 @@ int ready(bns_ctx *ctx, bool need_table, bool need_tax)
 
 extern "C" {
 
-int bns_version(void) { return 112; }
+int bns_version(void) { return 113; }
 
 int bns_device_pci_bus_id(int device, char *out, int cap)
 {
@@ -392,7 +396,7 @@ void bns_destroy(bns_ctx *ctx)
                       &ctx->st_out[0], &ctx->st_out[1], &ctx->st_out[2], &ctx->st_out[3], &ctx->st_hits, &ctx->st_kmers, &ctx->st_aux,
                       &ctx->st_runs[0], &ctx->st_runs[1], &ctx->st_runs[2], &ctx->st_runs[3], &ctx->st_words, &ctx->st_nmask, &ctx->st_bad,
                       &ctx->tally_direct, &ctx->tally_clade, &ctx->tally_scan, &ctx->conf_hits,
-                      &ctx->sk_regs, &ctx->sk_slot_of, &ctx->sk_slot_bin, &ctx->sk_seen, &ctx->sk_state};
+                      &ctx->sk_regs, &ctx->sk_slot_of, &ctx->sk_slot_bin, &ctx->sk_seen, &ctx->sk_state, &ctx->dust_flags};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->peer_stage) (void)hipHostFree(ctx->peer_stage);
     if (ctx->h_run_tax) (void)hipHostFree(ctx->h_run_tax);
@@ -1238,7 +1242,7 @@ int bns_build_table_device(bns_ctx *ctx, const char *d_bases, const uint64_t *d_
     if (ctx->spaced && !ctx->spaced_intended) return fail(ctx, BNS_ERR_ARG, "spaced build needs spaced_intended=1");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    if ((rc = pack_reads(ctx, d_bases, d_offsets, n_genomes, total_bases, st)) != BNS_OK) return rc;
+    if ((rc = pack_reads_dust(ctx, d_bases, d_offsets, n_genomes, total_bases, st)) != BNS_OK) return rc;
     const unsigned fgrid = grid_for(ctx, n_buckets, 256);
     hipLaunchKernelGGL(fill_u64_kernel, dim3(fgrid), dim3(256), 0, st, d_keys, (u64)n_buckets, BUILD_EMPTY);
     hipLaunchKernelGGL(fill_u32_kernel, dim3(fgrid), dim3(256), 0, st, d_vals, (u64)n_buckets, 0u);
@@ -1274,6 +1278,12 @@ int bns_build_table_device(bns_ctx *ctx, const char *d_bases, const uint64_t *d_
     HIPCHK(ctx, hipStreamSynchronize(st));
     if (header4) { header4[0] = n_buckets; header4[1] = h_cnt; header4[2] = h_cnt; header4[3] = upper; }
     return BNS_OK;
+}
+
+int bns_set_dust(bns_ctx *ctx, uint32_t window, uint32_t level) { return set_dust(ctx, window, level); }
+int bns_dust_mask(bns_ctx *ctx, const char *bases, const uint64_t *offsets, uint64_t n_seqs, uint32_t *flags)
+{
+    return dust_mask_host(ctx, bases, offsets, n_seqs, flags);
 }
 
 int bns_build_begin(bns_ctx *ctx, uint64_t n_buckets_hint) { return build_begin(ctx, n_buckets_hint); }

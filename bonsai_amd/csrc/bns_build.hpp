@@ -236,7 +236,7 @@ int build_add(bns_ctx *ctx, const char *d_bases, const u64 *d_offsets, u64 n_seq
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     if (st != ctx->stream) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // (begin / seed / a grow of an earlier add ran there)
-    if ((rc = pack_reads(ctx, d_bases, d_offsets, n_seqs, total_bases, st)) != BNS_OK) return rc;
+    if ((rc = pack_reads_dust(ctx, d_bases, d_offsets, n_seqs, total_bases, st)) != BNS_OK) return rc;
     unsigned long long *d_cnt = ((SmallLayout *)ctx->small.p)->load_cnt;
     ClassifyParams p;
     fill_params(ctx, p);

@@ -11,6 +11,7 @@ namespace {
 
 int tally_units(bns_ctx *ctx, const u32 *d_taxon, u64 n_units, hipStream_t st, bool neg);                               // bns_api.hip
 int sketch_units(bns_ctx *ctx, ClassifyParams p, const char *d_bases, u64 n_reads, u64 total_bases, hipStream_t st);   // bns_api.hip
+int dust_image_span(bns_ctx *ctx, const u64 *words, const u32 *nmask, const u64 *offsets, u64 n_seqs, u64 lo, u64 hi, hipStream_t st);   // bns_dust.hpp
 
 void fill_params(const bns_ctx *ctx, ClassifyParams &p)
 {
@@ -137,6 +138,8 @@ int launch_overflow_form(bns_ctx *ctx, const OverflowFormKey &key, const Classif
 struct ClassifyIn {
     const char *bases = nullptr; const u64 *words = nullptr; const u32 *nmask = nullptr;
     const u64 *offsets = nullptr; u64 n_reads = 0, total_bases = 0; u32 max_read_len = 0; int paired = 0;
+    bool masked = false;                                 // packed input of ours that bns_set_dust's pass has been over already (the text path)
+    u64 first_base = 0, end_base = 0;                    // the bases the offsets span, where the caller knows (a slice of a host batch); 0, 0: 0 .. total_bases
 };
 // The per-unit result arrays (device or host), and the hit stream; taxon is always there, the others where the caller wants them.
 struct UnitOut { u32 *taxon = nullptr, *missing = nullptr, *ambig = nullptr, *n_hits = nullptr, *hits = nullptr; };
@@ -245,17 +248,28 @@ int classify_finish(bns_ctx *ctx, const ClassifyIn &in, const UnitOut &out, cons
     return sketch_units(ctx, L.p, in.bases, in.n_reads, in.total_bases, st);
 }
 
-int classify_device_impl(bns_ctx *ctx, const ClassifyIn &in, const UnitOut &out, void *stream)
+int classify_device_impl(bns_ctx *ctx, const ClassifyIn &in0, const UnitOut &out, void *stream)
 {
-    BNS_RC(classify_check(ctx, in, out));
+    BNS_RC(classify_check(ctx, in0, out));
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    ClassifyIn in = in0;
     ClassifyLaunch L;
     L.st = stream ? (hipStream_t)stream : ctx->stream;
-    L.packed = in.words != nullptr;
     L.nm = in.paired ? 2 : 1;
     L.n_units = in.n_reads / (u64)L.nm;
     if (L.n_units == 0) return BNS_OK;
     if (too_many_units(L.n_units)) return fail(ctx, BNS_ERR_ARG, "more than 2^32 - 2^22 units in one batch: split it");
+    if (ctx->dust_w && !in.masked && (in.bases || in.words)) {
+        // bns_set_dust: ASCII is packed first and masked where it lies; a caller's packed image is masked into a copy of ours.  From
+        // here on the call is a packed one over ctx->words / ctx->nmask
+        const u64 lo = in.end_base ? in.first_base : 0, hi = in.end_base ? in.end_base : in.total_bases;
+        if (in.bases) {
+            BNS_RC(pack_reads(ctx, in.bases, in.offsets, in.n_reads, in.total_bases, L.st));
+            BNS_RC(dust_image_span(ctx, (const u64 *)ctx->words.p, (const u32 *)ctx->nmask.p, in.offsets, in.n_reads, lo, hi, L.st));
+        } else BNS_RC(dust_image_span(ctx, in.words, in.nmask, in.offsets, in.n_reads, lo, hi, L.st));
+        in.bases = nullptr; in.words = (const u64 *)ctx->words.p; in.nmask = (const u32 *)ctx->nmask.p;
+    }
+    L.packed = in.words != nullptr;
     BNS_RC(classify_prepare(ctx, in, out, L));
     BNS_RC(classify_launch(ctx, L));
     if (L.can_overflow) BNS_RC(classify_overflow_pass(ctx, in, L));
@@ -455,6 +469,7 @@ int classify_host_impl(bns_ctx *ctx, const HostIn &in, const uint64_t *offsets, 
         else ci.bases = (const char *)ctx->st_bases.p;
         ci.offsets = (const u64 *)ctx->st_offsets.p + r0; ci.n_reads = nr; ci.total_bases = total;
         ci.max_read_len = std::max<u32>(longest(r0, r0 + nr), 1); ci.paired = paired;
+        ci.first_base = offsets[r0]; ci.end_base = offsets[r0 + nr];
         return classify_device_impl(ctx, ci, o, st);
     };
     auto upload = [&](u64 r0, u64 r1, hipStream_t cs) -> int {

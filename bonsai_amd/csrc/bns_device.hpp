@@ -397,6 +397,7 @@ constexpr int MINB_AUX_U32 = MINB_LIST_U32 + 16 * MINB_STRIDE * 4;
 // seeds, whose 64 lookups touch 64 -- fewer passes, more fetches in flight per wavefront)
 constexpr int minb_aux_u32(int nb) { return MINB_LIST_U32 + nb * MINB_STRIDE * 4; }
 constexpr int DPP_WAVE_SHR1 = 0x138;            // lane i <- lane i-1 across the whole wavefront (gfx9 DPP)
+constexpr int DPP_WAVE_SHL1 = 0x130;            // lane i <- lane i+1 across the whole wavefront; lane 63 keeps `old`
 constexpr u32 MINB_NONE = 0xFFFFFFFFu;          // "no bucket wanted" (bucket indices are < 2^31)
 // Oversized minimizer groups (conserved sequence shared by many genomes) would make spill chains arbitrarily long, so
 // a chain is capped at MINB_MAX_CHAIN buckets: keys that find them all full go to a small plain-hashed overflow table

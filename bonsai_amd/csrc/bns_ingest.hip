@@ -838,9 +838,13 @@ int text_flush_batch(bns_ctx *ctx, TextWork &tw, TextCall &tc)
     if (tc.runs_overflow) { tc.status = BNS_TEXT_CAP; return text_roll_back(ctx, tw, tc); }
     u32 *o0 = (u32 *)tw.out[q][0].p, *o1 = (u32 *)tw.out[q][1].p, *o2 = (u32 *)tw.out[q][2].p, *o3 = (u32 *)tw.out[q][3].p;
     unsigned long long *d_cur = &((SmallLayout *)ctx->small.p)->runs_cursor;     // (zeroed at the start of the call: it runs on over the batches)
+    // bns_set_dust: the image of the batch is ours: masked where it lies, so that a parse-only call hands the masked image back as well
+    if (ctx->dust_w && (frc = dust_apply(ctx, (const u64 *)tw.words.p, (const u32 *)tw.nmask.p, (const u64 *)tw.offsets.p, n_reads, DustSpan{0, tc.acc_bases},
+                                         (u64 *)tw.words.p, (u32 *)tw.nmask.p, false, st)) != BNS_OK) return frc;
     if (!parse_only) {
         if (ctx->timing) HIPCHK(ctx, hipEventRecord(tw.tc0[q], st));
         ClassifyIn ci;
+        ci.masked = true;
         ci.words = (const u64 *)tw.words.p; ci.nmask = (const u32 *)tw.nmask.p; ci.offsets = (const u64 *)tw.offsets.p;
         ci.n_reads = n_reads; ci.total_bases = tc.acc_bases; ci.max_read_len = std::max<u32>(tc.acc_max_len, 1u); ci.paired = ns == 2 ? 1 : 0;
         const UnitOut dev{o0, out->missing || need_runs ? o1 : nullptr, out->ambig || need_runs ? o2 : nullptr, (out->n_hits || need_runs) ? o3 : nullptr,

@@ -425,6 +425,11 @@ void set_confidence(ClassifierGeneric &c, u64 num, u64 den)
     for (bns_ctx *cx : c.ctxs_) chk(cx, bns_set_confidence(cx, num, den), "bns_set_confidence");
 }
 
+void set_dust(ClassifierGeneric &c, unsigned level)
+{
+    for (bns_ctx *cx : c.ctxs_) chk(cx, bns_set_dust(cx, level ? 64u : 0u, level), "bns_set_dust");
+}
+
 void set_min_base_quality(ClassifierGeneric &c, unsigned q)
 {
     for (bns_ctx *cx : c.ctxs_) chk(cx, bns_set_min_base_quality(cx, q), "bns_set_min_base_quality");
@@ -871,6 +876,7 @@ Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &
     chk(ctx, bns_set_encoder(ctx, k, gaps.data(), opt.canon ? 1 : 0, 1), "bns_set_encoder");
     chk(ctx, bns_set_window(ctx, w_enc, opt.entropy && !opt.taxdepth ? BNS_SCORE_ENTROPY_PATH : BNS_SCORE_LEX), "bns_set_window");
     chk(ctx, bns_load_taxonomy(ctx, parent.data(), (u32)parent.size()), "bns_load_taxonomy");
+    if (opt.dust_level) chk(ctx, bns_set_dust(ctx, 64u, opt.dust_level), "bns_set_dust");      // (before the session: both passes of -D see one mask)
 
     // The genome files go to the device's build session (bns_build_begin .. bns_build_end) in batches of whole sequences: this thread
     // uploads and adds batch n while a second one reads batch n + 1.  Host memory and the HBM that holds bases are bounded by the

@@ -342,6 +342,9 @@ void set_confidence(ClassifierGeneric &c, u64 num, u64 den);
 // `bonsai classify -Q`: a base whose Phred+33 quality is below q counts as 'N', on every context of the classifier
 // (bns_set_min_base_quality: the text the device parses) and in pack_chunk (the records the host parser yields), before the first unit
 void set_min_base_quality(ClassifierGeneric &c, unsigned q);
+// `bonsai classify -m`: low-complexity masking (bns_set_dust, window 64) on every context; every input form reaches the device as a
+// packed image or as text, so none is left out
+void set_dust(ClassifierGeneric &c, unsigned level);
 // `bonsai classify -R`: a tally on every context of the classifier (bns_tally_enable), before the first unit ...
 void enable_tally(ClassifierGeneric &c);
 // `bonsai classify -R -u`: sketches of the distinct k-mers per taxon on every context (bns_sketch_enable), before the first unit;
@@ -441,6 +444,7 @@ struct BuildOptions {
     bool entropy = false;        // -e: score::Entropy (path-overload rule) instead of score::Lex
     bool taxdepth = false;       // -D: every window keeps the k-mer whose LCA over ALL genomes lies deepest in the taxonomy (DESIGN.md,
                                  // "Defined behaviour"): the files are read twice, so every path must be a regular file; excludes entropy and seed
+    unsigned dust_level = 0;     // -m: low-complexity masking of the genomes (bns_set_dust, window 64; 0: off).  A db does not record it
     int device = 0;
     u64 batch_bases = 1ULL << 30;   // -B: the genome files reach the device in batches of whole sequences of at most this many bases
                                     // (a longer sequence is a batch of its own); the environment's BNS_BUILD_BATCH overrides it

@@ -53,6 +53,9 @@ void usage(const char *exe)
                  "\ttaxon and the taxon's ancestors whose clade holds at least that fraction of its k-mers, else unclassified.\n"
                  "-Q:\tMinimum base quality, an integer in [0, 93] [0: off]: a base whose Phred+33 quality is lower counts as N, so no k-mer\n"
                  "\tover it is looked up (FASTQ records; FASTA has no quality).  Not for a read container: mask with `bonsai pack -Q`.\n"
+                 "-m:\tMask low-complexity sequence at this level, an integer in [1, 1000] (dustmasker's default: 20) [off]: symmetric DUST,\n"
+                 "\twindow 64, over the packed reads on the GPU; a masked base counts as N.  Every input form, a read container included.\n"
+                 "\tGive it when the db was built with `bonsai build -m` (a db does not record that).\n"
                  "<inr1.fq> may be a read container written by `bonsai pack` (2-bit reads + names): no parsing, no packing.\n",
                  exe, 1 << 24);
     std::exit(EXIT_FAILURE);
@@ -71,6 +74,18 @@ bool parse_confidence(const char *s, unsigned long long &num, unsigned long long
     num = ip * scale + fp; den = scale;
     return num <= den;
 }
+
+// `-m`: an integer in [1, 1000], digits only
+bool parse_dust_level(const char *s, unsigned &level)
+{
+    unsigned v = 0;
+    int n = 0;
+    for (; *s >= '0' && *s <= '9'; ++s, ++n) { v = v * 10 + (unsigned)(*s - '0'); if (v > 1000) return false; }
+    if (*s || !n || v < 1) return false;
+    level = v;
+    return true;
+}
+const char *const DUST_LEVEL_MSG = "[E] -m: the low-complexity level must be an integer in [1, 1000] (dustmasker's default is 20), not '%s'\n";
 
 // `-Q`: an integer in [0, 93], digits only
 bool parse_min_quality(const char *s, unsigned &q)
@@ -95,11 +110,11 @@ int classify_main(int argc, char *argv[])
     std::FILE *ofp = stdout, *taxon_fp = nullptr, *report_fp = nullptr;
     const char *names_path = nullptr;
     unsigned long long conf_num = 0, conf_den = 1;
-    unsigned min_qual = 0;
+    unsigned min_qual = 0, dust_level = 0;
     bool distinct = false, coverage = false;
     long sketch_taxa = 65536;
     if (argc < 4) usage(argv[0]);
-    while ((co = getopt(argc, argv, "Cc:p:o:S:afFkKg:L:NP:b:R:n:t:Q:udU:h?")) >= 0) {
+    while ((co = getopt(argc, argv, "Cc:p:o:S:afFkKg:L:NP:b:R:n:t:Q:m:udU:h?")) >= 0) {
         switch (co) {
             case 'h': case '?': usage(argv[0]); break;
             case 'C': canonicalize = false; break;
@@ -136,6 +151,9 @@ int classify_main(int argc, char *argv[])
                     std::fprintf(stderr, "[E] -Q: the minimum base quality must be an integer in [0, 93], not '%s'\n", optarg);
                     return EXIT_FAILURE;
                 }
+                break;
+            case 'm':
+                if (!parse_dust_level(optarg, dust_level)) { std::fprintf(stderr, DUST_LEVEL_MSG, optarg); return EXIT_FAILURE; }
                 break;
             case 'S': break;
             case 'g': devices = optarg; break;
@@ -214,6 +232,7 @@ int classify_main(int argc, char *argv[])
         c.report_out_ = report_fp;
         if (conf_num) bns::set_confidence(c, conf_num, conf_den);
         if (min_qual) bns::set_min_base_quality(c, min_qual);
+        if (dust_level) bns::set_dust(c, dust_level);
         if (report_fp) bns::enable_tally(c);
         if (distinct) bns::enable_sketch(c, (bns::u32)sketch_taxa);
         c.coverage_on_ = coverage;
@@ -297,7 +316,8 @@ int pack_main(int argc, char *argv[])
                 break;
             default:
                 std::fprintf(stderr, "Usage: %s pack [-o out.bnsp] [-c bases per chunk (2^27)] [-p pack threads] [-P parser threads] [-n: no read names] "
-                                     "[-Q minimum base quality: lower bases packed as N] <in1.fq> [<in2.fq>]\n", argv[0]);
+                                     "[-Q minimum base quality: lower bases packed as N] <in1.fq> [<in2.fq>]\n"
+                                     "(no -m: the host packer has no low-complexity mask; `bonsai classify -m` masks a container's reads on the GPU)\n", argv[0]);
                 return EXIT_FAILURE;
         }
     }
@@ -371,7 +391,9 @@ int distrib_main(int argc, char *argv[])
                              "Writes 'mapped_taxid<TAB>genome_taxids:kmers_mapped:total_genome_kmers', then a line per called taxid: the genomes with\n"
                              "windows called there, as <genome taxid>:<windows called here>:<all windows of the genome>.\n"
                              "-t: every window is called as `classify -t` calls it as a read: a decimal in [0, 1] with at most 9 digits after the\n"
-                             "    point.  Give the -t (and as -l the read length) of the classify run whose report is to be re-estimated.\n", argv[0]);
+                             "    point.  Give the -t (and as -l the read length) of the classify run whose report is to be re-estimated.\n"
+                             "(no -m: a window is called as classify calls that substring as a read, and the low-complexity mask of a substring is\n"
+                             " not the genome's mask restricted to it)\n", argv[0]);
         return EXIT_FAILURE;
     };
     int co, device = 0, layout = BNS_LAYOUT_MINBUCKET;
@@ -513,6 +535,9 @@ void build_usage(const char *exe)
                  "    nor -e: repeat them as they were given when the db was built.  <out.path> may be the -A path itself.\n"
                  "-D: Taxonomic-depth minimizers: every window of -w bases keeps the k-mer whose LCA over all genomes lies deepest in\n"
                  "    the taxonomy (then the smaller taxid, then the smaller k-mer).  Reads every genome file twice; excludes -e and -A.\n"
+                 "-m: Mask low-complexity sequence of the genomes at this level, an integer in [1, 1000] (dustmasker's default: 20) [off]:\n"
+                 "    symmetric DUST, window 64, on the GPU; no k-mer over a masked base enters the db.  With -A the added genomes are masked;\n"
+                 "    with -D both passes see the same mask.  The db does not record it: classify the reads with the same -m.\n"
                  "-t / -f build the entropy-minimized map the reference builds for them; tax-depth minimisation is -D.\n", exe);
     std::exit(EXIT_FAILURE);
 }
@@ -524,7 +549,7 @@ int build_main(int argc, char *argv[])
     bool gz = false, k_given = false, w_given = false;
     int c;
     if (argc < 4) build_usage(argv[0]);
-    while ((c = getopt(argc, argv, "Cw:M:S:p:k:T:F:g:A:B:DtefzHh?")) >= 0) {
+    while ((c = getopt(argc, argv, "Cw:M:S:p:k:T:F:g:A:B:m:DtefzHh?")) >= 0) {
         switch (c) {
             case 'C': opt.canon = false; break;
             case 'D': opt.taxdepth = true; break;
@@ -533,6 +558,9 @@ int build_main(int argc, char *argv[])
             case 'A': add_path = optarg; break;
             case 'B': { const long long v = std::atoll(optarg); if (v < 1) build_usage(argv[0]); opt.batch_bases = (bns::u64)v; } break;
             case 'e': opt.entropy = true; break;
+            case 'm':
+                if (!parse_dust_level(optarg, opt.dust_level)) { std::fprintf(stderr, DUST_LEVEL_MSG, optarg); return EXIT_FAILURE; }
+                break;
             case 'S': spacing = optarg; break;
             case 'T': tax_path = optarg; break;
             case 'M': seq2taxpath = optarg; break;

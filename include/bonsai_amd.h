@@ -525,9 +525,9 @@ int bns_build_minimize_stats(const bns_ctx *ctx, uint64_t *out6);
  *                      add; ms3 receives the milliseconds summed over the *n_adds adds since the last call.  A session begun with
  *                      timing off: BNS_ERR_STATE.
  *   bns_windows_end    frees the session; legal at any point.  bns_destroy ends an open session.
- * add, read or timing without a session: BNS_ERR_STATE.  bns_set_min_base_quality does not apply (sequences carry no quality); the
- * bns_tally_enable tally and the sketches are not touched (as with bns_resolve_batch).  Without a session nothing is allocated or
- * launched. */
+ * add, read or timing without a session: BNS_ERR_STATE.  begin while bns_set_dust is on: BNS_ERR_STATE.  bns_set_min_base_quality does
+ * not apply (sequences carry no quality); the bns_tally_enable tally and the sketches are not touched (as with bns_resolve_batch).
+ * Without a session nothing is allocated or launched. */
 int bns_windows_begin(bns_ctx *ctx, uint32_t window_len, uint32_t pair_cap);
 int bns_windows_begin_conf(bns_ctx *ctx, uint32_t window_len, uint32_t pair_cap, uint64_t num, uint64_t den);
 int bns_windows_add(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bases,
@@ -683,6 +683,31 @@ int bns_text_finish(bns_ctx *ctx, bns_text_info *info);
  * off (the default): nothing is launched, allocated or read that was not before.  bns_classify_batch* take no quality: a caller that holds
  * one masks with bns_pack_reads_qual_ptrs. */
 int bns_set_min_base_quality(bns_ctx *ctx, uint32_t q);
+/* ---- low-complexity masking (what `bonsai classify -m` and `bonsai build -m` set; version 113) ------------------------------------
+ * No reference counterpart: the step Kraken 2 applies to a library before it builds (dustmasker / k2mask), as symmetric DUST (Morgulis et
+ * al. 2006) defined in DESIGN.md.  window W in [8, 64] bases, level T in [1, 1000] (dustmasker's defaults: 64, 20).  Inside a maximal run
+ * of valid bases of one sequence -- valid as the packed image flags it: an N, any other byte and a base below bns_set_min_base_quality end a
+ * run -- a triplet is three consecutive bases; an interval of l consecutive triplets, 2 <= l <= W - 2, scores S = sum over triplet values
+ * t of c_t (c_t - 1) / 2, over (l - 1), c_t the occurrences of t in the interval; it is PERFECT when 10 S > T and no sub-interval (l >= 2)
+ * scores strictly higher; the mask is the union of the bases of all perfect intervals (l + 2 bases each).  Exact integer cross-products,
+ * no floating point.  A masked base is an invalid base: its flag is set and its code bits are 0, exactly what a minimum base quality does
+ * to a base, and everything behind the image follows from it.  No reverse-complement symmetry and no parity with NCBI dustmasker or
+ * minimap2's sdust is claimed.
+ * While on: every classifying entry point (those bns_tally_enable lists) packs ASCII input first (pack_kernel), masks the image
+ * (dust_mark_kernel, dust_apply_kernel on the call's stream) and classifies in the packed form; a caller's packed image is never written:
+ * a copy in the context's workspace is masked.  bns_classify_text masks behind its pack (quality masking first), and out->words /
+ * out->nmask hold the masked image.  bns_build_table_device, bns_build_add and bns_build_minimize_add mask the sequences they are given
+ * (both passes of a depth-minimizer build see the same mask).  bns_encode_batch*, the hash feeders, bns_probe* and bns_resolve_batch are
+ * not affected.  bns_windows_begin* return BNS_ERR_STATE while it is on: a window's call is classify's call of that substring as a read,
+ * and the mask of a substring is not the genome's mask restricted to it.
+ * window = 0 turns it off (the default; level is ignored): nothing is launched, allocated or read that was not before.  Otherwise window
+ * outside [8, 64] or level outside [1, 1000]: BNS_ERR_ARG.  While a build or window session is open: BNS_ERR_STATE.  Per context; table
+ * and taxonomy reloads keep it.  A db does not record that it was built masked: the caller has to remember.
+ * bns_dust_mask: the mask alone, for host arrays (bases, n_seqs + 1 offsets) with the context's current window and level; flags receives
+ * bns_packed_words(offsets[n_seqs], n_seqs) words in the image's layout (sequence s at word (offsets[s] >> 5) + s, base i of a word at bit
+ * 31 - i).  Only the bits DUST set are set: those of N's are not.  BNS_ERR_STATE while off.  Needs no encoder, table or taxonomy. */
+int bns_set_dust(bns_ctx *ctx, uint32_t window, uint32_t level);
+int bns_dust_mask(bns_ctx *ctx, const char *bases, const uint64_t *offsets, uint64_t n_seqs, uint32_t *flags);
 /* device -> device copy on the context's stream (a caller that keeps text in HBM moves the unconsumed tail in front of the next batch) */
 int bns_dev_copy(bns_ctx *ctx, void *dst, const void *src, size_t bytes);
 /* ... and between two contexts, src in src_ctx's device memory, dst in dst_ctx's (one device or two: the unconsumed tail of a block that
