@@ -136,6 +136,11 @@ def load():
         "bns_build_minimize_begin": (C.c_int, [vp, C.c_uint32, C.c_uint64]),
         "bns_build_minimize_add": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint64, vp]),
         "bns_build_minimize_stats": (C.c_int, [vp, u64p]),
+        "bns_build_minimize_begin_score": (C.c_int, [vp, C.c_uint32, C.c_uint64, C.c_int]),
+        "bns_build_count_begin": (C.c_int, [vp]),
+        "bns_build_count_add": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint64, u32p, vp]),
+        "bns_build_count_get": (C.c_int, [vp, u64p, C.c_uint64, u32p]),
+        "bns_build_count_stats": (C.c_int, [vp, u64p]),
         "bns_windows_begin": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
         "bns_windows_begin_conf": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]),
         "bns_windows_add": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp, vp]),

@@ -569,10 +569,17 @@ class Context:
         self._chk(self.L.bns_build_end(self.h), "bns_build_end")
 
     # ---- taxonomic-depth minimizers: the session's table of all k-mers (F) thinned to the deepest-LCA k-mer of every window (M)
-    def build_minimize_begin(self, w, n_buckets=0):
+    def build_minimize_begin(self, w, n_buckets=0, score="depth"):
         """freezes F (build_add / build_seed are refused from here on) and opens M with max(4, n_buckets rounded up to a power of
-        two) buckets; build_finish / build_end then act on M"""
-        self._chk(self.L.bns_build_minimize_begin(self.h, int(w), int(n_buckets)), "bns_build_minimize_begin")
+        two) buckets; build_finish / build_end then act on M.  score: "depth" (the deepest LCA of every window) or "fewest" (the
+        k-mer the fewest genomes hold: needs build_count_begin / build_count_add); an integer is handed to the library as it is"""
+        if score == "depth":
+            self._chk(self.L.bns_build_minimize_begin(self.h, int(w), int(n_buckets)), "bns_build_minimize_begin")
+            return
+        code = {"fewest": 1}.get(score, score)
+        if isinstance(code, str):
+            raise ValueError('score must be "depth" or "fewest"')
+        self._chk(self.L.bns_build_minimize_begin_score(self.h, int(w), int(n_buckets), int(code)), "bns_build_minimize_begin_score")
 
     def build_minimize_add(self, d_bases, d_offsets, n_seqs, total_bases, stream=None):
         """one batch of the sequences F was built from (device arrays, as build_add takes them, without taxids)"""
@@ -583,6 +590,37 @@ class Context:
         out = np.zeros(6, dtype=np.uint64)
         self._chk(self.L.bns_build_minimize_stats(self.h, _p(out, u64p)), "bns_build_minimize_stats")
         d = dict(zip(("batches", "grows", "scored_keys", "keys", "lookups"), (int(x) for x in out[:5])))
+        d["add_s"] = float(out[5]) * 1e-6
+        return d
+
+    # ---- fewest-genome minimizers: per k-mer of F, the number of distinct genome ids among the sequences that hold it
+    def build_count_begin(self):
+        """freezes F and gives every bucket of it a zeroed count (8 more bytes a bucket until build_end)"""
+        self._chk(self.L.bns_build_count_begin(self.h), "bns_build_count_begin")
+
+    def build_count_add(self, d_bases, d_offsets, n_seqs, total_bases, genome_ids, stream=None):
+        """one batch of the sequences F was built from (device arrays, as build_minimize_add takes them) and, on the HOST, the genome
+        id of every sequence: non-decreasing within the call and from one call to the next, none 0xFFFFFFFF"""
+        ids = np.asarray(genome_ids)
+        if ids.size != int(n_seqs):
+            raise ValueError("one genome id per sequence")
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) > 0xFFFFFFFF):
+            raise ValueError("genome ids are uint32")
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        self._chk(self.L.bns_build_count_add(self.h, d_bases, d_offsets, int(n_seqs), int(total_bases), _p(ids, u32p), stream), "bns_build_count_add")
+
+    def build_count(self, keys):
+        """uint32 array: for every key (as the encoder emits it) the number of distinct genomes counted so far, 0 for a key F does not hold"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        out = np.zeros(keys.size, dtype=np.uint32)
+        self._chk(self.L.bns_build_count_get(self.h, _p(keys, u64p), keys.size, _p(out, u32p)), "bns_build_count_get")
+        return out
+
+    def build_count_stats(self):
+        """{batches, launches (runs of one genome id), genomes (distinct ids seen), lookups, largest (count), add_s}"""
+        out = np.zeros(6, dtype=np.uint64)
+        self._chk(self.L.bns_build_count_stats(self.h, _p(out, u64p)), "bns_build_count_stats")
+        d = dict(zip(("batches", "launches", "genomes", "lookups", "largest"), (int(x) for x in out[:5])))
         d["add_s"] = float(out[5]) * 1e-6
         return d
 

@@ -249,6 +249,7 @@ int ready(bns_ctx *ctx, bool need_table, bool need_tax)
 #include "bns_classify.hpp"
 #include "bns_dust.hpp"
 #include "bns_build.hpp"
+#include "bns_fewest.hpp"
 #include "bns_minimize.hpp"
 #include "bns_table_load.hpp"
 #include "bns_windows.hpp"
@@ -256,7 +257,7 @@ int ready(bns_ctx *ctx, bool need_table, bool need_tax)
 
 extern "C" {
 
-int bns_version(void) { return 113; }
+int bns_version(void) { return 114; }
 
 int bns_device_pci_bus_id(int device, char *out, int cap)
 {
@@ -1306,7 +1307,16 @@ int bns_build_stats(const bns_ctx *ctx, uint64_t *out6)
     out6[4] = (u64)(ctx->build->s_add * 1e6); out6[5] = (u64)(ctx->build->s_grow * 1e6);
     return BNS_OK;
 }
-int bns_build_minimize_begin(bns_ctx *ctx, uint32_t w, uint64_t n_buckets_hint) { return minimize_begin(ctx, w, n_buckets_hint); }
+int bns_build_minimize_begin(bns_ctx *ctx, uint32_t w, uint64_t n_buckets_hint) { return bns_build_minimize_begin_score(ctx, w, n_buckets_hint, BNS_MINIMIZE_DEPTH); }
+int bns_build_minimize_begin_score(bns_ctx *ctx, uint32_t w, uint64_t n_buckets_hint, int score) { return minimize_begin(ctx, w, n_buckets_hint, score); }
+int bns_build_count_begin(bns_ctx *ctx) { return count_begin(ctx); }
+int bns_build_count_add(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bases,
+                        const uint32_t *h_genome, void *stream)
+{
+    return count_add(ctx, d_bases, d_offsets, n_seqs, total_bases, h_genome, stream);
+}
+int bns_build_count_get(bns_ctx *ctx, const uint64_t *h_keys, uint64_t n, uint32_t *h_counts) { return count_get(ctx, h_keys, n, h_counts); }
+int bns_build_count_stats(const bns_ctx *ctx, uint64_t *out6) { return count_stats(ctx, out6); }
 int bns_build_minimize_add(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bases, void *stream)
 {
     return minimize_add(ctx, d_bases, d_offsets, n_seqs, total_bases, stream);

@@ -76,6 +76,15 @@ struct BuildSession {
     u32 *depth = nullptr;            // depth[id] for id in [0, n_nodes): nodes on the chain id -> root, 0 where the chain reaches none
     u64 m_batches = 0, m_grows = 0, m_lookups = 0;
     double s_min = 0;                // wall seconds inside bns_build_minimize_add
+    // bns_build_count_begin (bns_fewest.hpp): two words per bucket of F, which is frozen from there on
+    bool counting = false;
+    u32 *g_count = nullptr;          // distinct genome ids among the sequences that hold the bucket's k-mer
+    u32 *g_stamp = nullptr;          // id + 1 of the genome that counted the bucket last, 0: none yet
+    bool g_any = false;              // a sequence has been counted: g_last is the id of the last one
+    u32 g_last = 0;
+    u64 g_batches = 0, g_launches = 0, g_genomes = 0, g_lookups = 0, g_largest = 0;
+    double s_count = 0;              // wall seconds inside bns_build_count_add
+    int min_score = 0;               // BNS_MINIMIZE_DEPTH / BNS_MINIMIZE_FEWEST of bns_build_minimize_begin_score
 };
 
 inline u64 build_upper(u64 nb) { return (u64)(nb * 0.77 + 0.5); }                  // khash64.h:198
@@ -100,6 +109,8 @@ void build_free(bns_ctx *ctx)
     if (s->f_keys) (void)hipFree(s->f_keys);
     if (s->f_vals) (void)hipFree(s->f_vals);
     if (s->depth) (void)hipFree(s->depth);
+    if (s->g_count) (void)hipFree(s->g_count);
+    if (s->g_stamp) (void)hipFree(s->g_stamp);
     delete s;
     ctx->build = nullptr;
 }
@@ -184,6 +195,7 @@ int build_seed(bns_ctx *ctx, u64 n_buckets, const u32 *flags, const u64 *keys, c
     int rc = build_session(ctx, &s, "bns_build_seed");
     if (rc != BNS_OK) return rc;
     if (s->minimizing) return fail(ctx, BNS_ERR_STATE, "bns_build_seed after bns_build_minimize_begin: the scored table is frozen");
+    if (s->counting) return fail(ctx, BNS_ERR_STATE, "bns_build_seed after bns_build_count_begin: the scored table is frozen");
     if (s->added || s->seeded || s->finished) return fail(ctx, BNS_ERR_STATE, "bns_build_seed comes once, between bns_build_begin and the first bns_build_add");
     if (n_buckets && (!flags || !keys || !vals)) return BNS_ERR_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -231,6 +243,7 @@ int build_add(bns_ctx *ctx, const char *d_bases, const u64 *d_offsets, u64 n_seq
     if (rc != BNS_OK) return rc;
     if (s->finished) return fail(ctx, BNS_ERR_STATE, "bns_build_add after bns_build_finish");
     if (s->minimizing) return fail(ctx, BNS_ERR_STATE, "bns_build_add after bns_build_minimize_begin: the scored table is frozen");
+    if (s->counting) return fail(ctx, BNS_ERR_STATE, "bns_build_add after bns_build_count_begin: the scored table is frozen");
     if (n_seqs == 0) { s->added = true; ++s->n_batches; return BNS_OK; }
     if (!d_offsets || !d_taxid) return BNS_ERR_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));

@@ -14,6 +14,8 @@
 //                                    (wang64(key) & mask, triangular steps, until the key or BUILD_EMPTY), read vals[slot], read
 //                                    depth[val]; score = (0xFFFFFFFF - depth) << 32 | val.  ONE lookup per position and chunk: the
 //                                    gather into a table of all k-mers is a cache miss per position and what this kernel costs.
+//                                    (SCORE 1, fewest-genome minimizers: count[slot] of bns_fewest.hpp in depth's place, score =
+//                                    count << 32 | val; bns_build_minimize_begin_score.  The SCORE 0 form is the code as it was.)
 //                             sweep  64 windows a round: the (score, k-mer) minimum of entries p .. p + ws - 1, read from LDS at
 //                                    lane-consecutive addresses (no bank conflict), ws = w - c + 1 from 1 to 1024.
 //                           An invalid position holds (~0, ~0), which no valid one does (~0 is no key a session accepts), so it never
@@ -59,9 +61,11 @@ __global__ __launch_bounds__(256) void depth_kernel(const TaxNode *__restrict__ 
     }
 }
 
-template <bool SPACED>
+// SCORE 0 (BNS_MINIMIZE_DEPTH): aux = depth[id], one word per taxonomy node.  SCORE 1 (BNS_MINIMIZE_FEWEST): aux = the genome counts of
+// bns_fewest.hpp, one word per bucket of F.
+template <bool SPACED, int SCORE>
 __global__ __launch_bounds__(64) void minimize_kernel(ClassifyParams p, u32 w, const u64 *__restrict__ fkeys, const u32 *__restrict__ fvals,
-                                                      u64 f_nb, const u32 *__restrict__ depth, u64 *__restrict__ mkeys,
+                                                      u64 f_nb, const u32 *__restrict__ aux, u64 *__restrict__ mkeys,
                                                       u32 *__restrict__ mvals, u64 m_nb, unsigned long long *cnt)
 {
     __shared__ u64 s_sc[MINZ_ENTRIES];
@@ -117,8 +121,12 @@ __global__ __launch_bounds__(64) void minimize_kernel(ClassifyParams p, u32 w, c
                     }
                     if (found) {
                         const u32 v = fvals[i];
-                        const u32 d = v < p.n_nodes ? depth[v] : 0u;
-                        score = ((u64)(0xFFFFFFFFu - d) << 32) | v;
+                        if (SCORE == 0) {
+                            const u32 d = v < p.n_nodes ? aux[v] : 0u;
+                            score = ((u64)(0xFFFFFFFFu - d) << 32) | v;
+                        } else {
+                            score = ((u64)aux[i] << 32) | v;     // FMencode(genomes that hold it, taxid): fewer genomes first
+                        }
                     } else { missing = true; valid = false; }
                 }
                 lookups += (u64)__popcll(ballot64(valid));
@@ -166,14 +174,16 @@ __global__ __launch_bounds__(64) void minimize_kernel(ClassifyParams p, u32 w, c
 
 namespace {
 
-int minimize_begin(bns_ctx *ctx, u32 w, u64 hint)
+int minimize_begin(bns_ctx *ctx, u32 w, u64 hint, int score)
 {
     BuildSession *s;
     int rc = build_session(ctx, &s, "bns_build_minimize_begin");
     if (rc != BNS_OK) return rc;
+    if (score != BNS_MINIMIZE_DEPTH && score != BNS_MINIMIZE_FEWEST) return fail(ctx, BNS_ERR_ARG, "bns_build_minimize_begin_score: score must be BNS_MINIMIZE_DEPTH or BNS_MINIMIZE_FEWEST");
     if (s->finished) return fail(ctx, BNS_ERR_STATE, "bns_build_minimize_begin after bns_build_finish");
     if (s->minimizing) return fail(ctx, BNS_ERR_STATE, "bns_build_minimize_begin called twice");
     if (ctx->win > ctx->c) return fail(ctx, BNS_ERR_STATE, "bns_build_minimize_begin needs a session that scored every k-mer: bns_set_window is beyond the comb");
+    if (score == BNS_MINIMIZE_FEWEST && !s->counting) return fail(ctx, BNS_ERR_STATE, "bns_build_minimize_begin_score: BNS_MINIMIZE_FEWEST needs the genome counts (bns_build_count_begin, bns_build_count_add)");
     if (w > ctx->c) {
         if (w > 1920u) return fail(ctx, BNS_ERR_ARG, "window of more than 1920 bases is not supported (a wavefront works on 2048-base chunks)");
         if (w - ctx->c + 1 > 1024u) return fail(ctx, BNS_ERR_ARG, "window of more than 1024 k-mers is not supported");
@@ -182,22 +192,26 @@ int minimize_begin(bns_ctx *ctx, u32 w, u64 hint)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     u32 *depth = nullptr;
-    HIPCHK(ctx, hipMalloc((void **)&depth, (size_t)ctx->n_nodes * 4));
-    hipLaunchKernelGGL(depth_kernel, dim3(grid_for(ctx, ctx->n_nodes, 256)), dim3(256), 0, st, (const TaxNode *)ctx->nodes, ctx->n_nodes, depth);
+    if (score == BNS_MINIMIZE_DEPTH) {
+        HIPCHK(ctx, hipMalloc((void **)&depth, (size_t)ctx->n_nodes * 4));
+        hipLaunchKernelGGL(depth_kernel, dim3(grid_for(ctx, ctx->n_nodes, 256)), dim3(256), 0, st, (const TaxNode *)ctx->nodes, ctx->n_nodes, depth);
+    }
     u64 nb = 4;
     while (nb < hint) nb <<= 1;
     u64 *mk; u32 *mv;
-    if ((rc = build_alloc_table(ctx, nb, &mk, &mv, st)) != BNS_OK) { (void)hipStreamSynchronize(st); (void)hipFree(depth); return rc; }
+    if ((rc = build_alloc_table(ctx, nb, &mk, &mv, st)) != BNS_OK) { (void)hipStreamSynchronize(st); if (depth) (void)hipFree(depth); return rc; }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
-        (void)hipFree(depth); (void)hipFree(mk); (void)hipFree(mv);
+        if (depth) (void)hipFree(depth);
+        (void)hipFree(mk); (void)hipFree(mv);
         ctx->err = std::string("bns_build_minimize_begin: ") + hipGetErrorString(e);
         return BNS_ERR_HIP;
     }
     s->f_keys = s->keys; s->f_vals = s->vals; s->f_nb = s->nb; s->f_n_keys = s->n_keys;
     s->keys = mk; s->vals = mv; s->nb = nb; s->n_keys = 0;
     s->depth = depth;
+    s->min_score = score;
     s->min_w = w > ctx->c ? w : ctx->c;
     s->minimizing = true;
     return BNS_OK;
@@ -225,10 +239,12 @@ int minimize_add(bns_ctx *ctx, const char *d_bases, const u64 *d_offsets, u64 n_
     s->failed = true;                                            // until the batch is in
     for (;;) {
         HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, 32, st));
-        if (ctx->spaced) hipLaunchKernelGGL((minimize_kernel<true>), dim3(grid), dim3(64), 0, st, p, s->min_w, (const u64 *)s->f_keys, (const u32 *)s->f_vals,
-                                            s->f_nb, (const u32 *)s->depth, s->keys, s->vals, s->nb, d_cnt);
-        else             hipLaunchKernelGGL((minimize_kernel<false>), dim3(grid), dim3(64), 0, st, p, s->min_w, (const u64 *)s->f_keys, (const u32 *)s->f_vals,
-                                            s->f_nb, (const u32 *)s->depth, s->keys, s->vals, s->nb, d_cnt);
+        const bool fewest = s->min_score == BNS_MINIMIZE_FEWEST;
+        const u32 *aux = fewest ? s->g_count : s->depth;
+        auto kern = ctx->spaced ? (fewest ? minimize_kernel<true, 1> : minimize_kernel<true, 0>)
+                                : (fewest ? minimize_kernel<false, 1> : minimize_kernel<false, 0>);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, st, p, s->min_w, (const u64 *)s->f_keys, (const u32 *)s->f_vals, s->f_nb, aux, s->keys,
+                           s->vals, s->nb, d_cnt);
         HIPCHK(ctx, hipGetLastError());
         unsigned long long h_cnt[4] = {0, 0, 0, 0};
         HIPCHK(ctx, hipMemcpyAsync(h_cnt, d_cnt, 32, hipMemcpyDeviceToHost, st));

@@ -831,8 +831,10 @@ void read_build_batches(const std::vector<std::string> &paths, const std::vector
     std::exception_ptr err;
     try {
         BuildBatch b;
+        u32 genome = 0;
         for (const std::string &path : paths) {
             if (q.abandoned()) break;
+            const u32 gid = genome++;
             const tax_t tx = get_taxid(path.c_str(), names);
             SeqReader rd(path.c_str());
             bseq1_t rec;
@@ -841,6 +843,7 @@ void read_build_batches(const std::vector<std::string> &paths, const std::vector
                 b.bases += rec.seq;
                 b.offsets.push_back(b.bases.size());
                 b.taxids.push_back(tx);
+                b.genomes.push_back(gid);
             }
         }
         if (!b.taxids.empty()) q.push(std::move(b));
@@ -861,22 +864,25 @@ Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &
     for (u16 g : gaps) c += g;
     const unsigned w = std::max<int>((int)c, std::max<int>(opt.wsz, (int)k));                 // bonsai.cpp:217 + spacer.h:61
     // -D (taxonomic-depth minimizers): pass A scores every k-mer (the window unset), pass B streams the same files again and selects
-    const unsigned w_enc = opt.taxdepth ? c : w;
+    // -G (fewest-genome minimizers): pass A the same, pass C counts the genome files that hold every k-mer, pass B selects by the counts
+    const bool scored = opt.taxdepth || opt.fewest;
+    const unsigned w_enc = scored ? c : w;
     const unsigned span = w_enc > c ? w_enc : c;
-    if (opt.taxdepth)                                                                          // (before any device is opened)
+    if (scored)                                                                                // (before any device is opened)
         for (const std::string &path : paths) {
             struct stat sb;
             if (::stat(path.c_str(), &sb) != 0) die("Could not read from file " + path);
-            if (!S_ISREG(sb.st_mode)) die("-D reads every genome file twice: " + path + " is not a regular file");
+            if (!S_ISREG(sb.st_mode))
+                die(std::string(opt.fewest ? "-G reads every genome file three times: " : "-D reads every genome file twice: ") + path + " is not a regular file");
         }
 
     bns_ctx *ctx = nullptr;
     chk(nullptr, bns_create(opt.device, &ctx), "bns_create");
     struct Guard { bns_ctx *c; ~Guard() { bns_destroy(c); } } guard{ctx};
     chk(ctx, bns_set_encoder(ctx, k, gaps.data(), opt.canon ? 1 : 0, 1), "bns_set_encoder");
-    chk(ctx, bns_set_window(ctx, w_enc, opt.entropy && !opt.taxdepth ? BNS_SCORE_ENTROPY_PATH : BNS_SCORE_LEX), "bns_set_window");
+    chk(ctx, bns_set_window(ctx, w_enc, opt.entropy && !scored ? BNS_SCORE_ENTROPY_PATH : BNS_SCORE_LEX), "bns_set_window");
     chk(ctx, bns_load_taxonomy(ctx, parent.data(), (u32)parent.size()), "bns_load_taxonomy");
-    if (opt.dust_level) chk(ctx, bns_set_dust(ctx, 64u, opt.dust_level), "bns_set_dust");      // (before the session: both passes of -D see one mask)
+    if (opt.dust_level) chk(ctx, bns_set_dust(ctx, 64u, opt.dust_level), "bns_set_dust");      // (before the session: the passes of -D and -G see one mask)
 
     // The genome files go to the device's build session (bns_build_begin .. bns_build_end) in batches of whole sequences: this thread
     // uploads and adds batch n while a second one reads batch n + 1.  Host memory and the HBM that holds bases are bounded by the
@@ -886,10 +892,12 @@ Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &
 
     GrowMem d_bases(ctx), d_off(ctx), d_tx(ctx);
     bool begun = false, begun_m = false;
-    u64 stats_a[6] = {0, 0, 0, 0, 0, 0}, mstats[6] = {0, 0, 0, 0, 0, 0};
+    u64 stats_a[6] = {0, 0, 0, 0, 0, 0}, mstats[6] = {0, 0, 0, 0, 0, 0}, cstats[6] = {0, 0, 0, 0, 0, 0};
     double t_wait = 0, t_upload = 0, t_finish = 0;                                             // seconds of this thread (BNS_CLI_TIMING)
-    // one pass over the files: bns_build_add of every batch, or (minimize) bns_build_minimize_add of every batch
-    auto stream_pass = [&](bool minimize) {
+    // one pass over the files: bns_build_add of every batch, (PASS_COUNT) bns_build_count_add or (PASS_MINIMIZE) bns_build_minimize_add
+    enum { PASS_ADD, PASS_COUNT, PASS_MINIMIZE };
+    auto stream_pass = [&](int pass) {
+        const bool minimize = pass == PASS_MINIMIZE;
         BatchQueue q;
         std::thread reader([&] { read_build_batches(paths, names, batch_bases, q); });
         struct Join { BatchQueue &q; std::thread &t; ~Join() { q.abandon(); if (t.joinable()) t.join(); } } join{q, reader};
@@ -928,7 +936,7 @@ Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &
                 u64 hint = 4;
                 const u64 est = ws > 1 ? std::max<u64>(1024, windows * 3 / (ws + 1)) : stats_a[3];
                 while ((u64)(hint * 0.77 + 0.5) < est) hint <<= 1;
-                chk(ctx, bns_build_minimize_begin(ctx, w, hint), "bns_build_minimize_begin");
+                chk(ctx, bns_build_minimize_begin_score(ctx, w, hint, opt.fewest ? BNS_MINIMIZE_FEWEST : BNS_MINIMIZE_DEPTH), "bns_build_minimize_begin");
                 begun_m = true;
             }
             const u64 total = b.offsets.back();
@@ -937,7 +945,7 @@ Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &
             d_bases.ensure(b.bases.size()); d_off.ensure(b.offsets.size() * 8);
             chk(ctx, bns_dev_upload(ctx, d_bases.p, b.bases.data(), b.bases.size()), "upload");
             chk(ctx, bns_dev_upload(ctx, d_off.p, b.offsets.data(), b.offsets.size() * 8), "upload");
-            if (!minimize) {
+            if (pass == PASS_ADD) {
                 d_tx.ensure(b.taxids.size() * 4);
                 chk(ctx, bns_dev_upload(ctx, d_tx.p, b.taxids.data(), b.taxids.size() * 4), "upload");
             }
@@ -946,18 +954,26 @@ Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &
             if (minimize)
                 chk(ctx, bns_build_minimize_add(ctx, (const char *)d_bases.p, (const u64 *)d_off.p, b.taxids.size(), total, nullptr),
                     "bns_build_minimize_add");
+            else if (pass == PASS_COUNT)
+                chk(ctx, bns_build_count_add(ctx, (const char *)d_bases.p, (const u64 *)d_off.p, b.taxids.size(), total, b.genomes.data(), nullptr),
+                    "bns_build_count_add");
             else
                 chk(ctx, bns_build_add(ctx, (const char *)d_bases.p, (const u64 *)d_off.p, b.taxids.size(), total, (const u32 *)d_tx.p, nullptr),
                     "bns_build_add");
         }
         q.rethrow();
     };
-    stream_pass(false);
+    stream_pass(PASS_ADD);
     if (!begun) die("Need input files from command line or file. See usage.");
-    if (opt.taxdepth) {
+    if (scored) {
         chk(ctx, bns_build_stats(ctx, stats_a), "bns_build_stats");
-        stream_pass(true);
-        if (!begun_m) chk(ctx, bns_build_minimize_begin(ctx, w, 0), "bns_build_minimize_begin");
+        if (opt.fewest) {
+            chk(ctx, bns_build_count_begin(ctx), "bns_build_count_begin");
+            stream_pass(PASS_COUNT);
+            chk(ctx, bns_build_count_stats(ctx, cstats), "bns_build_count_stats");
+        }
+        stream_pass(PASS_MINIMIZE);
+        if (!begun_m) chk(ctx, bns_build_minimize_begin_score(ctx, w, 0, opt.fewest ? BNS_MINIMIZE_FEWEST : BNS_MINIMIZE_DEPTH), "bns_build_minimize_begin");
         chk(ctx, bns_build_minimize_stats(ctx, mstats), "bns_build_minimize_stats");
     }
     d_bases.release(); d_off.release(); d_tx.release();
@@ -966,7 +982,7 @@ Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &
     u64 hdr[4] = {0, 0, 0, 0}, stats[6] = {0, 0, 0, 0, 0, 0};
     const double tf0 = tnow();
     chk(ctx, bns_build_finish(ctx, hdr), "bns_build_finish");
-    if (opt.taxdepth) std::memcpy(stats, stats_a, sizeof(stats));                              // (pass A's; the key count below is M's)
+    if (scored) std::memcpy(stats, stats_a, sizeof(stats));                                    // (pass A's; the key count below is M's)
     else chk(ctx, bns_build_stats(ctx, stats), "bns_build_stats");
     const u64 nb = hdr[0];
     db.k_ = k; db.w_ = w; db.s_ = gaps;
@@ -980,11 +996,15 @@ Database lca_map(const std::vector<std::string> &paths, const std::vector<u32> &
                      t_wait, t_upload, (double)stats[4] * 1e-6, (double)stats[5] * 1e-6, t_finish);
         std::fprintf(stderr, "build: %llu batches, %llu grows, %llu seeded keys, %llu keys in %llu buckets\n", (unsigned long long)stats[0],
                      (unsigned long long)stats[1], (unsigned long long)stats[2], (unsigned long long)hdr[2], (unsigned long long)nb);
-        if (opt.taxdepth)
+        if (opt.fewest)
+            std::fprintf(stderr, "count: %llu batches, %llu launches, %llu genomes, %llu lookups, largest count %llu\n", (unsigned long long)cstats[0],
+                         (unsigned long long)cstats[1], (unsigned long long)cstats[2], (unsigned long long)cstats[3], (unsigned long long)cstats[4]);
+        if (scored)
             std::fprintf(stderr, "minimize: %llu batches, %llu grows, %llu scored keys, %llu lookups, %llu keys in %llu buckets\n",
                          (unsigned long long)mstats[0], (unsigned long long)mstats[1], (unsigned long long)mstats[2], (unsigned long long)mstats[4],
                          (unsigned long long)hdr[2], (unsigned long long)nb);
-        if (opt.taxdepth) std::fprintf(stderr, "[timing] minimize: add %.3f s\n", (double)mstats[5] * 1e-6);
+        if (opt.fewest) std::fprintf(stderr, "[timing] count: add %.3f s\n", (double)cstats[5] * 1e-6);
+        if (scored) std::fprintf(stderr, "[timing] minimize: add %.3f s\n", (double)mstats[5] * 1e-6);
     }
     return db;
 }

@@ -444,6 +444,8 @@ struct BuildOptions {
     bool entropy = false;        // -e: score::Entropy (path-overload rule) instead of score::Lex
     bool taxdepth = false;       // -D: every window keeps the k-mer whose LCA over ALL genomes lies deepest in the taxonomy (DESIGN.md,
                                  // "Defined behaviour"): the files are read twice, so every path must be a regular file; excludes entropy and seed
+    bool fewest = false;         // -G: every window keeps the k-mer that the fewest genome FILES hold (then the smaller taxid, then the smaller
+                                 // k-mer; DESIGN.md, "Defined behaviour"): the files are read three times; excludes entropy, taxdepth and seed
     unsigned dust_level = 0;     // -m: low-complexity masking of the genomes (bns_set_dust, window 64; 0: off).  A db does not record it
     int device = 0;
     u64 batch_bases = 1ULL << 30;   // -B: the genome files reach the device in batches of whole sequences of at most this many bases

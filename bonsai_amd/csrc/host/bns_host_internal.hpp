@@ -198,7 +198,8 @@ struct BuildBatch {
     std::string bases;
     std::vector<u64> offsets{0};
     std::vector<u32> taxids;
-    void clear() { bases.clear(); offsets.assign(1, 0); taxids.clear(); }
+    std::vector<u32> genomes;      // per sequence: the index of its file in path order (bonsai build -G; bonsai distrib ignores it)
+    void clear() { bases.clear(); offsets.assign(1, 0); taxids.clear(); genomes.clear(); }
 };
 
 // one batch waits while the device works on the one before it and the reader fills the next

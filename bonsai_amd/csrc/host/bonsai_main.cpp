@@ -535,10 +535,13 @@ void build_usage(const char *exe)
                  "    nor -e: repeat them as they were given when the db was built.  <out.path> may be the -A path itself.\n"
                  "-D: Taxonomic-depth minimizers: every window of -w bases keeps the k-mer whose LCA over all genomes lies deepest in\n"
                  "    the taxonomy (then the smaller taxid, then the smaller k-mer).  Reads every genome file twice; excludes -e and -A.\n"
+                 "-G: Fewest-genome minimizers: every window of -w bases keeps the k-mer that the fewest genome files hold (then the smaller\n"
+                 "    taxid, then the smaller k-mer).  A genome is one input file.  Reads every genome file three times; excludes -e, -D and -A.\n"
                  "-m: Mask low-complexity sequence of the genomes at this level, an integer in [1, 1000] (dustmasker's default: 20) [off]:\n"
                  "    symmetric DUST, window 64, on the GPU; no k-mer over a masked base enters the db.  With -A the added genomes are masked;\n"
-                 "    with -D both passes see the same mask.  The db does not record it: classify the reads with the same -m.\n"
-                 "-t / -f build the entropy-minimized map the reference builds for them; tax-depth minimisation is -D.\n", exe);
+                 "    with -D and -G all passes see the same mask.  The db does not record it: classify the reads with the same -m.\n"
+                 "-t / -f build the entropy-minimized map the reference builds for them; tax-depth minimisation is -D,\n"
+                 "feature-count minimisation is -G.\n", exe);
     std::exit(EXIT_FAILURE);
 }
 
@@ -549,10 +552,11 @@ int build_main(int argc, char *argv[])
     bool gz = false, k_given = false, w_given = false;
     int c;
     if (argc < 4) build_usage(argv[0]);
-    while ((c = getopt(argc, argv, "Cw:M:S:p:k:T:F:g:A:B:m:DtefzHh?")) >= 0) {
+    while ((c = getopt(argc, argv, "Cw:M:S:p:k:T:F:g:A:B:m:DGtefzHh?")) >= 0) {
         switch (c) {
             case 'C': opt.canon = false; break;
             case 'D': opt.taxdepth = true; break;
+            case 'G': opt.fewest = true; break;
             case 'k': opt.k = (unsigned)std::atoi(optarg); k_given = true; break;
             case 'w': opt.wsz = std::atoi(optarg); w_given = true; break;
             case 'A': add_path = optarg; break;
@@ -604,6 +608,13 @@ int build_main(int argc, char *argv[])
         if (opt.k < 1 || opt.k > 32) throw bns::Error("k must be in [1,32]");
         if (opt.taxdepth && opt.entropy)
             throw bns::Error("-D and -e exclude each other: a window keeps its k-mer by one score, taxonomic depth or entropy");
+        if (opt.fewest && opt.entropy)
+            throw bns::Error("-G and -e exclude each other: a window keeps its k-mer by one score, the genomes that hold it or entropy");
+        if (opt.fewest && opt.taxdepth)
+            throw bns::Error("-G and -D exclude each other: a window keeps its k-mer by one score, the genomes that hold it or taxonomic depth");
+        if (opt.fewest && !add_path.empty())
+            throw bns::Error("-G and -A exclude each other: fewest-genome selection counts every k-mer of every genome, and a db holds neither "
+                             "the table of all k-mers it was selected from nor the counts");
         if (opt.taxdepth && !add_path.empty())
             throw bns::Error("-D and -A exclude each other: tax-depth selection scores every k-mer of every genome, and a db does not hold "
                              "the table of all k-mers it was selected from");

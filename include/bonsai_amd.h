@@ -96,7 +96,7 @@ int bns_set_window(bns_ctx *ctx, uint32_t w, int score);
  * chunks of 2^27 slots when they do not (an 8e9-key db: 210 GB of arrays, 200+ GB of table); BNS_LAYOUT_KHASH keeps them resident. */
 int bns_load_table(bns_ctx *ctx, uint64_t n_buckets, const uint32_t *flags, const uint64_t *keys,
                    const uint32_t *vals, int layout);
-/* ---- the `void *stream` argument of the _device entry points, bns_build_add, bns_build_minimize_add and bns_windows_add ----------
+/* ---- the `void *stream` argument of the _device entry points, bns_build_add, bns_build_minimize_add, bns_build_count_add and bns_windows_add
  * `stream` is a hipStream_t of the context's device; NULL means the context's own stream (the one every host-buffer entry point
  * works on).  For a non-NULL stream:
  *   ORDER     everything the call enqueues -- kernels, memsets, the copies of its counters -- goes on `stream`, in order.  Inputs
@@ -107,9 +107,9 @@ int bns_load_table(bns_ctx *ctx, uint64_t n_buckets, const uint32_t *flags, cons
  *             bns_classify_batch_packed_device when max_read_len is given AND no unit can hold more than 128 k-mers
  *             (mates * (max_read_len - seed span + 1) <= 128: no overflow list to read back).  Their inputs and outputs are the
  *             device's until `stream` has been waited for.  These have synchronised `stream` when they return:
- *             bns_load_table_device, bns_build_table_device, bns_build_add, bns_build_minimize_add, and the two classify calls
+ *             bns_load_table_device, bns_build_table_device, bns_build_add, bns_build_minimize_add, bns_build_count_add, and the two classify calls
  *             with max_read_len = 0 (the longest read is read back) or with units of more than 128 k-mers (the overflow count is).
- *             bns_build_add, bns_build_minimize_add and bns_windows_add first wait for the context's own stream (begin, seed, a
+ *             bns_build_add, bns_build_minimize_add, bns_build_count_add and bns_windows_add first wait for the context's own stream (begin, seed, a
  *             reset or an earlier grow worked there).
  *   WORKSPACE a context has ONE workspace (its counters, records, packed image, flag words, scratch, overflow list, tally and
  *             sketches), shared by all its calls.  Two calls on one context on different streams must not overlap: ordering them
@@ -486,6 +486,44 @@ int bns_build_minimize_begin(bns_ctx *ctx, uint32_t w, uint64_t n_buckets_hint);
 int bns_build_minimize_add(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bases,
                            void *stream);
 int bns_build_minimize_stats(const bns_ctx *ctx, uint64_t *out6);
+
+/* ---- fewest-genome minimizers (version 114): every window keeps the k-mer that the fewest genomes hold ----------------------------
+ * Every sequence carries a genome id, a u32 below 0xFFFFFFFF (`bonsai build -G`: the index of its file).  n(x) is the number of
+ * DISTINCT genome ids among the sequences that hold x as a valid k-mer: a k-mer that occurs five times in one genome, in one contig
+ * or in several, has n = 1.  With score(x) = (n(x) << 32) | F[x] a window selects the smallest (score, k-mer): fewer genomes, then
+ * the smaller taxid, then the smaller k-mer; windows, validity, w <= c and M's values (F[k-mer]) are those of the section above.  M is
+ * a function of the set of (sequence, genome id, taxid) triples: batch cuts, table sizes and grows change nothing, nor does the
+ * numbering of the ids so long as it keeps the partition of the sequences.
+ * The counts are a third stream of the SAME sequences, between the adds and the minimizing:
+ *   bns_build_count_begin   in an open, unfinished, unfailed session whose window is not beyond the comb and that is not minimizing
+ *                           (else BNS_ERR_STATE; a second begin too).  Freezes F -- bns_build_add and bns_build_seed return
+ *                           BNS_ERR_STATE from here on -- and allocates a zeroed count and stamp per bucket of F: no memory for them
+ *                           is BNS_ERR_TABLE, and the session stays as it was.
+ *   bns_build_count_add     bns_build_minimize_add's inputs plus a HOST array of n_seqs genome ids.  The ids must not decrease within
+ *                           the call, the first must be at least the last id of the previous call, none may be 0xFFFFFFFF: otherwise
+ *                           BNS_ERR_ARG with nothing enqueued and nothing changed.  One kernel launch per run of equal ids (a genome is
+ *                           counted once because every lane in flight carries ONE id: count_kernel, csrc/bns_fewest.hpp).  A k-mer that
+ *                           F does not hold fails the call with BNS_ERR_TABLE ("not part of the scored build") and faults nothing;
+ *                           after that only bns_build_end is accepted.  n_seqs == 0 counts as a batch.  Returns when the device is
+ *                           done with the batch.
+ *   bns_build_count_get     n(x) so far for n keys as the encoder emits them (host arrays), 0 for a key F does not hold.  From
+ *                           bns_build_count_begin until bns_build_end, also after bns_build_minimize_begin and bns_build_finish
+ *                           behind it; on the context's own stream.  (A bns_build_finish WITHOUT minimizing compacts the table the
+ *                           counts belong to: BNS_ERR_STATE from then on.)
+ *   bns_build_count_stats   out6 = {batches, launches (genome runs), distinct genome ids seen, positions looked up, the largest count,
+ *                           microseconds inside add}.
+ *   bns_build_minimize_begin_score  bns_build_minimize_begin with the score named: BNS_MINIMIZE_DEPTH is that call as it is;
+ *                           BNS_MINIMIZE_FEWEST needs bns_build_count_begin to have been called (else BNS_ERR_STATE), computes no
+ *                           depths and selects by the counts as they stand.  Any other score: BNS_ERR_ARG.
+ * Memory: 8 more bytes a bucket of F from bns_build_count_begin to bns_build_end. */
+#define BNS_MINIMIZE_DEPTH 0
+#define BNS_MINIMIZE_FEWEST 1
+int bns_build_count_begin(bns_ctx *ctx);
+int bns_build_count_add(bns_ctx *ctx, const char *d_bases, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bases,
+                        const uint32_t *h_genome, void *stream);
+int bns_build_count_get(bns_ctx *ctx, const uint64_t *h_keys, uint64_t n, uint32_t *h_counts);
+int bns_build_count_stats(const bns_ctx *ctx, uint64_t *out6);
+int bns_build_minimize_begin_score(bns_ctx *ctx, uint32_t w, uint64_t n_buckets_hint, int score);
 
 /* ---- window session (version 110): every window of L bases of every sequence, called as a read (`bonsai distrib`) -------------
  * With L = window_len, sequence s of n bases has max(0, n - L + 1) windows; window p is its bases [p, p + L).  The CALL of a window is
