@@ -96,6 +96,7 @@ def load():
         "bns_tally_read": (C.c_int, [vp, u64p, u64p, C.c_uint32, C.c_int]),
         "bns_table_tally": (C.c_int, [vp, u64p, u64p, C.c_uint32]),
         "bns_set_confidence": (C.c_int, [vp, C.c_uint64, C.c_uint64]),
+        "bns_set_min_hit_groups": (C.c_int, [vp, C.c_uint32]),
         "bns_sketch_enable": (C.c_int, [vp, C.c_uint32]),
         "bns_sketch_read": (C.c_int, [vp, u32p, vp, C.c_uint32, u32p, u32p, C.c_int]),
         "bns_classify_batch": (C.c_int, [vp, vp, u64p, C.c_uint64, C.c_int, u32p, u32p, u32p, u32p, u32p]),

@@ -10,7 +10,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 SRC = os.path.join(PKG, "csrc", "bns_api.hip")
 SRC_INFLATE = os.path.join(PKG, "csrc", "bns_inflate.hip")      # BGZF members inflated on the device: a translation unit of its own
-DEPS = [os.path.join(PKG, "csrc", f) for f in ("bns_api.hip", "bns_kernels.hip", "bns_kernels.hpp", "bns_claims.hpp", "bns_device.hpp", "bns_inflate.hip", "bns_inflate.hpp", "bns_inflate_wave.hpp", "bns_ingest.hip", "bns_gzstream.hip", "bns_tally.hpp", "bns_inspect.hpp", "bns_confidence.hpp", "bns_lines.hpp", "bns_minqual.hpp", "bns_dust.hpp", "bns_sketch.hpp", "bns_build.hpp", "bns_fewest.hpp", "bns_minimize.hpp", "bns_windows.hpp", "bns_hashers.hpp", "bns_table_plan.hpp", "bns_table_load.hpp", "bns_classify_plan.hpp", "bns_classify.hpp", "bns_text_plan.hpp")] + \
+DEPS = [os.path.join(PKG, "csrc", f) for f in ("bns_api.hip", "bns_kernels.hip", "bns_kernels.hpp", "bns_claims.hpp", "bns_device.hpp", "bns_inflate.hip", "bns_inflate.hpp", "bns_inflate_wave.hpp", "bns_ingest.hip", "bns_gzstream.hip", "bns_tally.hpp", "bns_inspect.hpp", "bns_confidence.hpp", "bns_lines.hpp", "bns_minqual.hpp", "bns_dust.hpp", "bns_sketch.hpp", "bns_hit_groups.hpp", "bns_build.hpp", "bns_fewest.hpp", "bns_minimize.hpp", "bns_windows.hpp", "bns_hashers.hpp", "bns_table_plan.hpp", "bns_table_load.hpp", "bns_classify_plan.hpp", "bns_classify.hpp", "bns_text_plan.hpp")] + \
        [os.path.join(ROOT, "include", "bonsai_amd.h")]
 OUT = os.path.join(PKG, "lib", "libbonsai_amd.so")
 

@@ -243,6 +243,11 @@ class Context:
         num, den = confidence_fraction(threshold)
         self._chk(self.L.bns_set_confidence(self.h, num, den), "bns_set_confidence")
 
+    def set_min_hit_groups(self, n):
+        """bns_set_min_hit_groups: every classify call leaves a unit unclassified unless at least n DISTINCT keys of it (all mates
+        together) are found in the table; n in [0, 64], 0 turns it off.  Applied behind set_confidence's walk; only the taxon changes."""
+        self._chk(self.L.bns_set_min_hit_groups(self.h, int(n)), "bns_set_min_hit_groups")
+
     def sketch_enable(self, max_taxa=65536):
         """bns_sketch_enable: a HyperLogLog sketch (4096 one-byte registers) of the distinct k-mers every classify call looks up, per
         taxon bin, for up to max_taxa bins; 0 frees them and turns it off.  Needs a loaded taxonomy (unless 0)."""

@@ -8,6 +8,7 @@
 #include "bns_inspect.hpp"
 #include "bns_confidence.hpp"
 #include "bns_sketch.hpp"
+#include "bns_hit_groups.hpp"
 #include "bns_text_plan.hpp"
 
 #include <dlfcn.h>
@@ -139,6 +140,8 @@ struct bns_ctx {
     // bns_set_confidence: theta = conf_num / conf_den (0: off); conf_hits: the hit stream of a launch whose caller wants none
     u64 conf_num = 0, conf_den = 1;
     DevBuf conf_hits;
+    // bns_set_min_hit_groups: a classified unit needs this many distinct found keys (bns_hit_groups.hpp); 0: off, 1: no effect
+    u32 min_hit_groups = 0;
     // bns_sketch_enable: one HyperLogLog sketch per bin a sample touches (bns_sketch.hpp); sketch_cap = max_taxa, 0: off.  While it is on
     // the hit stream of a launch whose caller wants none goes to conf_hits as well
     u32 sketch_cap = 0;
@@ -257,7 +260,7 @@ int ready(bns_ctx *ctx, bool need_table, bool need_tax)
 
 extern "C" {
 
-int bns_version(void) { return 114; }
+int bns_version(void) { return 115; }
 
 int bns_device_pci_bus_id(int device, char *out, int cap)
 {
@@ -676,9 +679,24 @@ int sketch_zero(bns_ctx *ctx)
     return BNS_OK;
 }
 
+// f(spaced, layout, MIN) for the passes that look a launch's k-mers up again (sketch_kernel, hit_groups_kernel): MIN is the minimizer
+// identity of the clustered layout, 0 for the others
+template <class F>
+void dispatch_reprobe(const bns_ctx *ctx, F &&f)
+{
+    const bool whole_key = ctx->table_canon && ctx->table_shift == 0 && ctx->table_len == ctx->table_k;    // (bns_probe_device's dispatch)
+    dispatch_sp_layout(ctx->spaced, ctx->layout, [&](auto sp, auto ly) {
+        if constexpr (decltype(ly)::value == 2) {
+            if (!whole_key)           f(sp, ly, std::integral_constant<int, 1>{});
+            else if (ctx->table_wide) f(sp, ly, std::integral_constant<int, 2>{});
+            else                      f(sp, ly, std::integral_constant<int, 0>{});
+        } else f(sp, ly, std::integral_constant<int, 0>{});
+    });
+}
+
 // the k-mers of one classify launch into the sketches, on the launch's stream behind it.  p: the launch's parameters (offsets, units,
-// mates, hit stream, records; packed input: its words and flags); ASCII input is packed first, as bns_encode_batch_device does.
-int sketch_units(bns_ctx *ctx, ClassifyParams p, const char *d_bases, u64 n_reads, u64 total_bases, hipStream_t st)
+// mates, hit stream, records, and the packed image: classify_finish has packed ASCII input).
+int sketch_units(bns_ctx *ctx, const ClassifyParams &p, hipStream_t st)
 {
     const u32 n_bins = ctx->n_nodes + 1u;
     hipLaunchKernelGGL(sketch_seen_kernel, dim3(grid_for(ctx, p.n_units, 4)), dim3(256), 0, st, (const u32 *)p.hits, p.offsets, (u32)p.nmates,
@@ -687,23 +705,24 @@ int sketch_units(bns_ctx *ctx, ClassifyParams p, const char *d_bases, u64 n_read
     hipLaunchKernelGGL(sketch_assign_kernel, dim3(1), dim3(SKETCH_SCAN_BLOCK), 0, st, (const u8 *)ctx->sk_seen.p, (u32 *)ctx->sk_slot_of.p,
                        (u32 *)ctx->sk_slot_bin.p, n_bins, ctx->sketch_cap, (u32 *)ctx->sk_state.p);
     HIPCHK(ctx, hipGetLastError());
-    if (d_bases) {
-        const int rc = pack_reads(ctx, d_bases, p.offsets, n_reads, total_bases, st);
-        if (rc != BNS_OK) return rc;
-        p.words = (const u64 *)ctx->words.p; p.nmask = (const u32 *)ctx->nmask.p;
-    }
     const unsigned grid = grid_for(ctx, p.n_units, 4);
     const u32 *slot_of = (const u32 *)ctx->sk_slot_of.p;
     u8 *regs = (u8 *)ctx->sk_regs.p;
-    const bool whole_key = ctx->table_canon && ctx->table_shift == 0 && ctx->table_len == ctx->table_k;    // (bns_probe_device's dispatch)
-    dispatch_sp_layout(ctx->spaced, ctx->layout, [&](auto sp, auto ly) {
-        constexpr bool SP = decltype(sp)::value;
-        constexpr int LY = decltype(ly)::value;
-        if constexpr (LY == 2) {
-            if (!whole_key)           hipLaunchKernelGGL((sketch_kernel<SP, 2, 1>), dim3(grid), dim3(256), 0, st, p, slot_of, regs);
-            else if (ctx->table_wide) hipLaunchKernelGGL((sketch_kernel<SP, 2, 2>), dim3(grid), dim3(256), 0, st, p, slot_of, regs);
-            else                      hipLaunchKernelGGL((sketch_kernel<SP, 2, 0>), dim3(grid), dim3(256), 0, st, p, slot_of, regs);
-        } else hipLaunchKernelGGL((sketch_kernel<SP, LY, 0>), dim3(grid), dim3(256), 0, st, p, slot_of, regs);
+    dispatch_reprobe(ctx, [&](auto sp, auto ly, auto mn) {
+        hipLaunchKernelGGL((sketch_kernel<decltype(sp)::value, decltype(ly)::value, decltype(mn)::value>), dim3(grid), dim3(256), 0, st, p, slot_of, regs);
+    });
+    HIPCHK(ctx, hipGetLastError());
+    return BNS_OK;
+}
+
+// bns_set_min_hit_groups: the taxa of the launch's records zeroed where a unit has fewer distinct found keys, on the launch's stream
+// behind the confidence walk.  p: the launch's parameters, with the packed image.
+int hit_groups_units(bns_ctx *ctx, const ClassifyParams &p, hipStream_t st)
+{
+    const unsigned grid = grid_for(ctx, (p.n_units + HG_GROUP - 1) / HG_GROUP, 4);
+    const u32 n_min = ctx->min_hit_groups;
+    dispatch_reprobe(ctx, [&](auto sp, auto ly, auto mn) {
+        hipLaunchKernelGGL((hit_groups_kernel<decltype(sp)::value, decltype(ly)::value, decltype(mn)::value>), dim3(grid), dim3(256), 0, st, p, n_min);
     });
     HIPCHK(ctx, hipGetLastError());
     return BNS_OK;
@@ -832,6 +851,16 @@ int bns_set_confidence(bns_ctx *ctx, uint64_t num, uint64_t den)
     if (!ctx->nodes) return fail(ctx, BNS_ERR_STATE, "no taxonomy loaded (bns_load_taxonomy)");
     const u64 g = std::gcd(num, den);                // (the same theta; small terms keep the device's exact ceil on its short path)
     ctx->conf_num = num / g; ctx->conf_den = den / g;
+    return BNS_OK;
+}
+
+int bns_set_min_hit_groups(bns_ctx *ctx, uint32_t n)
+{
+    if (!ctx) return BNS_ERR_ARG;
+    if (ctx->build) return fail(ctx, BNS_ERR_STATE, "bns_set_min_hit_groups while a build session is open (bns_build_end)");
+    if (ctx->windows) return fail(ctx, BNS_ERR_STATE, "bns_set_min_hit_groups while a window session is open (bns_windows_end)");
+    if (n > HG_MAX) return fail(ctx, BNS_ERR_ARG, "bns_set_min_hit_groups: n must be in [0, 64]");
+    ctx->min_hit_groups = n;
     return BNS_OK;
 }
 

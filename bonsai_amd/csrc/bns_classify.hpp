@@ -10,7 +10,8 @@
 namespace {
 
 int tally_units(bns_ctx *ctx, const u32 *d_taxon, u64 n_units, hipStream_t st, bool neg);                               // bns_api.hip
-int sketch_units(bns_ctx *ctx, ClassifyParams p, const char *d_bases, u64 n_reads, u64 total_bases, hipStream_t st);   // bns_api.hip
+int sketch_units(bns_ctx *ctx, const ClassifyParams &p, hipStream_t st);                                                // bns_api.hip
+int hit_groups_units(bns_ctx *ctx, const ClassifyParams &p, hipStream_t st);                                            // bns_api.hip
 int dust_image_span(bns_ctx *ctx, const u64 *words, const u32 *nmask, const u64 *offsets, u64 n_seqs, u64 lo, u64 hi, hipStream_t st);   // bns_dust.hpp
 
 void fill_params(const bns_ctx *ctx, ClassifyParams &p)
@@ -229,23 +230,30 @@ int classify_overflow_pass(bns_ctx *ctx, const ClassifyIn &in, const ClassifyLau
     return BNS_OK;
 }
 
-// confidence walk, the records split into the caller's arrays, tally and sketches
+// confidence walk, minimum hit groups, the records split into the caller's arrays, tally and sketches
 int classify_finish(bns_ctx *ctx, const ClassifyIn &in, const UnitOut &out, const ClassifyLaunch &L)
 {
     hipStream_t st = L.st;
     const u64 n_units = L.n_units;
+    const bool hit_groups = ctx->min_hit_groups >= 2;    // (1 changes nothing: a taxon implies a hit)
+    ClassifyParams p = L.p;
+    if ((hit_groups || ctx->sketch_cap) && in.bases) {   // both passes walk the packed image: ASCII input is packed, once
+        BNS_RC(pack_reads(ctx, in.bases, in.offsets, in.n_reads, in.total_bases, st));
+        p.words = (const u64 *)ctx->words.p; p.nmask = (const u32 *)ctx->nmask.p;
+    }
     if (ctx->conf_num) {                             // bns_set_confidence: the taxa of the records walked up to theta's clade
         hipLaunchKernelGGL(confidence_kernel, dim3(grid_for(ctx, (n_units + CONF_GROUP - 1) / CONF_GROUP, 4)), dim3(256), 0, st, (uint4 *)ctx->records.p,
                            (const u64 *)in.offsets, (u32)L.nm, (const u32 *)L.p.hits, (u64)n_units, (const TaxNode *)ctx->nodes, ctx->n_nodes, ctx->conf_num,
                            ctx->conf_den);
         HIPCHK(ctx, hipGetLastError());
     }
+    if (hit_groups) BNS_RC(hit_groups_units(ctx, p, st));   // bns_set_min_hit_groups: taxon 0 below n distinct found keys
     hipLaunchKernelGGL(unpack_kernel, dim3(grid_for(ctx, n_units, 256)), dim3(256), 0, st, (const uint4 *)ctx->records.p, (u64)n_units,
                        out.taxon, out.missing, out.ambig, out.n_hits);
     HIPCHK(ctx, hipGetLastError());
     BNS_RC(tally_units(ctx, out.taxon, n_units, st, false));   // (every classifying entry point comes through here, once per unit)
     if (!ctx->sketch_cap) return BNS_OK;
-    return sketch_units(ctx, L.p, in.bases, in.n_reads, in.total_bases, st);
+    return sketch_units(ctx, p, st);
 }
 
 int classify_device_impl(bns_ctx *ctx, const ClassifyIn &in0, const UnitOut &out, void *stream)

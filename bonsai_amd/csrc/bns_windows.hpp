@@ -450,6 +450,7 @@ int windows_begin(bns_ctx *ctx, u32 window_len, u32 pair_cap, u64 num = 0, u64 d
     if (den == 0 || num > den) return fail(ctx, BNS_ERR_ARG, "confidence num / den: den > 0 and num <= den");
     if (ctx->windows) return fail(ctx, BNS_ERR_STATE, "a window session is already open (bns_windows_end)");
     if (ctx->dust_w) return fail(ctx, BNS_ERR_STATE, "bns_windows_begin while low-complexity masking is on (bns_set_dust): a window's call is classify's call of that substring as a read, and the mask of a substring is not the genome's mask restricted to it");
+    if (ctx->min_hit_groups) return fail(ctx, BNS_ERR_STATE, "bns_windows_begin while a minimum of hit groups is set (bns_set_min_hit_groups): a window's distinct-key count cannot be read from the session's prefix ranges");
     int rc = windows_ready(ctx, window_len);
     if (rc != BNS_OK) return rc;
     if (pair_cap == 0) return fail(ctx, BNS_ERR_ARG, "pair_cap is 0");

@@ -425,6 +425,11 @@ void set_confidence(ClassifierGeneric &c, u64 num, u64 den)
     for (bns_ctx *cx : c.ctxs_) chk(cx, bns_set_confidence(cx, num, den), "bns_set_confidence");
 }
 
+void set_min_hit_groups(ClassifierGeneric &c, unsigned n)
+{
+    for (bns_ctx *cx : c.ctxs_) chk(cx, bns_set_min_hit_groups(cx, n), "bns_set_min_hit_groups");
+}
+
 void set_dust(ClassifierGeneric &c, unsigned level)
 {
     for (bns_ctx *cx : c.ctxs_) chk(cx, bns_set_dust(cx, level ? 64u : 0u, level), "bns_set_dust");

@@ -339,6 +339,9 @@ using Classifier = ClassifierGeneric;
 
 // `bonsai classify -t`: the confidence threshold num / den on every context of the classifier (bns_set_confidence), before the first unit
 void set_confidence(ClassifierGeneric &c, u64 num, u64 den);
+// `bonsai classify -M`: a called unit needs n distinct found keys, on every context of the classifier (bns_set_min_hit_groups), before
+// the first unit; it acts on the device behind every classify launch, so every input form is covered
+void set_min_hit_groups(ClassifierGeneric &c, unsigned n);
 // `bonsai classify -Q`: a base whose Phred+33 quality is below q counts as 'N', on every context of the classifier
 // (bns_set_min_base_quality: the text the device parses) and in pack_chunk (the records the host parser yields), before the first unit
 void set_min_base_quality(ClassifierGeneric &c, unsigned q);

@@ -51,6 +51,8 @@ void usage(const char *exe)
                  "-U:\tTaxa that can have a sketch per GPU context, 4 KiB each [65536]; beyond that a taxon's k-mers are not counted (a warning says so).\n"
                  "-t:\tConfidence threshold in [0, 1] (digits, at most 9 after the point) [0]: a read (pair) is called at the first of its\n"
                  "\ttaxon and the taxon's ancestors whose clade holds at least that fraction of its k-mers, else unclassified.\n"
+                 "-M:\tMinimum hit groups, an integer in [0, 64] [0: off]: a read (pair) is called only when at least that many DISTINCT k-mers\n"
+                 "\tof it (both mates together) are found in the db; a k-mer found at many positions counts once.  Applied after -t.\n"
                  "-Q:\tMinimum base quality, an integer in [0, 93] [0: off]: a base whose Phred+33 quality is lower counts as N, so no k-mer\n"
                  "\tover it is looked up (FASTQ records; FASTA has no quality).  Not for a read container: mask with `bonsai pack -Q`.\n"
                  "-m:\tMask low-complexity sequence at this level, an integer in [1, 1000] (dustmasker's default: 20) [off]: symmetric DUST,\n"
@@ -98,6 +100,17 @@ bool parse_min_quality(const char *s, unsigned &q)
     return true;
 }
 
+// `-M`: an integer in [0, 64], digits only
+bool parse_min_hit_groups(const char *s, unsigned &n_min)
+{
+    unsigned v = 0;
+    int n = 0;
+    for (; *s >= '0' && *s <= '9'; ++s, ++n) { v = v * 10 + (unsigned)(*s - '0'); if (v > 64) return false; }
+    if (*s || !n) return false;
+    n_min = v;
+    return true;
+}
+
 int classify_main(int argc, char *argv[])
 {
     int co, num_threads = std::min(4, bns::usable_cpus()), emit_kraken = 1, emit_fastq = 0, emit_all = 0, chunk_size = 1 << 24;
@@ -110,11 +123,11 @@ int classify_main(int argc, char *argv[])
     std::FILE *ofp = stdout, *taxon_fp = nullptr, *report_fp = nullptr;
     const char *names_path = nullptr;
     unsigned long long conf_num = 0, conf_den = 1;
-    unsigned min_qual = 0, dust_level = 0;
+    unsigned min_qual = 0, dust_level = 0, min_hit_groups = 0;
     bool distinct = false, coverage = false;
     long sketch_taxa = 65536;
     if (argc < 4) usage(argv[0]);
-    while ((co = getopt(argc, argv, "Cc:p:o:S:afFkKg:L:NP:b:R:n:t:Q:m:udU:h?")) >= 0) {
+    while ((co = getopt(argc, argv, "Cc:p:o:S:afFkKg:L:NP:b:R:n:t:Q:m:M:udU:h?")) >= 0) {
         switch (co) {
             case 'h': case '?': usage(argv[0]); break;
             case 'C': canonicalize = false; break;
@@ -154,6 +167,12 @@ int classify_main(int argc, char *argv[])
                 break;
             case 'm':
                 if (!parse_dust_level(optarg, dust_level)) { std::fprintf(stderr, DUST_LEVEL_MSG, optarg); return EXIT_FAILURE; }
+                break;
+            case 'M':
+                if (!parse_min_hit_groups(optarg, min_hit_groups)) {
+                    std::fprintf(stderr, "[E] -M: the minimum number of hit groups must be an integer in [0, 64], not '%s'\n", optarg);
+                    return EXIT_FAILURE;
+                }
                 break;
             case 'S': break;
             case 'g': devices = optarg; break;
@@ -233,6 +252,7 @@ int classify_main(int argc, char *argv[])
         if (conf_num) bns::set_confidence(c, conf_num, conf_den);
         if (min_qual) bns::set_min_base_quality(c, min_qual);
         if (dust_level) bns::set_dust(c, dust_level);
+        if (min_hit_groups) bns::set_min_hit_groups(c, min_hit_groups);
         if (report_fp) bns::enable_tally(c);
         if (distinct) bns::enable_sketch(c, (bns::u32)sketch_taxa);
         c.coverage_on_ = coverage;

@@ -230,6 +230,24 @@ int bns_table_tally(bns_ctx *ctx, uint64_t *direct, uint64_t *clade, uint32_t le
  * nothing is launched or allocated.  Reloading the taxonomy keeps the setting.  bns_resolve_batch and bns_probe* are not affected. */
 int bns_set_confidence(bns_ctx *ctx, uint64_t num, uint64_t den);
 
+/* ---- minimum hit groups (what `bonsai classify -M` sets; version 115) ---------------------------------------------------------------
+ * No reference counterpart, and no parity with Kraken 2's --minimum-hit-groups (runs of one minimizer) is claimed: this project's own
+ * definition, DESIGN.md.  For each unit, G = the number of DISTINCT keys among the k-mers of all its mates that classify looks up and
+ * finds in the table.  The key is what is looked up: the canonical k-mer, the forward k-mer when the encoder is not canonical, the
+ * spaced key of a spaced seed, nothing for a spaced seed without spaced_intended; over the image classify saw (after a minimum base
+ * quality and bns_set_dust).  A key found at several positions, or in both mates, counts once; no order enters.  After the vote, its
+ * overflow pass and the confidence walk, the taxon of a unit becomes 0 when it was not 0 and G < n.  Only the taxon changes: missing,
+ * ambig, n_hits and the hits stay.  Needs no taxonomy of its own: a taxon that is no node (0xFFFFFFFF included) is zeroed like any other.
+ * Every classifying entry point (those bns_tally_enable lists) applies it on the stream of the classify launch (hit_groups_kernel,
+ * behind confidence_kernel and before the results are unpacked), so the tally counts the new taxa; the sketches go by each k-mer's own
+ * value and do not change.  ASCII input is packed first (pack_kernel into the context's workspace; once when the sketches are on too);
+ * the hit stream is not needed.
+ * n in [0, 64], else BNS_ERR_ARG.  n = 0 (the default) and n = 1 (a taxon implies a hit) launch, allocate and read nothing.  While a
+ * build or window session is open: BNS_ERR_STATE; bns_windows_begin* return BNS_ERR_STATE while n > 0 (a window's distinct-key count
+ * cannot be read from the session's prefix ranges).  Per context; table and taxonomy reloads keep it.  bns_resolve_batch and bns_probe*
+ * are not affected. */
+int bns_set_min_hit_groups(bns_ctx *ctx, uint32_t n);
+
 /* ---- distinct k-mers per taxon (what `bonsai classify -R -u` reports) --------------------------------------------------------------
  * No reference counterpart (Kraken 2's --report-minimizer-data, KrakenUniq); defined in DESIGN.md.  One HyperLogLog sketch per bin.
  * What is counted: every unit a classify launch processes (the entry points bns_tally_enable lists), every k-mer classify looks up:
@@ -563,7 +581,7 @@ int bns_build_minimize_begin_score(bns_ctx *ctx, uint32_t w, uint64_t n_buckets_
  *                      add; ms3 receives the milliseconds summed over the *n_adds adds since the last call.  A session begun with
  *                      timing off: BNS_ERR_STATE.
  *   bns_windows_end    frees the session; legal at any point.  bns_destroy ends an open session.
- * add, read or timing without a session: BNS_ERR_STATE.  begin while bns_set_dust is on: BNS_ERR_STATE.  bns_set_min_base_quality does
+ * add, read or timing without a session: BNS_ERR_STATE.  begin while bns_set_dust or bns_set_min_hit_groups is on: BNS_ERR_STATE.  bns_set_min_base_quality does
  * not apply (sequences carry no quality); the bns_tally_enable tally and the sketches are not touched (as with bns_resolve_batch).
  * Without a session nothing is allocated or launched. */
 int bns_windows_begin(bns_ctx *ctx, uint32_t window_len, uint32_t pair_cap);
