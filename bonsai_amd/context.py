@@ -157,6 +157,10 @@ class Context:
     def table_warning(self):
         return self.L.bns_table_warning(self.h).decode()
 
+    # debug_set bit: classify_kernel takes a wavefront's work counter by its index & 7 instead of its XCD number, so that a grid of
+    # two workgroups (debug_claim_waves(8)) reaches all eight counters and goes from a dry one to the next; same results
+    DBG_SHARD_BY_WAVE = 0x200000
+
     def debug_set(self, bits):
         """test / profiling switches (BNS_DBG_* in bns_api.hip, bns_table_plan.hpp and bns_classify_plan.hpp); not part of the public header"""
         self._chk(self.L.bns_debug_set(self.h, bits), "bns_debug_set")

@@ -42,13 +42,13 @@ struct DevBuf {
 // ctx->small: the few device words the entry points share with their kernels.  Every entry point zeroes ITS words on its own
 // stream before use; nothing here persists across calls.
 struct SmallLayout {
-    u32 work_counter; u32 pad0[31];            // [0,128)   classify_kernel's claim counter, on a line of its own (80 M atomics/s)
-    u32 ovf_count, max_len; u32 pad1[30];      // [128,256) classify: units handed to the overflow kernel; longest read of the batch
-    unsigned long long load_cnt[8];            // [256,320) table load / device build counters
-    unsigned long long runs_cursor;            // [320,328) hit_runs_kernel's output cursor
-    unsigned long long lines_cursor;           // [328,336) lines_len_kernel: line bytes of the call so far
+    u32 work_counter[CLAIM_SHARDS][CLAIM_COUNTER_STRIDE];   // [0,1024)     classify_kernel's claim counters, one per XCD, each on a line of its own (one word: 86 M atomics/s)
+    u32 ovf_count, max_len; u32 pad1[30];      // [1024,1152) classify: units handed to the overflow kernel; longest read of the batch
+    unsigned long long load_cnt[8];            // [1152,1216) table load / device build counters
+    unsigned long long runs_cursor;            // [1216,1224) hit_runs_kernel's output cursor
+    unsigned long long lines_cursor;           // [1224,1232) lines_len_kernel: line bytes of the call so far
 };
-constexpr size_t SMALL_BYTES = 512;
+constexpr size_t SMALL_BYTES = 1536;
 constexpr size_t SMALL_CLASSIFY_ZERO = offsetof(SmallLayout, max_len) + sizeof(u32);   // what a classify call zeroes, in one memset
 static_assert(sizeof(SmallLayout) <= SMALL_BYTES, "ctx->small is allocated with SMALL_BYTES");
 static_assert(offsetof(SmallLayout, load_cnt) >= SMALL_CLASSIFY_ZERO, "classify's memset must not reach the other entry points' words");
@@ -295,12 +295,12 @@ int bns_debug_last_classify_form(const bns_ctx *ctx, uint32_t *out, int n)
     return c;
 }
 #ifdef BNS_WAVE_TIMES
-// measurement builds only: the WAVE_STAMPS (5) wall-clock stamps of each of the 8192 wavefronts of the last classify_kernel launch
-extern "C" int bns_debug_wave_times(bns_ctx *ctx, unsigned long long *out40960)
+// measurement builds only: the WAVE_STAMPS (8) words (five wall-clock stamps, three claim-wait figures) of each of the 8192 wavefronts of the last classify_kernel launch
+extern "C" int bns_debug_wave_times(bns_ctx *ctx, unsigned long long *out65536)
 {
-    if (!ctx || !out40960) return BNS_ERR_ARG;
+    if (!ctx || !out65536) return BNS_ERR_ARG;
     if (hipDeviceSynchronize() != hipSuccess) return BNS_ERR_HIP;
-    if (hipMemcpyFromSymbol(out40960, HIP_SYMBOL(bns::g_wave_times), sizeof(bns::g_wave_times)) != hipSuccess) return BNS_ERR_HIP;
+    if (hipMemcpyFromSymbol(out65536, HIP_SYMBOL(bns::g_wave_times), sizeof(bns::g_wave_times)) != hipSuccess) return BNS_ERR_HIP;
     return BNS_OK;
 }
 #endif

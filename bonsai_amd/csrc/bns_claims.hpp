@@ -18,12 +18,19 @@ namespace bns {
 //                  otherwise, staggered                1 + (w mod full) units, the base their prefix sum: the wavefronts'
 //                                                      later claims are then spread over one claim's duration from the start,
 //                                                      as they are in the steady state, instead of coming in step
-// dynamic part   claim index d (the work counter counts claims from 0) stands for the `full` units from dyn_base + d * full,
-//                dyn_base = the units of the static part.  A base at or past n_units means the batch is dealt out.
+// dynamic part   claim index g (claims are counted from 0) stands for the `full` units from dyn_base + g * full, dyn_base = the
+//                units of the static part.  A base at or past n_units means: past the end.
+//                The indices are handed out by CLAIM_SHARDS work counters, one per XCD, each on a cache line of its own: draw d
+//                from counter x is claim g = CLAIM_SHARDS * d + x, so every counter holds an interleaved eighth of the one tiling
+//                and none of them a stretch of its own that could finish late.  A wavefront draws from its XCD's counter; when that
+//                one is past the end (it stays so: a counter only grows) it goes on to the next, and after the eighth the batch is
+//                dealt out.  Draws past the end: one per wavefront and counter at the most, so the farthest index lies
+//                CLAIM_SHARDS * wavefronts claims behind the last -- with 8192 wavefronts 2.03 M units, which is why a batch has
+//                fewer than 2^32 - 2^22 units: the 32-bit base does not wrap.
 // Every claim is at most `full` units (full * mates + 1 offsets must fit one 64-lane load); the last one is cut at n_units by
 // the caller (claim_cnt).
 // (Claims that shrink over the end of the batch -- 16, 8, 4 units over the last 32 per resident wavefront -- were built and
-// measured: 8192 wavefronts draw them faster than one counter hands them out, docs/KERNEL_NOTES.md "Dealing the batch out".)
+// measured on ONE counter: 8192 wavefronts draw them faster than it hands them out, docs/KERNEL_NOTES.md "Dealing the batch out".)
 
 // units of wavefronts [0, w) of a staggered static part
 BNS_CLAIMS_HD uint32_t claim_stagger_prefix(uint32_t w, uint32_t full)
@@ -39,6 +46,11 @@ BNS_CLAIMS_HD void claim_static(uint32_t w, uint32_t chunk, uint32_t full, uint3
     base = claim_stagger_prefix(w, full);
     size = 1u + w % full;
 }
+
+// draw d from work counter x -> the dynamic claim it stands for
+constexpr uint32_t CLAIM_SHARDS = 8;
+constexpr uint32_t CLAIM_COUNTER_STRIDE = 32;                // u32 words from one counter to the next: a 128-byte line each
+BNS_CLAIMS_HD uint32_t claim_shard_global(uint32_t d, uint32_t x) { return d * CLAIM_SHARDS + x; }
 
 // dynamic claim d -> its first unit
 BNS_CLAIMS_HD uint32_t claim_dynamic_base(uint32_t dyn_base, uint32_t d, uint32_t full) { return dyn_base + d * full; }

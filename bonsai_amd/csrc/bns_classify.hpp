@@ -164,7 +164,7 @@ int classify_prepare(bns_ctx *ctx, const ClassifyIn &in, const UnitOut &out, Cla
 {
     hipStream_t st = L.st;
     SmallLayout *sm = (SmallLayout *)ctx->small.p;
-    HIPCHK(ctx, hipMemsetAsync(sm, 0, SMALL_CLASSIFY_ZERO, st));   // work_counter, ovf_count, max_len in one memset
+    HIPCHK(ctx, hipMemsetAsync(sm, 0, SMALL_CLASSIFY_ZERO, st));   // the eight work counters, ovf_count, max_len in one memset
     u32 max_read_len = in.max_read_len;
     if (max_read_len == 0) {
         hipLaunchKernelGGL(max_len_kernel, dim3(grid_for(ctx, in.n_reads, 256)), dim3(256), 0, st, in.offsets, (u64)in.n_reads, &sm->max_len);
@@ -188,7 +188,7 @@ int classify_prepare(bns_ctx *ctx, const ClassifyIn &in, const UnitOut &out, Cla
     BNS_RC(ensure(ctx, ctx->records, (size_t)L.n_units * 16));
     p.records = (uint4 *)ctx->records.p;
     p.ovf_count = &sm->ovf_count; p.ovf_list = L.can_overflow ? (u64 *)ctx->ovf_list.p : nullptr;
-    p.work_counter = &sm->work_counter;
+    p.work_counter = &sm->work_counter[0][0];
     // reference behaviour for a spaced seed through the string for_each: nothing is emitted
     p.emit_none = (ctx->spaced && !ctx->spaced_intended) ? 1 : 0;
     return BNS_OK;

@@ -15,6 +15,7 @@ namespace bns {
 // bns_debug_set bits a classify launch reads (tests and profiling; 0 in production; the other bits: bns_api.hip, bns_table_plan.hpp)
 constexpr int BNS_DBG_OVC_OFF = 0x2000;             // classify: never the cooperative overflow lookup (A/B of the two forms)
 constexpr int BNS_DBG_OVC_ON = 0x8000;              // classify: always the cooperative overflow lookup
+constexpr int BNS_DBG_SHARD_BY_WAVE = 0x200000;     // classify_kernel: a wavefront's work counter by its index & 7 instead of its XCD (tests: two workgroups reach all eight counters and the stealing; same results)
 
 constexpr u32 LDS_CAP = 128;   // distinct taxa per unit held in LDS; beyond that the overflow kernel takes over
 

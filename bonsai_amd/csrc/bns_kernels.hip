@@ -1351,8 +1351,10 @@ __device__ __forceinline__ void classify_unit(const ClassifyParams &p, u64 u, u6
 }
 
 #ifdef BNS_WAVE_TIMES
-// per wavefront: kernel entry, first claim in hand, first unit finished, last unit finished, exit (tools/wave_times.py)
-constexpr int WAVE_STAMPS = 5;
+// per wavefront: kernel entry, first claim in hand, first unit finished, last unit finished, exit; then the ticks it spent between
+// asking to look at a claim and having it (the wait in front of the readfirstlane of next_v), summed over its looks, the number of
+// looks, and the longest of them (tools/wave_times.py)
+constexpr int WAVE_STAMPS = 8;
 __device__ unsigned long long g_wave_times[WAVE_STAMPS * 8192];
 #endif
 template <bool SPACED, int LAYOUT, int KT, int NM, int SPAN = 8, bool OVC = false, bool WIDE = false, bool PACKED = false>
@@ -1380,7 +1382,7 @@ __global__ __launch_bounds__(256, (ClassifyTraits<SPACED, LAYOUT, KT, NM, SPAN, 
     struct TimeStamp {
         unsigned long long t[WAVE_STAMPS]; u32 slot;
         __device__ ~TimeStamp() { if ((threadIdx.x & 63u) == 0 && slot < 8192u) { t[4] = wall_clock64(); for (int i = 0; i < WAVE_STAMPS; ++i) g_wave_times[WAVE_STAMPS * slot + i] = t[i]; } }
-    } stamp{{(unsigned long long)wall_clock64(), 0, 0, 0, 0}, blockIdx.x * 4u + (u32)wv};
+    } stamp{{(unsigned long long)wall_clock64(), 0, 0, 0, 0, 0, 0, 0}, blockIdx.x * 4u + (u32)wv};
 #endif
     // unit indices are 32-bit here (bns_classify_batch_device rejects batches of 2^32 units or more)
     const u32 n_units = (u32)p.n_units;
@@ -1399,9 +1401,38 @@ __global__ __launch_bounds__(256, (ClassifyTraits<SPACED, LAYOUT, KT, NM, SPAN, 
     // prefetch.  The first 256 bases of the next unit travel while a unit is classified.  Offsets travel through VECTOR loads so
     // that LDS waits (lgkmcnt) never stall on them.
     const u32 FULL = classify_chunk(nm);
-    // claim index of the next chunk (lane 0 holds the result).  No counter: the batch is dealt out by the static claims alone, and claim 0
-    // lies past its end (claim_base = n_units).
-    auto claim = [&]() -> u32 { u32 *const c = cold_params()->work_counter; return c && lane == 0 ? atomicAdd(c, 1u) : 0u; };
+    // The work counter a wavefront draws from is its XCD's, one of CLAIM_SHARDS (bns_claims.hpp): eight words hand out eight times
+    // what one does, and an atomic on the XCD's own word comes back sooner.  Placement changes speed only: whichever counter a draw
+    // comes from, it stands for a claim of the one tiling.  (BNS_DBG_SHARD_BY_WAVE: the wavefront's index instead of the XCD.)
+    // The home shard is read at entry and once more at the end of every run of chunks, where the wavefront has to know when it is
+    // back at home (a wavefront does not change its XCD): a register read there instead of an SGPR held across the unit loop.
+    auto home_shard = [&]() -> u32 {
+        u32 x;
+        asm("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 3)" : "=s"(x));
+        if (cold_params()->dbg & BNS_DBG_SHARD_BY_WAVE) x = blockIdx.x * 4u + (u32)wv;
+        return x & (CLAIM_SHARDS - 1u);
+    };
+    u32 shard = home_shard();
+    // draw of the next chunk from the shard's counter (lane 0 holds the result).  No counter: the batch is dealt out by the static claims
+    // alone, and every claim lies past its end (claim_base = n_units).
+    auto claim = [&]() -> u32 {
+        u32 *const c = cold_params()->work_counter;
+        return c && lane == 0 ? atomicAdd(c + shard * CLAIM_COUNTER_STRIDE, 1u) : 0u;
+    };
+    // looking at a claim: the index asked for earlier, wave-uniform.  The wait for the atomic's return is here.
+    auto look = [&](u32 v) -> u32 {
+#ifdef BNS_WAVE_TIMES                        // (the wait, in wall-clock ticks: an asm statement, so that it stays between the two stamps)
+        const unsigned long long t0 = wall_clock64();
+        u32 d;
+        asm volatile("v_readfirstlane_b32 %0, %1" : "=s"(d) : "v"(v));
+        const unsigned long long dt = wall_clock64() - t0;
+        stamp.t[5] += dt; stamp.t[6] += 1u;
+        if (dt > stamp.t[7]) stamp.t[7] = dt;
+        return d;
+#else
+        return (u32)__builtin_amdgcn_readfirstlane((int)v);
+#endif
+    };
     // (the offsets pointer is taken from the kernarg segment at the point of use and advanced in SGPRs: kept as a per-lane address
     // across the kernel it cost two VGPRs -- or, in the instantiations at the 64-register limit, 8 bytes of scratch)
     auto load_offs = [&](u32 base, u32 cnt) -> u64 {
@@ -1415,64 +1446,82 @@ __global__ __launch_bounds__(256, (ClassifyTraits<SPACED, LAYOUT, KT, NM, SPAN, 
 #endif
     if (base >= n_units) return;
     cnt = claim_cnt(base, cnt, n_units);
-    u64 offs = load_offs(base, cnt);
-    Prefetch pre;
-    {
-        const u64 o0 = readlane64(offs, 0);
-        prefetch_clear<PACKED>(pre);
-        prefetch_issue<PACKED>(p, (u64)base * nm, o0, readlane((u32)offs, 1) - (u32)o0, pre);
-    }
     uint4 pend = make_uint4(0, 0, 0, 0);
     u32 pend_u = 0;
     bool pend_valid = false;
+    // A run of chunks from one shard: the first one's offsets and first bases are fetched in the open, every further one's under the
+    // chunk before it.  A wavefront has one run, and one more per shard it goes on to at the end of the batch.
     for (;;) {
-        u32 next_v = 0;
-        u32 nbase = 0xFFFFFFFFu;
-        u64 noffs = 0;
-        const u32 jload = cnt > 2u ? cnt - 2u : 0u;              // the unit in front of which the next claim is looked at: the last but one
-        for (u32 j = 0; j < cnt; ++j) {
-            if (j == jload) {
-                if (j == 0u) next_v = claim();                       // (a chunk of one or two units: asked for and looked at on the spot)
-                nbase = claim_dynamic_base(cold_params()->claim_base, (u32)__builtin_amdgcn_readfirstlane((int)next_v), FULL);
-                if (nbase < n_units) noffs = load_offs(nbase, claim_cnt(nbase, FULL, n_units));
-            }
-            Prefetch npre;
-            // Issued by classify_unit behind the unit's first pack, so that the pack's wait for `pre` (here since the previous unit's
-            // last probe) is not a wait for these, and the first wait that covers them is the first bucket fetch's own:
-            auto issue_next = [&]() __attribute__((always_inline)) {
-                // first 256 bases of the unit after this one: the next of the chunk, or the first of the next chunk
-                // (one load site for both: two, merged behind the branches, come out as loads into different registers and a copy --
-                // with a vmcnt(0) in front of it)
-                prefetch_clear<PACKED>(npre);
-                u64 n0 = 0, nr = 0;
-                u32 nL = 0;                                          // (no unit after this one: a read of no bases loads nothing)
-                if (j + 1u < cnt) {
-                    n0 = readlane64(offs, (int)((j + 1u) * nm));
-                    nL = readlane((u32)offs, (int)((j + 1u) * nm + 1u)) - (u32)n0;
-                    nr = (u64)(base + j + 1u) * nm;
-                } else if (nbase < n_units) {
-                    n0 = readlane64(noffs, 0);
-                    nL = readlane((u32)noffs, 1) - (u32)n0;
-                    nr = (u64)nbase * nm;
+        u64 offs = load_offs(base, cnt);
+        Prefetch pre;
+        {
+            const u64 o0 = readlane64(offs, 0);
+            prefetch_clear<PACKED>(pre);
+            prefetch_issue<PACKED>(p, (u64)base * nm, o0, readlane((u32)offs, 1) - (u32)o0, pre);
+        }
+        u32 nbase;
+        for (;;) {
+            u32 next_v = 0;
+            nbase = 0xFFFFFFFFu;
+            u64 noffs = 0;
+            const u32 jload = cnt > 2u ? cnt - 2u : 0u;              // the unit in front of which the next claim is looked at: the last but one
+            for (u32 j = 0; j < cnt; ++j) {
+                if (j == jload) {
+                    if (j == 0u) next_v = claim();                       // (a chunk of one or two units: asked for and looked at on the spot)
+                    nbase = claim_dynamic_base(cold_params()->claim_base, claim_shard_global(look(next_v), shard), FULL);
+                    if (nbase < n_units) noffs = load_offs(nbase, claim_cnt(nbase, FULL, n_units));
                 }
-                prefetch_issue<PACKED>(p, nr, n0, nL, npre);
-                if (j + 1u == jload) next_v = claim();               // the next chunk: looked at in front of the unit after this one
-                // The previous unit's record is stored next to the prefetch loads: gfx9 has one counter for loads and stores, so the
-                // first wait after a store waits for its acknowledgement too.
-                if (pend_valid && lane == 0) cold_params()->records[pend_u] = pend;
-            };
-            classify_unit<SPACED, LAYOUT, KT, NM, SPAN, OVC, WIDE, PACKED>(p, base + j, offs, j * nm, true, pre, ctr_keys, ctr_cnt, s_mh[wv] + MINB_LIST_U32,
-                                          s_mh[wv] + MINB_LIST_U32 + LDS_CAP, LDS_CAP, true, s_ring[wv], s_mh[wv], s_pk[wv], pend, pend_valid, issue_next);
-            pend_u = base + j;
-            pre = npre;
+                Prefetch npre;
+                // Issued by classify_unit behind the unit's first pack, so that the pack's wait for `pre` (here since the previous unit's
+                // last probe) is not a wait for these, and the first wait that covers them is the first bucket fetch's own:
+                auto issue_next = [&]() __attribute__((always_inline)) {
+                    // first 256 bases of the unit after this one: the next of the chunk, or the first of the next chunk
+                    // (one load site for both: two, merged behind the branches, come out as loads into different registers and a copy --
+                    // with a vmcnt(0) in front of it)
+                    prefetch_clear<PACKED>(npre);
+                    u64 n0 = 0, nr = 0;
+                    u32 nL = 0;                                          // (no unit after this one: a read of no bases loads nothing)
+                    if (j + 1u < cnt) {
+                        n0 = readlane64(offs, (int)((j + 1u) * nm));
+                        nL = readlane((u32)offs, (int)((j + 1u) * nm + 1u)) - (u32)n0;
+                        nr = (u64)(base + j + 1u) * nm;
+                    } else if (nbase < n_units) {
+                        n0 = readlane64(noffs, 0);
+                        nL = readlane((u32)noffs, 1) - (u32)n0;
+                        nr = (u64)nbase * nm;
+                    }
+                    prefetch_issue<PACKED>(p, nr, n0, nL, npre);
+                    if (j + 1u == jload) next_v = claim();               // the next chunk: looked at in front of the unit after this one
+                    // The previous unit's record is stored next to the prefetch loads: gfx9 has one counter for loads and stores, so the
+                    // first wait after a store waits for its acknowledgement too.
+                    if (pend_valid && lane == 0) cold_params()->records[pend_u] = pend;
+                };
+                classify_unit<SPACED, LAYOUT, KT, NM, SPAN, OVC, WIDE, PACKED>(p, base + j, offs, j * nm, true, pre, ctr_keys, ctr_cnt, s_mh[wv] + MINB_LIST_U32,
+                                              s_mh[wv] + MINB_LIST_U32 + LDS_CAP, LDS_CAP, true, s_ring[wv], s_mh[wv], s_pk[wv], pend, pend_valid, issue_next);
+                pend_u = base + j;
+                pre = npre;
 #ifdef BNS_WAVE_TIMES
-            stamp.t[3] = wall_clock64();
-            if (!stamp.t[2]) stamp.t[2] = stamp.t[3];
+                stamp.t[3] = wall_clock64();
+                if (!stamp.t[2]) stamp.t[2] = stamp.t[3];
 #endif
+            }
+            if (nbase >= n_units) break;
+            base = nbase; offs = noffs;
+            cnt = claim_cnt(base, FULL, n_units);     // (recomputed: nothing but the base is carried over)
+        }
+        // Past the end: this shard is dry, and stays so (its counter only grows).  On to the next one, on the spot.  Nothing here waits
+        // for another wavefront.  It ends: every pass leaves one more dry shard behind, the first was the wavefront's own, so after
+        // seven passes at the most `shard` is back at home, all eight are dry and the batch is dealt out -- seven extra atomics per
+        // wavefront, at the very end of the launch.  (Without a counter nothing is drawn: the static claims were the batch.)
+        if (!cold_params()->work_counter) break;
+        const u32 home = home_shard();
+        while ((shard = (shard + 1u) & (CLAIM_SHARDS - 1u)) != home) {
+            nbase = claim_dynamic_base(cold_params()->claim_base, claim_shard_global(look(claim()), shard), FULL);
+            if (nbase < n_units) break;
         }
         if (nbase >= n_units) break;
-        base = nbase; offs = noffs;
-        cnt = claim_cnt(base, FULL, n_units);     // (recomputed: nothing but the base is carried over)
+        base = nbase;
+        cnt = claim_cnt(base, FULL, n_units);
     }
     if (pend_valid && lane == 0) cold_params()->records[pend_u] = pend;
 }

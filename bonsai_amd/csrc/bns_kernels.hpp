@@ -71,7 +71,7 @@ struct ClassifyParams {
     u32 *taxon, *missing, *ambig, *n_hits, *hits;
     uint4 *records;     // classify_kernel writes one {taxon, missing, ambig, n_hits} record per unit; unpack_kernel splits it
     u32 *ovf_count;
-    u32 *work_counter;  // classify_kernel: the next dynamic claim index (bns_claims.hpp), from 0
+    u32 *work_counter;  // classify_kernel: the first of the CLAIM_SHARDS work counters, CLAIM_COUNTER_STRIDE words apart, each the next draw of its shard, from 0 (bns_claims.hpp); null: no dynamic claims
     u32 chunk;          // units per claim: classify_chunk(nmates); fewer when the batch is small -- every wavefront then takes one such claim by its index and none from the counter
     u32 claim_base;     // dynamic claim d stands for the units from claim_base + d * chunk (written by launch_classify: the units its grid's static claims take)
     u64 *ovf_list;

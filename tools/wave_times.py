@@ -2,7 +2,11 @@
 """Where does each of the 8192 wavefronts of one classify_kernel launch spend its time?  (measurement build -DBNS_WAVE_TIMES; run
 with BONSAI_AMD_LIB=<that build>)  Five stamps per wavefront: kernel entry, first claim in hand, first unit finished, last unit
 finished, exit.  Prints the percentiles of each as fractions of the kernel's duration, and the share of wave-time (wavefronts x
-duration) that lies before a wavefront's first unit has finished and after its last one has."""
+duration) that lies before a wavefront's first unit has finished and after its last one has.
+Three more words per wavefront say what it waited for its claims: the ticks between asking to look at a claim and having it (the
+wait in front of the readfirstlane of the atomic's result), summed over its looks, the number of looks, and its longest look.
+Printed as "claim_wait": the share of wave-time, the median over the wavefronts of a wavefront's mean look, and the longest look
+of the launch, in wall-clock ticks and in microseconds (the wall clock runs at 100 MHz)."""
 import ctypes, json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,6 +15,8 @@ import torch
 import bench, bonsai_amd
 
 STAMPS = ("entry", "first_claim", "first_unit_done", "last_unit_done", "exit")
+WORDS = 8                                  # WAVE_STAMPS of the measurement build: the five stamps, then look ticks, looks, longest look
+TICK_US = 0.01
 PCTS = (0, 1, 5, 25, 50, 75, 95, 99, 100)
 
 sys.argv = [sys.argv[0], "--no-cpu", "--no-probe", "--steps", "3", "--warmup", "1"] + sys.argv[1:]
@@ -18,11 +24,12 @@ sys.argv = [sys.argv[0], "--no-cpu", "--no-probe", "--steps", "3", "--warmup", "
 orig = bonsai_amd.Context
 class Keep(orig):
     def close(self):
-        t = np.zeros(len(STAMPS) * 8192, dtype=np.uint64)
+        t = np.zeros(WORDS * 8192, dtype=np.uint64)
         self.L.bns_debug_wave_times.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self.L.bns_debug_wave_times(self.h, t.ctypes.data)
-        t = t.reshape(8192, len(STAMPS)).astype(np.int64)
+        t = t.reshape(8192, WORDS).astype(np.int64)
         t = t[t[:, 4] > 0]
+        look_ticks, looks, look_max = t[:, 5], t[:, 6], t[:, 7]
         base, end = t[:, 0].min(), t[:, 4].max()
         dur = float(end - base)
         f = (t - base) / dur
@@ -42,6 +49,19 @@ class Keep(orig):
         # what a unit takes in the steady state, for scale: (last - first unit done) over the units in between is not known per
         # wavefront, but the first unit's own time against the batch mean is
         out["first_unit_ticks_median"] = float(np.median(t[:, 2] - t[:, 1]))
+        asked = looks > 0
+        per_look = look_ticks[asked] / looks[asked]
+        out["claim_wait"] = {
+            "looks": int(looks.sum()),
+            "wave_time_share": round(float(look_ticks.sum() / (n * dur)), 5),
+            "resident_time_share": round(float(look_ticks.sum() / float((t[:, 4] - t[:, 0]).sum())), 5),
+            "per_look_ticks_mean": round(float(look_ticks.sum() / max(1, int(looks.sum()))), 3),
+            "per_look_ticks_median_of_wave_means": round(float(np.median(per_look)), 3) if asked.any() else None,
+            "per_look_ticks_p95_of_wave_means": round(float(np.percentile(per_look, 95)), 3) if asked.any() else None,
+            "per_look_ticks_max": int(look_max.max()),
+            "per_look_us_median_of_wave_means": round(float(np.median(per_look)) * TICK_US, 4) if asked.any() else None,
+            "per_look_us_max": round(int(look_max.max()) * TICK_US, 3),
+        }
         print(json.dumps(out))
         # by XCD (block index mod 8 is the usual round-robin)
         blk = np.arange(8192)[: t.shape[0]] // 4
